@@ -30,12 +30,20 @@ k % world == rank (heifgpu_batch_opts), so the total work is fixed
 gather to one device (heifgpu_gather_tiles, xGMI peer copies) is not in the
 timed region.
 
-e2e (rank 0, default on): the PCIe-inclusive rate beside `value`: the same
+A plain run sets up, warms up, times the K steps (the roofline and
+stage_ms_per_step come from HIP events recorded in those same steps), writes
+the planes with --dump-outputs DIR (dump_outputs) and prints the line.
+--full adds what takes runs of its own, after the timed region: the bit-exact
+check of every image against the oracle (--verify), one decode alone
+(latency_ms_one_step, stage_ms_alone), e2e, cpu_baseline, the single-thread
+host parse, and with several ranks the tile-split gather and chain floor.
+
+e2e (--full, rank 0; off with --no-e2e): the PCIe-inclusive rate beside `value`: the same
 files re-parsed on the host (heifgpu_image_parse_many on a thread pool),
 flattened into pinned memory and uploaded (heifgpu_batch_prepare_ex, two
 batches reloaded alternately) while the previous batch decodes.
 
-cpu_baseline: the CPU oracle (oracle/, spec restatement; the reference Rust
+cpu_baseline (--full; off with --no-cpu-baseline): the CPU oracle (oracle/, spec restatement; the reference Rust
 path cannot decode pixels), built -march=native on the measuring host,
 decoding tiles on one thread per CPU this job may use (the cgroup quota) for
 ~10 s; the 1-core figure and the node's CPU count are reported beside it.
@@ -306,6 +314,41 @@ def verify_distinct(outs, files, info, stride, offset, threads) -> int:
     return len(outs)
 
 
+DUMP_SAMPLES = 12 << 20  # float32 samples a dump holds over all images (48 MiB)
+
+
+def dump_outputs(dst, outs, rank, world) -> None:
+    """`--dump-outputs DIR`: what the last timed step left in the caller's
+    planes, for comparing two builds output for output (the inputs depend on
+    the arguments alone).  DIR/y.npy, cb.npy, cr.npy: float32 [images, n], of
+    every image the samples at n positions of the flattened plane drawn by
+    default_rng((image index, plane)) (the whole plane where it has no more
+    than n samples); n shares DUMP_SAMPLES equally among the images, 2/3 luma
+    and 1/6 each chroma.  DIR/plane_sums.npy: float64 [images, 3], the sum
+    of every sample of each whole plane (0 for a plane the format lacks).
+    With more than one rank, rank r's files end in _rank<r>."""
+    import numpy as np
+
+    dst.mkdir(parents=True, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    share = DUMP_SAMPLES // len(outs) // 6
+    sums = np.zeros((len(outs), 3), np.float64)
+    samples = {}
+    for i, o in enumerate(outs):
+        for c, (name, t) in enumerate((("y", o.y), ("cb", o.cb), ("cr", o.cr))):
+            if t is None:
+                continue
+            pl = t.cpu().numpy().view(np.uint8 if t.element_size() == 1 else np.uint16).reshape(-1)
+            sums[i, c] = pl.sum(dtype=np.float64)
+            n = share * (1 if c else 4)
+            if pl.size > n:
+                pl = pl[np.random.default_rng((i, c)).integers(0, pl.size, n)]
+            samples.setdefault(name, []).append(pl.astype(np.float32))
+    for name, rows in samples.items():
+        np.save(dst / f"{name}{sfx}.npy", np.stack(rows))
+    np.save(dst / f"plane_sums{sfx}.npy", sums)
+
+
 def end_to_end(H, ctx, files, outs0, n_batches, threads, stream, info) -> dict:
     """Host parse + pinned upload + decode of n_batches batches of `files`
     (re-parsed every time), two device batches reloaded alternately so the
@@ -373,6 +416,12 @@ def main():
     ap.add_argument("--e2e-batches", type=int, default=6)
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: only the rank launch, rendezvous (gloo) and timing reduction")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks: oracle verification, one-decode latency, "
+                         "e2e, CPU baseline, single-thread host parse, tile-split gather and chain floor "
+                         "(--verify, --no-e2e, --no-cpu-baseline and --cpu-seconds apply only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the planes of the last timed step to DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
     tiles_split = args.split == "tiles"
 
@@ -392,7 +441,7 @@ def main():
 
     # the CPU baseline's -march=native oracle must be selected before anything imports the oracle
     # (the CPU baseline runs on rank 0 at N=1 only)
-    with_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    with_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     cpu_build = native_oracle() if with_cpu else None
     if world > 1:
         import torch.distributed as dist
@@ -427,9 +476,11 @@ def main():
         files = [permuted_heic(src, s) for s in seeds]
     # host demux + parameter sets + slice headers alone (heifgpu_image_parse_many)
     host_threads = effective_cpus()
-    t0 = time.perf_counter()
-    images = H.HeifImage.parse_many(files, threads=1)
-    host_parse_ms = (time.perf_counter() - t0) * 1e3 / len(files)
+    host_parse_ms = None
+    if args.full:
+        t0 = time.perf_counter()
+        images = H.HeifImage.parse_many(files, threads=1)
+        host_parse_ms = (time.perf_counter() - t0) * 1e3 / len(files)
     t0 = time.perf_counter()
     images = H.HeifImage.parse_many(files, threads=host_threads)
     host_parse_ms_mt = (time.perf_counter() - t0) * 1e3 / len(files)
@@ -438,6 +489,8 @@ def main():
     # a tile split's planes sit in one buffer: one IPC handle per rank for the gather to rank 0
     outs, outbuf = ctx.alloc_outputs_contiguous(images) if tiles_split else (ctx.alloc_outputs(images), None)
     stride, offset = (world, rank) if tiles_split else (1, 0)
+    if args.dump_outputs and outbuf is not None:
+        outbuf.zero_()  # a tile split leaves the other ranks' tiles unwritten: the same bytes in every run
     t0 = time.perf_counter()
     batch = ctx.prepare(images, tile_stride=stride, tile_offset=offset, parse=args.parse, pics_per_wave=args.ppw)
     upload_s = time.perf_counter() - t0
@@ -476,16 +529,20 @@ def main():
     st = batch.status(stream.cuda_stream)
     if any(st):
         raise SystemExit(f"rank {rank}: decode status {st}")
+    if args.dump_outputs:
+        dump_outputs(pathlib.Path(args.dump_outputs), outs, rank, world)
 
     # one more decode after the timed region, alone: the single-decode latency,
     # wall clock from the call to the planes being ready (streaming mode
     # overlaps the stages, so their sum is not the latency)
-    torch.cuda.synchronize()
-    t_lat = time.perf_counter()
-    step()
-    stream.synchronize()
-    latency_ms = (time.perf_counter() - t_lat) * 1e3
-    alone = ctx.stage_times()
+    latency_ms, alone = None, None
+    if args.full:
+        torch.cuda.synchronize()
+        t_lat = time.perf_counter()
+        step()
+        stream.synchronize()
+        latency_ms = (time.perf_counter() - t_lat) * 1e3
+        alone = ctx.stage_times()
     ctx.set_timing(False)
 
     # Row e2 across processes (outside the timed region): the tile split's
@@ -493,7 +550,7 @@ def main():
     # the image split (default), one image is decoded tile-split for this check.
     gather = None
     g_full, g_seeds = None, None
-    if world > 1 and not c4u:  # (the distinct-tile control is a one-GPU measurement)
+    if args.full and world > 1 and not c4u:  # (the distinct-tile control is a one-GPU measurement)
         from heif_amd.tile_split import DeviceBackend, gather_to_rank0
 
         if tiles_split:
@@ -529,7 +586,7 @@ def main():
     # independent pictures, /root/reference/src/heic/decoder.rs:114-119, so the
     # split removes tiles from a rank but never shortens that chain)
     split_parse = None
-    if tiles_split:
+    if args.full and tiles_split:
         mine = {"rank": rank, "tiles": len(range(offset, info.num_tiles, stride)), "parse_ms": round(per_step[0], 3),
                 "parse_ms_alone": round(alone[0], 3)}
         split_parse = [mine]
@@ -560,12 +617,12 @@ def main():
                         "below which no rank's parse can go however the tiles are split"}}
 
     e2e = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         e2e = end_to_end(H, ctx, files, outs, args.e2e_batches, host_threads, stream, info)
 
     if rank == 0:
         verified = 0
-        if args.verify:
+        if args.full and args.verify:
             n_check = len(files) if args.verify < 0 else min(args.verify, len(files))
             if c4u:  # every image has its own tiles: each decoded by the oracle
                 verified = verify_distinct(outs[:n_check], files[:n_check], info, stride, offset, host_threads)
@@ -682,20 +739,22 @@ def main():
             },
             "stage_ms_per_step": {k: round(v, 3) for k, v in zip(
                 ["parse", "transform", "intra", "deblock", "sao_out", "rbsp"], per_step)},
-            "stage_ms_alone": {k: round(v, 3) for k, v in zip(
-                ["parse", "transform", "intra", "deblock", "sao_out", "rbsp"], alone)},
             "pipeline": "three parse-output sets: decode n+2's k_rbsp+k_parse (parse stream), decode n+1's k_transform "
                         "(transform stream) and decode n's intra/deblock/SAO (recon stream) overlap; "
                         "the timed region includes the pipeline fill and drain; stage_ms_per_step are means over the "
                         "timed steps (overlap included), stage_ms_alone one decode with nothing beside it",
-            "latency_ms_one_step": round(latency_ms, 3),  # wall clock, one decode alone (host launch included)
-            "stage_ms_alone_sum": round(sum(alone), 3),
             "pipeline_hbm_gbs": round(launch_bytes / (elapsed / args.steps) / 1e9, 2),
-            "host_parse_ms_per_image": round(host_parse_ms, 3),
             "host_parse_ms_per_image_mt": {"threads": host_threads, "ms": round(host_parse_ms_mt, 4)},
             "upload_s": round(upload_s, 3),
-            "verified_images": verified,
+            "full": args.full,
         }
+        if args.full:
+            line["stage_ms_alone"] = {k: round(v, 3) for k, v in zip(
+                ["parse", "transform", "intra", "deblock", "sao_out", "rbsp"], alone)}
+            line["latency_ms_one_step"] = round(latency_ms, 3)  # wall clock, one decode alone (host launch included)
+            line["stage_ms_alone_sum"] = round(sum(alone), 3)
+            line["host_parse_ms_per_image"] = round(host_parse_ms, 3)
+            line["verified_images"] = verified
         if e2e:
             line["e2e"] = e2e
         if gather:

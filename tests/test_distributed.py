@@ -321,3 +321,40 @@ def test_bench_torchrun_environment_is_used_as_is():
                                 {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert rc == 0, err
     assert lines[0]["n_gpus"] == 1 and len(lines[0]["ranks"]) == 1
+
+
+def test_dump_outputs_samples_and_sums(tmp_path, monkeypatch):
+    """--dump-outputs on host tensors: float32 samples at default_rng((image,
+    plane)) positions (the whole plane where it is small enough), 16-bit
+    planes read unsigned, float64 whole-plane sums, a missing chroma plane
+    skipped, the same files from a second call, and the default budget within
+    64 MB."""
+    from types import SimpleNamespace as NS
+
+    assert bench.DUMP_SAMPLES * 4 + (1 << 20) <= 64 * 10**6
+    monkeypatch.setattr(bench, "DUMP_SAMPLES", 600)  # 2 images: 200 luma and 50 + 50 chroma samples each
+    g = np.random.default_rng(7)
+    planes = [[g.integers(0, 65536, s, dtype=np.uint16) for s in ((20, 30), (10, 15), (5, 10))] for _ in range(2)]
+    outs = [NS(y=torch.from_numpy(p[0].view(np.int16)), cb=torch.from_numpy(p[1].view(np.int16)),
+               cr=torch.from_numpy(p[2].view(np.int16))) for p in planes]
+    bench.dump_outputs(tmp_path / "a", outs, 0, 1)
+    bench.dump_outputs(tmp_path / "b", outs, 0, 1)
+    assert sorted(f.name for f in (tmp_path / "a").iterdir()) == ["cb.npy", "cr.npy", "plane_sums.npy", "y.npy"]
+    for f in (tmp_path / "a").iterdir():
+        assert f.read_bytes() == (tmp_path / "b" / f.name).read_bytes()
+    sums = np.load(tmp_path / "a" / "plane_sums.npy")
+    assert sums.dtype == np.float64
+    for c, (name, n) in enumerate((("y", 200), ("cb", 50), ("cr", 50))):
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == (2, n)
+        for i in range(2):
+            flat = planes[i][c].reshape(-1)
+            assert sums[i, c] == flat.sum(dtype=np.float64)
+            want = flat if flat.size <= n else flat[np.random.default_rng((i, c)).integers(0, flat.size, n)]
+            assert np.array_equal(got[i], want.astype(np.float32))
+    # 8-bit 4:0:0, two ranks: luma alone, whole, in rank-suffixed files
+    y8 = g.integers(0, 256, (4, 6), dtype=np.uint8)
+    bench.dump_outputs(tmp_path / "c", [NS(y=torch.from_numpy(y8), cb=None, cr=None)], 1, 2)
+    assert sorted(f.name for f in (tmp_path / "c").iterdir()) == ["plane_sums_rank1.npy", "y_rank1.npy"]
+    assert np.array_equal(np.load(tmp_path / "c" / "y_rank1.npy"), y8.reshape(1, -1).astype(np.float32))
+    assert np.load(tmp_path / "c" / "plane_sums_rank1.npy").tolist() == [[float(y8.sum()), 0.0, 0.0]]

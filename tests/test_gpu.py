@@ -190,6 +190,43 @@ def test_bench_shard_every_image(H, ctx, oracle_tiles, halfmoonbay, parse, geom)
         check_permuted(o, seeds, oracle_tiles)
 
 
+def test_bench_plain_run_dumps_last_step(H, oracle_tiles, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, prints
+    the headline keys without the side measurements, and --dump-outputs
+    writes the last timed step's planes: per image the whole-plane sums and
+    the samples at default_rng((image, plane)) positions, both equal to the
+    oracle's tiles placed by the image's permutation; at most 64 MB."""
+    import subprocess
+    import sys
+
+    import bench
+    from heif_amd.synthetic import permutation
+
+    p = subprocess.run([sys.executable, str(bench.ROOT / "bench.py"), "--gpus", "1", "--batch", "2", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "d")], capture_output=True, text=True,
+                       timeout=120)
+    assert p.returncode == 0, p.stderr
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    assert line["unit"] == "Mpixels/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert line["value"] == pytest.approx(2 * 4032 * 3024 / (line["ms_per_step"] * 1e3), rel=1e-3)
+    for k in ("cpu_baseline", "e2e", "verified_images", "latency_ms_one_step", "stage_ms_alone"):
+        assert k not in line
+    files = sorted(f.name for f in (tmp_path / "d").iterdir())
+    assert files == ["cb.npy", "cr.npy", "plane_sums.npy", "y.npy"]
+    assert sum(f.stat().st_size for f in (tmp_path / "d").iterdir()) <= 64 * 10**6
+    sums = np.load(tmp_path / "d" / "plane_sums.npy")
+    assert sums.dtype == np.float64 and sums.shape == (2, 3)
+    for c, name in enumerate(("y", "cb", "cr")):
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        assert got.dtype == np.float32 and got.shape == (2, bench.DUMP_SAMPLES // 2 // 6 * (1 if c else 4))
+        for i in range(2):
+            ref = assemble(oracle_tiles, permutation(48, i))[c].reshape(-1)
+            assert sums[i, c] == ref.sum(dtype=np.float64)
+            idx = np.random.default_rng((i, c)).integers(0, ref.size, got.shape[1])
+            assert np.array_equal(got[i], ref[idx].astype(np.float32)), (name, i)
+
+
 def _damaged_halfmoonbay(oracle_mod, data, tile=5):
     """halfmoonbay with the last eighth of one grid tile's slice data
     overwritten with 0xff: the host accepts it, the kernels flag it."""

@@ -10,7 +10,7 @@ for ((k = 0; k < ROUNDS; ++k)); do
     for spec in "$@"; do
         name=${spec%%:*}; envs=""; [ "$spec" != "$name" ] && envs=${spec#*:}
         log="$R/gpurun_out/ab_${name}_$k.log"
-        timeout -k 10 300 env ${envs//,/ } python3 "$R/bench.py" --steps ${AB_STEPS:-10} --warmup 2 \
+        timeout -k 10 300 env ${envs//,/ } python3 "$R/bench.py" --full --steps ${AB_STEPS:-10} --warmup 2 \
             --verify 0 --no-cpu-baseline --no-e2e ${AB_ARGS:-} > "$log" 2>&1 || { echo "$name FAILED"; tail -5 "$log"; exit 1; }
         python3 - "$log" "$name" <<'PY'
 import json, sys

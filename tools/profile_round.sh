@@ -11,7 +11,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o kt --output-format csv -- \
-    python3 "$R/bench.py" ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+    python3 "$R/bench.py" --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o fetch --output-format csv -- \
     python3 "$R/bench.py" ${BENCH_ARGS:-} --steps 1 --warmup 1 --no-cpu-baseline --no-e2e --verify 0 > "$OUT/fetch.log" 2>&1
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" -o write --output-format csv -- \
