@@ -342,6 +342,16 @@ class DeviceBatch:
         return {"mode": mode, "workgroups": v[1].value, "pics_per_wave": v[2].value,
                 "waves_per_workgroup": v[3].value}
 
+    def lanes_variant(self) -> str:
+        """The body this batch's lanes parse runs (heifgpu_batch_lanes_variant):
+        "lean" or "general" ("general" too in the other parse modes).
+        HEIFGPU_LANES_VARIANT=general at prepare keeps the general body."""
+        if not hasattr(lib, "heifgpu_batch_lanes_variant"):  # an earlier build of this ABI
+            return "general"
+        v = ctypes.c_uint32()
+        _lib.check(lib.heifgpu_batch_lanes_variant(self._h, ctypes.byref(v)))
+        return "lean" if v.value else "general"
+
     def free(self):
         if self._h is not None and self._h.value:
             lib.heifgpu_batch_free(self._h)

@@ -137,7 +137,7 @@ EXPORTS = (
     "heifgpu_bins_coeff_abs_level_remaining", "heifgpu_bins_exp_golomb", "heifgpu_image_tile_params", "heifgpu_debug_counters",
     "heifgpu_image_parse_item", "heifgpu_ycbcr_to_rgb", "heifgpu_batch_prepare_ex", "heifgpu_gather_tiles",
     "heifgpu_image_parse_many", "heifgpu_batch_parse_geometry", "heifgpu_ipc_export", "heifgpu_ipc_open",
-    "heifgpu_ipc_close", "heifgpu_batch_status_previous", "heifgpu_abi_version",
+    "heifgpu_ipc_close", "heifgpu_batch_status_previous", "heifgpu_abi_version", "heifgpu_batch_lanes_variant",
 )
 
 
@@ -208,8 +208,13 @@ def _load() -> ctypes.CDLL:
         "heifgpu_ipc_export": (I32, [VP, P(IpcHandle)]),
         "heifgpu_ipc_open": (I32, [I32, P(IpcHandle), P(VP)]),
         "heifgpu_ipc_close": (I32, [VP]),
+        "heifgpu_batch_lanes_variant": (I32, [VP, P(U32)]),
     }
+    # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
+    optional = {"heifgpu_batch_lanes_variant"}
     for name, (res, args) in sig.items():
+        if name in optional and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

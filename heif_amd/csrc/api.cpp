@@ -785,6 +785,9 @@ int heifgpu_batch_prepare_ex(heifgpu_ctx *ctx, const heifgpu_image *const *imgs,
     a.stream_patience_us = ctx->stream.patience_us;
     // rows wrap round the lanes (waves) of a picture: the WPP context staging
     a.wpp_ring = mode == PARSE_SOLO ? (hb.max_wpp_rows > solo_waves ? 1 : 0) : hb.wpp_ring;
+    a.lanes_lean = mode == PARSE_LANES
+                       ? lanes_variant_for(hb.seqs.data(), hb.pics.data(), int(hb.pics.size()), a.wpp_ring)
+                       : LANES_GENERAL;
     a.has_assembly = hb.has_assembly ? 1 : 0;
     a.total_rows = int(hb.rows);
     a.bytes_per_sample = hb.bps;
@@ -973,6 +976,12 @@ int heifgpu_batch_parse_geometry(const heifgpu_batch *b, uint32_t *mode, uint32_
     if (workgroups) *workgroups = (uint32_t(a.n_slots) + ppw - 1) / ppw;
     if (pics_per_wave) *pics_per_wave = ppw;
     if (waves_per_workgroup) *waves_per_workgroup = solo ? uint32_t(a.solo_waves) : 1u;
+    return HEIFGPU_OK;
+}
+
+int heifgpu_batch_lanes_variant(const heifgpu_batch *b, uint32_t *variant) {
+    if (!b || !b->loaded || !variant) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    *variant = b->args.parse_mode == PARSE_LANES ? uint32_t(b->args.lanes_lean) : uint32_t(LANES_GENERAL);
     return HEIFGPU_OK;
 }
 

@@ -6,6 +6,8 @@
 //   the grid tiles k % stride == offset are decoded (the tile split across GPUs):
 //   their windows must match the oracle and every other sample must keep the
 //   sentinel the planes start with
+//   emu_check file.heic 0 [more.heic ...]: host only; the files as one batch
+//   (its picture count, parse mode and lanes variant: prepare's choices)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -25,20 +27,38 @@ int main(int argc, char **argv) {
     if (argc < 2) return 2;
     setvbuf(stdout, nullptr, _IONBF, 0);  // every line out before a sanitizer abort
     int stages = argc > 2 ? atoi(argv[2]) : 5;
-    const uint32_t tstride = argc > 4 ? uint32_t(atoi(argv[3])) : 1u, toff = argc > 4 ? uint32_t(atoi(argv[4])) : 0u;
-    FILE *f = fopen(argv[1], "rb");
-    fseek(f, 0, SEEK_END);
-    long n = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    std::vector<uint8_t> data(static_cast<size_t>(n), 0);
-    if (fread(data.data(), 1, size_t(n), f) != size_t(n)) return 2;
-    fclose(f);
+    const bool host_only = stages <= 0;
+    const uint32_t tstride = !host_only && argc > 4 ? uint32_t(atoi(argv[3])) : 1u,
+                   toff = !host_only && argc > 4 ? uint32_t(atoi(argv[4])) : 0u;
+    auto read_file = [](const char *path, std::vector<uint8_t> &out) {
+        FILE *f = fopen(path, "rb");
+        if (!f) return false;
+        fseek(f, 0, SEEK_END);
+        long n = ftell(f);
+        fseek(f, 0, SEEK_SET);
+        out.assign(static_cast<size_t>(n), 0);
+        const bool ok = fread(out.data(), 1, size_t(n), f) == size_t(n);
+        fclose(f);
+        return ok;
+    };
+    std::vector<uint8_t> data;
+    if (!read_file(argv[1], data)) return 2;
+    std::vector<std::vector<uint8_t>> more_data;  // host only: the rest of the batch
+    for (int k = 3; host_only && k < argc; ++k) {
+        more_data.emplace_back();
+        if (!read_file(argv[k], more_data.back())) return 2;
+    }
     ParsedImage im;
+    std::vector<ParsedImage> more(more_data.size());
     HostBatch hb;
     try {  // the host's checks reject what the kernels never see (the API returns the error)
         im = parse_heic(data.data(), data.size());
-        const ParsedImage *ims[1] = {&im};
-        hb = build_batch(ims, 1, tstride, toff);
+        std::vector<const ParsedImage *> ims{&im};
+        for (size_t k = 0; k < more.size(); ++k) {
+            more[k] = parse_heic(more_data[k].data(), more_data[k].size());
+            ims.push_back(&more[k]);
+        }
+        hb = build_batch(ims.data(), ims.size(), tstride, toff);
     } catch (const std::exception &e) {
         printf("host rejected: %s\n", e.what());
         return 3;
@@ -111,12 +131,18 @@ int main(int argc, char **argv) {
     a.xntu = a.intra_stream ? xntu.data() : nullptr;
     a.stream_patience_us = knobs.patience_us;
     a.wpp_ring = mode == PARSE_SOLO ? (hb.max_wpp_rows > solo_waves ? 1 : 0) : hb.wpp_ring;
+    // the body the GPU would run (prepare's predicate and knob)
+    a.lanes_lean = mode == PARSE_LANES
+                       ? lanes_variant_for(hb.seqs.data(), hb.pics.data(), int(hb.pics.size()), a.wpp_ring)
+                       : LANES_GENERAL;
     a.has_assembly = hb.has_assembly ? 1 : 0;
     a.total_rows = int(hb.rows);
     a.bytes_per_sample = bps;
     a.chroma_format = hb.chroma;
     if (stages <= 0) {  // host only: container, parameter sets, slice headers, batch layout
         printf("host ok: %zu pictures\n", hb.pics.size());
+        printf("parse mode: %s\n", mode == PARSE_SOLO ? "solo" : mode == PARSE_SPREAD ? "spread" : "lanes");
+        if (mode == PARSE_LANES) printf("lanes variant: %s\n", a.lanes_lean ? "lean" : "general");
         return 0;
     }
     // k_rbsp zeroes the decode's status words, row counts, progress words and TU
@@ -151,6 +177,7 @@ int main(int argc, char **argv) {
     printf("parse mode: %s\n", mode == PARSE_SOLO     ? "solo"
                                : mode == PARSE_SPREAD ? "spread"
                                                       : "lanes");
+    if (mode == PARSE_LANES) printf("lanes variant: %s\n", a.lanes_lean ? "lean" : "general");
     printf("parse: status 0x%x, %llu TBs, %llu coefficients\n", st, (unsigned long long)ntu, (unsigned long long)ncoef);
     if (stages >= 2 && !a.intra_stream) emu_transform(a);  // (streaming: k_intra_stream transforms each TB)
     if (stages >= 3) {

@@ -65,6 +65,8 @@ struct BatchArgs {
     uint32_t stream_patience_us;  // first launch: give a picture up after this long without parse progress (0: at once)
     int has_assembly;          // some picture is PD_ASSEMBLY (launch_deblock runs k_assemble first)
     int intra_split;           // k_intra: luma and chroma on separate waves (set by launch_intra)
+    // (added last: every other kernel's argument offsets, and so its code, stay as they were)
+    int lanes_lean;            // lanes parse: the lean tool set's body (lanes_variant_for; LANES_*)
 };
 
 // k_ycbcr_rgb (color.hip): one decoded image → interleaved RGB8, rotated
@@ -129,6 +131,12 @@ bool intra_stream_for(int parse_mode, int n_pics, bool has_assembly, const Strea
 // (pics: the batch's pictures; one with dependent slice segments starting inside a
 // CTB row (PicDesc.flags, PD_NMID_SHIFT) makes it a lanes parse: only that engine takes them)
 int parse_mode_for(int requested, int n_pics, const PicDesc *pics = nullptr);
+// the lanes parse's body for a batch (parse_lanes.hip, EngT): lean when every
+// picture is 4:2:0 without PCM, transform_skip, cu_transquant_bypass, slice
+// segments inside it or wrapping rows; HEIFGPU_LANES_VARIANT=general|auto
+enum : int { LANES_GENERAL = 0, LANES_LEAN = 1 };
+bool lanes_lean_eligible(const SeqParams *seqs, const PicDesc *pics, int n_pics, int wpp_ring);
+int lanes_variant_for(const SeqParams *seqs, const PicDesc *pics, int n_pics, int wpp_ring);
 // spread mode's wave slots (row << 20 | picture); -1 if the batch exceeds the encoding
 int spread_parse_order(const PicDesc *pics, int n, std::vector<uint32_t> &order);
 int solo_waves_for(int lane_rows);

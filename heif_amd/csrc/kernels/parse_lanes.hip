@@ -52,12 +52,12 @@
 extern "C" __device__ int hg_writelane(int src, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
 #endif
 
-// HG_PARSE_TU (library build, Makefile): 1 compiles the lanes / rows kernels and
-// launch_parse, 2 (kernels/parse_solo.hip) the solo / spread kernels, so each
-// translation unit gets its own code-generation flags; unset, everything (the
-// host emulation and the counter builds)
-#if defined(HG_PARSE_TU) && HG_PARSE_TU != 1 && HG_PARSE_TU != 2
-#error "HG_PARSE_TU is 1 or 2"
+// HG_PARSE_TU (library build, Makefile): 1 compiles the general lanes kernel and
+// launch_parse, 2 (kernels/parse_solo.hip) the solo / spread kernels, 3
+// (kernels/parse_lean.hip) the lean lanes kernel, so each translation unit
+// gets its own code-generation flags; unset, everything (the host emulation)
+#if defined(HG_PARSE_TU) && HG_PARSE_TU != 1 && HG_PARSE_TU != 2 && HG_PARSE_TU != 3
+#error "HG_PARSE_TU is 1, 2 or 3"
 #endif
 #if !defined(HG_PARSE_TU) || HG_PARSE_TU == 1
 #define HG_PARSE_WANT_LANES 1
@@ -68,6 +68,23 @@ extern "C" __device__ int hg_writelane(int src, int lane, int old) __asm("llvm.a
 #define HG_PARSE_WANT_SOLO 1
 #else
 #define HG_PARSE_WANT_SOLO 0
+#endif
+#if !defined(HG_PARSE_TU) || HG_PARSE_TU == 3
+#define HG_PARSE_WANT_LEAN 1
+#else
+#define HG_PARSE_WANT_LEAN 0
+#endif
+
+// branches a conforming stream of ordinary content almost never takes (substream
+// starts, the escape form of coeff_abs_level_remaining, capacity and syntax
+// errors): laid out after the units' hot blocks (HG_NO_COLD_HINTS turns the
+// hints off; A/B in DESIGN 5.15)
+#if !defined(HG_NO_COLD_HINTS)
+#define HG_UNLIKELY(x) __builtin_expect(!!(x), 0)
+#define HG_LIKELY(x) __builtin_expect(!!(x), 1)
+#else
+#define HG_UNLIKELY(x) (x)
+#define HG_LIKELY(x) (x)
 #endif
 
 namespace hg {
@@ -265,9 +282,19 @@ HG_HD inline size_t lane_blocks_bytes(int n) { return (sizeof(LaneLds) * (size_t
 // picture's WPP rows are lanes of one wave, so no hand-off leaves the wave).
 // (r05's row waves, k_parse_rows, were this engine with spread mode's
 // hand-offs; removed in r06, their A/B record is DESIGN 5.4)
-struct Eng {
+//
+// Tool set (Lean): the general body keeps every coding tool of every chroma
+// format at run time; the lean body is compiled for the set nearly every HEIC
+// still uses (lanes_lean_eligible: 4:2:0, no PCM, transform_skip or
+// cu_transquant_bypass, no slice segments inside a picture's rows or between
+// them, no wrapping rows), with those picture constants and per-CU / per-TB
+// flags folded (HG_PIC_CHROMA .. lane_fl below).  Sign hiding, cu_qp_delta, WPP,
+// SAO and the bit depth stay run-time values in both.
+template <bool Lean>
+struct EngT {
     static constexpr bool kSolo = false;
     static constexpr bool kSpread = false;
+    static constexpr bool kLean = Lean;
     static constexpr bool kCtxReg = false;  // contexts in LDS (ctx)
     static constexpr bool kRowCtx = true;
     uint8_t *ctx;
@@ -284,6 +311,8 @@ struct Eng {
     HG_HD int scan8(int scan, int i) const { return sp8 && scan == 0 ? sp8[i] : kScanPos[3][scan][i]; }
     HG_HD int scan8_inv(int scan, int r) const { return inv8 && scan == 0 ? inv8[r] : kScanInv[3][scan][r]; }
 };
+using Eng = EngT<false>;
+using EngLean = EngT<true>;
 
 // Solo mode (k_parse_solo): one substream per WAVE, run by its lane 0 alone,
 // so the engine state is wave-uniform.  The state rows live in two VGPRs
@@ -316,6 +345,7 @@ struct Win {
 template <bool Spread>
 struct EngSoloT {
     static constexpr bool kSolo = true;
+    static constexpr bool kLean = false;    // every tool at run time
     static constexpr bool kRowCtx = false;  // rows per pStateIdx (tlo / thi)
     // one wave per workgroup: the rows of a picture on different CUs, their
     // WPP progress, context hand-off, SAO and depth lines in coherent global
@@ -490,6 +520,41 @@ struct SoloWin {
         ++ck;
     }
 };
+
+// ------------------------------------------------------------------ tool set
+// The picture constants and flags the units test, through the engine's tool
+// set: run-time values of the picture (LDS reads, divergent branches) in the
+// general bodies, constants in the lean one.  PF_COHERENT is the streaming
+// spread parse's alone (BatchArgs::xntu): neither lanes body tests it.
+constexpr uint32_t kLeanOffFlags = SP_TRANSFORM_SKIP | SP_TQ_BYPASS | SP_PCM | SP_PCM_LOOP_FILTER_DISABLED |
+                                   SP_ROW_SEGMENTS | ((uint32_t)PD_NMID_MAX << PD_NMID_SHIFT);
+// (the chroma format's three as in-place constant selections, not functions:
+// written as accessor functions, or read once into a local, they moved the
+// code generation of the solo / spread kernels, which this tool set leaves
+// alone: the spread kernel 52,940 -> 48,952 B and one image 24.8 -> 25.8 ms,
+// DESIGN 5.15; so every read stands where the general body had it)
+#define HG_PIC_CHROMA(P) (EG::kLean ? 1 : (P).chroma)
+#define HG_PIC_SUBX(P) (EG::kLean ? 1 : (P).subx)
+#define HG_PIC_SUBY(P) (EG::kLean ? 1 : (P).suby)
+template <class EG>
+HG_HD inline uint32_t pic_flags(const LanePic &P) {
+    uint32_t f = P.flags;
+    if constexpr (!EG::kSolo) f &= ~PF_COHERENT;
+    if constexpr (EG::kLean) f &= ~kLeanOffFlags;
+    return f;
+}
+// rows wrap round the picture's lanes (WPP context staging)
+template <class EG>
+HG_HD inline bool pic_ring(const LanePic &P) {
+    if constexpr (EG::kLean) return false;
+    else return P.ring != 0;
+}
+// Lane.fl as the units test it: cu_transquant_bypass, transform_skip and PCM never set in the lean body
+template <class EG>
+HG_HD inline uint32_t lane_fl(const Lane &L) {
+    if constexpr (EG::kLean) return L.fl & ~(uint32_t)(F_BYPASS | F_TS | F_PCM);
+    else return L.fl;
+}
 
 // ------------------------------------------------------------------ memory helpers
 #if defined(HG_HOST_EMU)
@@ -1177,28 +1242,29 @@ HG_HD inline bool wpp_ready(const Lane &L, const LanePic &P, const Env &E) {
 // RBSP offset (absolute) at which a lane about to run U_CTU starts its
 // substream (engine and context initialisation, unit_ctu), or ~0u
 // dependent slice segments starting inside a CTB row of picture P (PicDesc.flags)
-HG_HD inline uint32_t lanes_nmid(const LanePic &P) { return (P.flags >> PD_NMID_SHIFT) & PD_NMID_MAX; }
+template <class EG>
+HG_HD inline uint32_t lanes_nmid(const LanePic &P) { return (pic_flags<EG>(P) >> PD_NMID_SHIFT) & PD_NMID_MAX; }
 
 // (Mid: the lanes engine, which takes dependent segments starting inside a
 // row; the scalar engines do not, parse_mode_for gives such batches the lanes parse)
-template <bool Mid>
+template <class EG>
 HG_HD inline uint32_t substream_start(const Lane &L, const LanePic &P, const BatchArgs &a) {
     if (L.c != 0) {
-        if constexpr (Mid) {
+        if constexpr (!EG::kSolo && !EG::kLean) {
             if (L.status & ST_SEGSW) {
                 // a dependent segment starting inside the row (the picture's row
                 // entries, the end entry, then these); past the picture's
                 // list (a corrupt stream, flagged by unit_ctu): the RBSP end
                 const uint32_t m = L.fl >> kMsegShift;
                 return P.bits_off +
-                       (a.rsubs[P.sub_first + (uint32_t)P.hctb + (m < lanes_nmid(P) ? 1u + m : 0u)] & SUB_OFFSET);
+                       (a.rsubs[P.sub_first + (uint32_t)P.hctb + (m < lanes_nmid<EG>(P) ? 1u + m : 0u)] & SUB_OFFSET);
             }
         }
         return ~0u;
     }
     if ((L.fl & F_WPP) || L.row == 0)
         return P.bits_off + (a.rsubs[P.sub_first + ((L.fl & F_WPP) ? L.row : 0)] & SUB_OFFSET);
-    if (P.flags & SP_ROW_SEGMENTS) {  // no WPP: a dependent slice segment may start at this row
+    if (pic_flags<EG>(P) & SP_ROW_SEGMENTS) {  // no WPP: a dependent slice segment may start at this row
         const uint32_t e = a.rsubs[P.sub_first + L.row];
         if (!(e & SUB_CONTINUE)) return P.bits_off + (e & SUB_OFFSET);
     }
@@ -1214,8 +1280,9 @@ HG_HD inline void row_outputs(Lane &L, const LanePic &P) {
 // one coefficient, one 4-byte store.  (Grouping four into a 16-byte store
 // through registers measured 5 % slower: the selects run on every lane of
 // every coefficient step, the saved stores were cheap.)
+template <class EG>
 HG_HD inline void coef_push(Lane &L, const LanePic &P, uint32_t w) {
-    if (P.flags & PF_COHERENT) store_word_agent((uint32_t *)(P.coef_base + L.coef_row + L.ncoef++), w);
+    if (pic_flags<EG>(P) & PF_COHERENT) store_word_agent((uint32_t *)(P.coef_base + L.coef_row + L.ncoef++), w);
     else P.coef_base[L.coef_row + L.ncoef++] = w;
 }
 
@@ -1227,13 +1294,13 @@ HG_HD inline void unit_ctu(Lane &L, LaneLds &ld, LanePic &P, const Env &E, const
     if (!wpp_ready<EG>(L, P, E)) return;
     L.ctbx = L.c << P.log2ctb;
     L.ctby = L.row << P.log2ctb;
-    const uint32_t start = substream_start<!EG::kSolo>(L, P, *E.a);
-    if (start != ~0u) {
+    const uint32_t start = substream_start<EG>(L, P, *E.a);
+    if (HG_UNLIKELY(start != ~0u)) {
         // substream start: contexts (init; the WPP copy already in ld.ctx; or, a
         // dependent slice segment without WPP, the previous segment's final
         // state, which the lane still holds: 9.3.2.4) + engine.  A dependent
         // segment starting inside a row (ST_SEGSW) keeps the contexts and qPY_PREV
-        const bool segsw = !EG::kSolo && (L.status & ST_SEGSW) != 0;
+        const bool segsw = !EG::kSolo && !EG::kLean && (L.status & ST_SEGSW) != 0;
         const bool init = !segsw && (L.row == 0 || ((L.fl & F_WPP) && P.wctb < 2));
         const bool wpp_copy = !init && (L.fl & F_WPP);
         if constexpr (EG::kCtxReg) {
@@ -1250,7 +1317,7 @@ HG_HD inline void unit_ctu(Lane &L, LaneLds &ld, LanePic &P, const Env &E, const
             } else if (wpp_copy) {
                 w = 0;
                 if (ln < CTX_PAD / 4) {
-                    const uint8_t *src = (EG::kSpread || P.ring) ? wpp_stage(E, P, L.row) : ld.ctx;
+                    const uint8_t *src = (EG::kSpread || pic_ring<EG>(P)) ? wpp_stage(E, P, L.row) : ld.ctx;
                     const uint32_t *sw = reinterpret_cast<const uint32_t *>(src) + ln;
                     w = EG::kSpread ? load_agent(sw) : *sw;
                 }
@@ -1260,7 +1327,7 @@ HG_HD inline void unit_ctu(Lane &L, LaneLds &ld, LanePic &P, const Env &E, const
         } else if (init) {
 #pragma nounroll
             for (int i = 0; i < CTX_NUM; ++i) ld.ctx[i] = ctx_init_state(c_ctx_init_l[i], P.sliceQp);
-        } else if (wpp_copy && (EG::kSpread || P.ring)) {
+        } else if (wpp_copy && (EG::kSpread || pic_ring<EG>(P))) {
             const uint32_t *src = reinterpret_cast<const uint32_t *>(wpp_stage(E, P, L.row));
             uint32_t *dst = reinterpret_cast<uint32_t *>(ld.ctx);
 #pragma nounroll
@@ -1269,14 +1336,14 @@ HG_HD inline void unit_ctu(Lane &L, LaneLds &ld, LanePic &P, const Env &E, const
         engine_init(L, G, start, P.bits_end);
         if (segsw) {
             L.status &= ~ST_SEGSW;
-            if ((L.fl >> kMsegShift) >= lanes_nmid(P)) L.status |= ST_SUBSTREAM_END;  // no such segment
+            if ((L.fl >> kMsegShift) >= lanes_nmid<EG>(P)) L.status |= ST_SUBSTREAM_END;  // no such segment
             L.fl += kMsegOne;
         } else {
             if (L.row == 0) L.fl |= F_FIRST_QG;
             if constexpr (!EG::kSolo) {
                 // WPP: this row's lane counts the segments started inside rows from
                 // those of earlier rows (batch.cpp: after the picture's mid list)
-                const uint32_t nm = lanes_nmid(P);
+                const uint32_t nm = lanes_nmid<EG>(P);
                 if ((L.fl & F_WPP) && nm)
                     L.fl = (L.fl & (kMsegOne - 1)) |
                            (E.a->subs[P.sub_first + (uint32_t)P.hctb + 1u + nm + L.row] << kMsegShift);
@@ -1321,7 +1388,7 @@ HG_HD inline void unit_ctu(Lane &L, LaneLds &ld, LanePic &P, const Env &E, const
                 put8(b, (uint32_t)v);
                 put8(b + 1, (uint32_t)v >> 8);
             };
-            const int ncomp = P.chroma ? 3 : 1;
+            const int ncomp = HG_PIC_CHROMA(P) ? 3 : 1;
             int type1 = 0, eo1 = 0;
 #pragma unroll
             for (int cc = 0; cc < 3; ++cc) {
@@ -1401,6 +1468,7 @@ HG_HD inline void unit_cqt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
 }
 
 HG_HD inline void cu_done(Lane &L, LaneLds &ld, LanePic &P);
+template <class EG>
 HG_HD inline void tu_emit(Lane &L, const LanePic &P);
 
 // pcm_flag = 1 (7.3.8.7 pcm_sample(); the reference parses the SPS PCM fields,
@@ -1427,14 +1495,14 @@ HG_HD inline void pcm_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     L.fl = (L.fl | F_PCM | F_TB_CBF) & ~F_TS;
     // luma, then Cb and Cr; a 4:2:2 chroma block (raster, m wide, 2m tall) is
     // two stacked square TBs
-    const int ntb = P.chroma == 0 ? 1 : (P.chroma == 2 ? 5 : 3), nh = P.chroma == 2 ? 2 : 1;
+    const int ntb = HG_PIC_CHROMA(P) == 0 ? 1 : (HG_PIC_CHROMA(P) == 2 ? 5 : 3), nh = HG_PIC_CHROMA(P) == 2 ? 2 : 1;
     for (int t = 0; t < ntb; ++t) {
         const int c = t == 0 ? 0 : 1 + (t - 1) / nh, h = t == 0 ? 0 : (t - 1) % nh;
-        const int l2 = (c && P.chroma != 3) ? L.ql - 1 : L.ql, m = 1 << l2;
+        const int l2 = (c && HG_PIC_CHROMA(P) != 3) ? L.ql - 1 : L.ql, m = 1 << l2;
         const int pbd = c ? P.pcmBdC : P.pcmBdY, sh = (c ? P.bdC : P.bdY) - pbd;
         L.tb_cidx = c;
-        L.tb_x = c ? L.qx >> P.subx : L.qx;
-        L.tb_y = c ? (L.qy >> P.suby) + (h << l2) : L.qy;
+        L.tb_x = c ? L.qx >> HG_PIC_SUBX(P) : L.qx;
+        L.tb_y = c ? (L.qy >> HG_PIC_SUBY(P)) + (h << l2) : L.qy;
         L.tb_log2 = l2;
         L.tb_mode = 1;
         L.tb_coef0 = L.ncoef;
@@ -1446,16 +1514,16 @@ HG_HD inline void pcm_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
             const uint32_t w = ((uint32_t)G.rbsp[b] << 16) | ((uint32_t)G.rbsp[b + 1] << 8) | (uint32_t)G.rbsp[b + 2];
             const uint32_t v = (w >> (24u - (bit & 7u) - (uint32_t)pbd)) & ((1u << pbd) - 1u);
             bit += (uint32_t)pbd;
-            if (L.ncoef + L.nesc < P.coef_cap) coef_push(L, P, ((v << sh) << 16) | (uint32_t)i);
+            if (L.ncoef + L.nesc < P.coef_cap) coef_push<EG>(L, P, ((v << sh) << 16) | (uint32_t)i);
             else L.status |= ST_CAPACITY;
         }
-        tu_emit(L, P);
+        tu_emit<EG>(L, P);
     }
     L.fl &= ~(F_PCM | F_TB_CBF);
     {  // the CU's 4x4 blocks: one block for the deblocking edges
         const int nb = n >> 2, gx0 = L.qx >> 2, gy0 = L.qy >> 2;
         const int wx = gx0 + nb <= P.w4 ? nb : P.w4 - gx0, hy = gy0 + nb <= P.h4 ? nb : P.h4 - gy0;
-        const uint64_t nf = ((L.fl & F_BYPASS) || (P.flags & SP_PCM_LOOP_FILTER_DISABLED)) ? MF_NOFILT : 0;
+        const uint64_t nf = ((L.fl & F_BYPASS) || (pic_flags<EG>(P) & SP_PCM_LOOP_FILTER_DISABLED)) ? MF_NOFILT : 0;
         const uint64_t rep = 0x0101010101010101ull;
         for (int y = 0; y < hy; ++y) {
             uint8_t *row = P.gflags + (size_t)(gy0 + y) * P.w4 + gx0;
@@ -1484,10 +1552,10 @@ HG_HD inline void unit_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     }
     update_qpy(L, P);
     L.fl &= ~(F_BYPASS | F_NXN);
-    if ((P.flags & SP_TQ_BYPASS) && dec(L, G, CTX_TQ_BYPASS)) L.fl |= F_BYPASS;
+    if ((pic_flags<EG>(P) & SP_TQ_BYPASS) && dec(L, G, CTX_TQ_BYPASS)) L.fl |= F_BYPASS;
     if (L.ql == P.minCb && !dec(L, G, CTX_PART_MODE)) L.fl |= F_NXN;
     const bool nxn = (L.fl & F_NXN) != 0;
-    const bool pcm = !nxn && (P.flags & SP_PCM) && L.ql >= P.pcmMin && L.ql <= P.pcmMax && term(L, G);
+    const bool pcm = !nxn && (pic_flags<EG>(P) & SP_PCM) && L.ql >= P.pcmMin && L.ql <= P.pcmMax && term(L, G);
     {  // CtDepth of the CU
         const int nd = 1 << (L.ql - 3);
         const int dy = (L.qy - L.ctby) >> 3, dx = (L.qx - L.ctbx) >> 3;
@@ -1496,9 +1564,11 @@ HG_HD inline void unit_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
             ld.dA[dx + k] = (uint8_t)L.qd;
         }
     }
-    if (pcm) {
-        pcm_cu(L, ld, P, G);
-        return;
+    if constexpr (!EG::kLean) {
+        if (pcm) {
+            pcm_cu(L, ld, P, G);
+            return;
+        }
     }
     const int np = nxn ? 4 : 1;
     const int pb = nxn ? 1 << (L.ql - 1) : 1 << L.ql;
@@ -1520,8 +1590,8 @@ HG_HD inline void unit_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         }
     }
     L.cu_modes = modes;
-    if (P.chroma) {  // intra_chroma_pred_mode: per PB with 4:4:4, else per CU; 8.4.3
-        const int nc = P.chroma == 3 ? np : 1;
+    if (HG_PIC_CHROMA(P)) {  // intra_chroma_pred_mode: per PB with 4:4:4, else per CU; 8.4.3
+        const int nc = HG_PIC_CHROMA(P) == 3 ? np : 1;
         int cms = 0;
         for (int i = 0; i < nc; ++i) {
             const int icpm = dec(L, G, CTX_CHROMA_MODE) ? (int)byp_bits(L, G, 2) : 4;
@@ -1533,7 +1603,7 @@ HG_HD inline void unit_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
                 cm = icpm == 0 ? 0 : (icpm == 1 ? 26 : (icpm == 2 ? 10 : 1));
                 if (cm == lm) cm = 34;
             }
-            if (P.chroma == 2) cm = mode422(cm);
+            if (HG_PIC_CHROMA(P) == 2) cm = mode422(cm);
             cms |= cm << (8 * i);
         }
         L.cu_chroma = nc == 1 ? (int)((uint32_t)cms * 0x01010101u) : cms;  // byte k: PB k
@@ -1555,9 +1625,9 @@ HG_HD inline void unit_tt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         else
             split = L.tl > P.maxTb || (nxn && L.td == 0);
         uint32_t cbf = 0;  // cbf_cb | cbf_cr << 1, 4:2:2 lower TBs << 2 / << 3 (7.3.8.8)
-        if ((L.tl > 2 && P.chroma) || P.chroma == 3) {
+        if ((L.tl > 2 && HG_PIC_CHROMA(P)) || HG_PIC_CHROMA(P) == 3) {
             const uint32_t pc = L.td == 0 ? 3u : (L.tcbf >> (4 * (L.td - 1))) & 3u;
-            const bool two = P.chroma == 2 && (!split || L.tl == 3);
+            const bool two = HG_PIC_CHROMA(P) == 2 && (!split || L.tl == 3);
             if (pc & 1) {
                 cbf |= (uint32_t)dec(L, G, CTX_CBF_CHROMA + L.td);
                 if (two) cbf |= (uint32_t)dec(L, G, CTX_CBF_CHROMA + L.td) << 2;
@@ -1576,10 +1646,10 @@ HG_HD inline void unit_tt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     L.fl &= ~F_CBF_L;
     if (dec(L, G, CTX_CBF_LUMA + (L.td == 0 ? 1 : 0))) L.fl |= F_CBF_L;
     // transform_unit
-    const bool chroma4 = (P.chroma == 1 || P.chroma == 2) && L.tl == 2;
+    const bool chroma4 = (HG_PIC_CHROMA(P) == 1 || HG_PIC_CHROMA(P) == 2) && L.tl == 2;
     const uint32_t pc = L.td > 0 ? (L.tcbf >> (4 * (L.td - 1))) & 15u : 0u;  // the parent's chroma cbfs
-    const bool cbf_c = P.chroma == 0 ? false : (chroma4 ? pc != 0 : cbf != 0);
-    if (((L.fl & F_CBF_L) || cbf_c) && (P.flags & SP_CU_QP_DELTA) && !(L.fl & F_DQP_CODED)) {
+    const bool cbf_c = HG_PIC_CHROMA(P) == 0 ? false : (chroma4 ? pc != 0 : cbf != 0);
+    if (((L.fl & F_CBF_L) || cbf_c) && (pic_flags<EG>(P) & SP_CU_QP_DELTA) && !(L.fl & F_DQP_CODED)) {
         int v = 0;  // cu_qp_delta_abs: TR prefix (cMax 5), EG0 suffix
         while (v < 5 && dec(L, G, CTX_CU_QP_DELTA + (v == 0 ? 0 : 1))) ++v;
         if (v == 5) {
@@ -1598,7 +1668,7 @@ HG_HD inline void unit_tt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         // 7.4.9.14: CuQpDeltaVal in [-(26 + QpBdOffsetY / 2), 25 + QpBdOffsetY / 2]
         // (outside it, QpY and the scaling shift would leave their ranges)
         const int vlo = -(26 + P.qpbdY / 2), vhi = 25 + P.qpbdY / 2;
-        if (v < vlo || v > vhi) {
+        if (HG_UNLIKELY(v < vlo || v > vhi)) {
             L.status |= ST_SYNTAX;
             v = v < vlo ? vlo : vhi;
         }
@@ -1609,7 +1679,7 @@ HG_HD inline void unit_tt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     {  // edge / no-filter flags of every 4x4 luma block of the TB (MF_*)
         const int nb = 1 << (L.tl - 2), gx0 = L.tx >> 2, gy0 = L.ty >> 2;
         const int wx = gx0 + nb <= P.w4 ? nb : P.w4 - gx0, hy = gy0 + nb <= P.h4 ? nb : P.h4 - gy0;
-        const uint64_t nf = (L.fl & F_BYPASS) ? MF_NOFILT : 0;
+        const uint64_t nf = (lane_fl<EG>(L) & F_BYPASS) ? MF_NOFILT : 0;
         const uint64_t rep = 0x0101010101010101ull;
         for (int y = 0; y < hy; ++y) {
             uint8_t *row = P.gflags + (size_t)(gy0 + y) * P.w4 + gx0;
@@ -1619,13 +1689,15 @@ HG_HD inline void unit_tt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     }
     const int blk = L.td == 0 ? 0 : (((L.tx >> L.tl) & 1) | (((L.ty >> L.tl) & 1) << 1));
     // luma, then Cb and Cr (two each with 4:2:2: upper, lower)
-    L.tb_n = (P.chroma != 0 && (!chroma4 || blk == 3)) ? (P.chroma == 2 ? 5 : 3) : 1;
+    L.tb_n = (HG_PIC_CHROMA(P) != 0 && (!chroma4 || blk == 3)) ? (HG_PIC_CHROMA(P) == 2 ? 5 : 3) : 1;
     L.tb_t = 0;
     L.st = U_TB;
 }
 
 // record of the current TB (TuRec, desc.hpp)
+template <class EG>
 HG_HD inline void tu_emit(Lane &L, const LanePic &P) {
+    const uint32_t fl = lane_fl<EG>(L);
     int qp;
     if (L.tb_cidx == 0) {
         qp = L.qpy_cur + P.qpbdY;
@@ -1633,19 +1705,19 @@ HG_HD inline void tu_emit(Lane &L, const LanePic &P) {
         const int off = L.tb_cidx == 1 ? P.cbOff : P.crOff;
         int qpi = L.qpy_cur + off;
         qpi = qpi < -P.qpbdC ? -P.qpbdC : (qpi > 57 ? 57 : qpi);
-        qp = chroma_qp_map(qpi, P.chroma) + P.qpbdC;
+        qp = chroma_qp_map(qpi, HG_PIC_CHROMA(P)) + P.qpbdC;
     }
     uint32_t f = (uint32_t)L.tb_cidx;
-    if (L.fl & F_TB_CBF) f |= TU_CBF;
-    if (L.fl & F_TS) f |= TU_TSKIP;
-    if (L.fl & F_BYPASS) f |= TU_BYPASS;
-    if (L.fl & F_PCM) f |= TU_PCM | TU_BYPASS;
+    if (fl & F_TB_CBF) f |= TU_CBF;
+    if (fl & F_TS) f |= TU_TSKIP;
+    if (fl & F_BYPASS) f |= TU_BYPASS;
+    if (fl & F_PCM) f |= TU_PCM | TU_BYPASS;
     if (L.tb_cidx == 0 && L.tb_log2 == 2) f |= TU_DST;
-    if (L.ntu < P.tu_cap) {
+    if (HG_LIKELY(L.ntu < P.tu_cap)) {
         const uint32_t w0 = (uint32_t)L.tb_x | ((uint32_t)L.tb_y << 16);
         const uint32_t w1 = (uint32_t)L.tb_log2 | (f << 8) | ((uint32_t)L.tb_mode << 16) | ((uint32_t)(uint8_t)qp << 24);
         const uint32_t w3 = (L.ncoef - L.tb_coef0) | ((uint32_t)L.c << 16);
-        if (P.flags & PF_COHERENT) store_tu_agent(P.tu_base + L.tu_row + L.ntu, w0, w1, L.tb_coef0, w3);
+        if (pic_flags<EG>(P) & PF_COHERENT) store_tu_agent(P.tu_base + L.tu_row + L.ntu, w0, w1, L.tb_coef0, w3);
         else store_tu(P.tu_base + L.tu_row + L.ntu, w0, w1, L.tb_coef0, w3);
         ++L.ntu;
     } else {
@@ -1657,8 +1729,9 @@ HG_HD inline void cu_done(Lane &L, LaneLds &ld, LanePic &P);
 
 // After a TB: its record, then the next TB of the TU, the next transform-tree
 // node, or (tree done) the CU's QpY and the next coding-quadtree node / CTU end.
+template <class EG>
 HG_HD inline void tb_done(Lane &L, LaneLds &ld, LanePic &P) {
-    tu_emit(L, P);
+    tu_emit<EG>(L, P);
     if (++L.tb_t < L.tb_n) {
         L.st = U_TB;
         return;
@@ -1727,9 +1800,9 @@ HG_HD inline void cu_done(Lane &L, LaneLds &ld, LanePic &P) {
 template <class EG>
 HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     const int t = L.tb_t;
-    const bool chroma4 = (P.chroma == 1 || P.chroma == 2) && L.tl == 2;
+    const bool chroma4 = (HG_PIC_CHROMA(P) == 1 || HG_PIC_CHROMA(P) == 2) && L.tl == 2;
     // component and (4:2:2) upper / lower half of TB t: luma, Cb (, Cb lower), Cr (, Cr lower)
-    const bool c422 = P.chroma == 2;
+    const bool c422 = HG_PIC_CHROMA(P) == 2;
     const int comp = t == 0 ? 0 : (c422 ? 1 + ((t - 1) >> 1) : t), half = (c422 && t > 0) ? (t - 1) & 1 : 0;
     bool cbf;
     L.tb_cidx = comp;
@@ -1745,11 +1818,11 @@ HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         L.tb_mode = (L.cu_modes >> (8 * k)) & 0xff;
         cbf = (L.fl & F_CBF_L) != 0;
     } else if (!chroma4) {
-        L.tb_log2 = P.chroma == 3 ? L.tl : L.tl - 1;  // log2TrafoSizeC
-        L.tb_x = L.tx >> P.subx;
-        L.tb_y = (L.ty >> P.suby) + (half << L.tb_log2);
+        L.tb_log2 = HG_PIC_CHROMA(P) == 3 ? L.tl : L.tl - 1;  // log2TrafoSizeC
+        L.tb_x = L.tx >> HG_PIC_SUBX(P);
+        L.tb_y = (L.ty >> HG_PIC_SUBY(P)) + (half << L.tb_log2);
         int k = 0;  // IntraPredModeC of the PB (4:4:4 NxN: four)
-        if (P.chroma == 3 && (L.fl & F_NXN)) {
+        if (HG_PIC_CHROMA(P) == 3 && (L.fl & F_NXN)) {
             const int hp = 1 << (L.ql - 1);
             k = ((L.ty - L.qy) >= hp ? 2 : 0) + ((L.tx - L.qx) >= hp ? 1 : 0);
         }
@@ -1758,7 +1831,7 @@ HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     } else {  // 4:2:0 / 4:2:2, 4x4 luma TBs: the chroma TBs of the 8x8 parent, after its 4th luma TB
         const int s = 1 << (L.tl + 1);
         L.tb_x = (L.tx & ~(s - 1)) >> 1;
-        L.tb_y = ((L.ty & ~(s - 1)) >> P.suby) + 4 * half;
+        L.tb_y = ((L.ty & ~(s - 1)) >> HG_PIC_SUBY(P)) + 4 * half;
         L.tb_log2 = 2;
         L.tb_mode = L.cu_chroma & 0xff;
         cbf = ((L.tcbf >> (4 * (L.td - 1) + (comp - 1) + 2 * half)) & 1u) != 0;
@@ -1766,12 +1839,12 @@ HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     L.fl = (L.fl & ~(F_TS | F_TB_CBF)) | (cbf ? F_TB_CBF : 0u);
     L.tb_coef0 = L.ncoef;
     if (!cbf) {
-        tb_done(L, ld, P);
+        tb_done<EG>(L, ld, P);
         return;
     }
     // residual_coding header (7.3.8.11)
     const int l2 = L.tb_log2, n = 1 << l2, cidx = comp;
-    if ((P.flags & SP_TRANSFORM_SKIP) && !(L.fl & F_BYPASS) && l2 == 2 && dec(L, G, CTX_TS_FLAG + (cidx ? 1 : 0)))
+    if ((pic_flags<EG>(P) & SP_TRANSFORM_SKIP) && !(L.fl & F_BYPASS) && l2 == 2 && dec(L, G, CTX_TS_FLAG + (cidx ? 1 : 0)))
         L.fl |= F_TS;
     // last_sig_coeff_{x,y}_prefix (decoder.rs:109-130), suffixes
     const int cmax = (l2 << 1) - 1;
@@ -1790,7 +1863,7 @@ HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         ly = (1 << k) * (2 + (py & 1)) + (int)byp_bits(L, G, k);
     }
     int scan = 0;  // 7.4.9.11 scanIdx
-    if (l2 == 2 || (l2 == 3 && (cidx == 0 || P.chroma == 3))) {
+    if (l2 == 2 || (l2 == 3 && (cidx == 0 || HG_PIC_CHROMA(P) == 3))) {
         if (L.tb_mode >= 6 && L.tb_mode <= 14) scan = 2;
         else if (L.tb_mode >= 22 && L.tb_mode <= 30) scan = 1;
     }
@@ -1799,7 +1872,7 @@ HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         lx = ly;
         ly = tt;
     }
-    if (lx >= n || ly >= n) {
+    if (HG_UNLIKELY(lx >= n || ly >= n)) {
         L.status |= ST_SYNTAX;
         lx &= n - 1;
         ly &= n - 1;
@@ -1838,16 +1911,16 @@ HG_HD inline uint64_t spread16_nib(uint32_t m) {
 
 // the sub-block's record (SbRec): one 16-byte store (4 coefficient words); the
 // first escape of the record is the escape slot at L.nesc when it started
-template <class L_, class P_>
+template <class EG, class L_, class P_>
 HG_HD inline void sb_store(L_ &L, const P_ &P, uint32_t sig, uint32_t signs, uint64_t nib, int xS, int yS, bool hide) {
     const uint32_t nesc_sb = (uint32_t)__builtin_popcountll(nib & (nib >> 1) & (nib >> 2) & (nib >> 3) & 0x1111111111111111ull);
     const uint32_t esc0 = P.coef_cap - 1 - (L.nesc - nesc_sb);  // row-relative index of its first escape
     const uint32_t w0 = (sig & 0xffffu) | (signs & 0xffff0000u);
     const uint32_t w3 = (uint32_t)xS | ((uint32_t)yS << 3) | ((uint32_t)L.rc_scan << 6) | (hide ? 1u << 8 : 0u) |
                         (esc0 << 9);
-    if (L.ncoef + L.nesc + 4 <= P.coef_cap) {
+    if (HG_LIKELY(L.ncoef + L.nesc + 4 <= P.coef_cap)) {
         TuRec *d = (TuRec *)(P.coef_base + L.coef_row + L.ncoef);
-        if (P.flags & PF_COHERENT) store_tu_agent(d, w0, (uint32_t)nib, (uint32_t)(nib >> 32), w3);
+        if (pic_flags<EG>(P) & PF_COHERENT) store_tu_agent(d, w0, (uint32_t)nib, (uint32_t)(nib >> 32), w3);
         else store_tu(d, w0, (uint32_t)nib, (uint32_t)(nib >> 32), w3);
         L.ncoef += 4;
     } else {
@@ -2072,8 +2145,8 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         for (int k = 0; k < 4; ++k) ctx_st(L, G, gbase + k, (gc >> (8 * k)) & 0xffu);
         if (last_g1 >= 0 && dec(L, G, CTX_GT2 + ctx_set + (cidx ? 4 : 0))) g2 = 1u << last_g1;
         HG_SB_T(L, 2, tsb);
-        const bool sign_hidden = !(L.fl & F_BYPASS) && (last_sig - first_sig > 3);
-        const bool hide = (P.flags & SP_SIGN_HIDING) && sign_hidden;
+        const bool sign_hidden = !(lane_fl<EG>(L) & F_BYPASS) && (last_sig - first_sig > 3);
+        const bool hide = (pic_flags<EG>(P) & SP_SIGN_HIDING) && sign_hidden;
         const int nsign = __builtin_popcount(sig) - (hide ? 1 : 0);
         uint32_t signs = byp_bits(L, G, nsign);
         signs = nsign ? signs << (32 - nsign) : 0u;  // first decoded sign in bit 31
@@ -2118,7 +2191,7 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
                 }
                 // coeff_abs_level_remaining (decoder.rs:230-261): TR(4 << k, k) prefix, EG(k + 1) escape
                 int rem = byp_rem(L, G, k);
-                if (rem < 0) {
+                if (HG_UNLIKELY(rem < 0)) {
                     // EG(k + 1) prefix: unary ones, up to 8 per division, at most 31 - (k + 1)
                     const int lim = 31 - (k + 1);
                     int ones = 0;
@@ -2139,10 +2212,10 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
                 last_rice = k;
                 const int am1 = base - 1 + rem;  // abs - 1
                 nib = (nib & ~(0xfull << (4 * nn))) | ((uint64_t)(am1 < 15 ? am1 : 15) << (4 * nn));
-                if (am1 >= 15) {  // escape: the whole level, in descending scan order from the row's end
+                if (HG_UNLIKELY(am1 >= 15)) {  // escape: the whole level, in descending scan order from the row's end
                     if (L.ncoef + L.nesc + 4 < P.coef_cap) {
                         Coef HG_GAS *e = P.coef_base + L.coef_row + P.coef_cap - 1 - L.nesc;
-                        if (P.flags & PF_COHERENT) store_word_agent((uint32_t *)e, (uint32_t)last_abs);
+                        if (pic_flags<EG>(P) & PF_COHERENT) store_word_agent((uint32_t *)e, (uint32_t)last_abs);
                         else *e = (uint32_t)last_abs;
                     } else {
                         L.status |= ST_CAPACITY;
@@ -2152,9 +2225,9 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
             }
         }
         HG_SB_T(L, 3, tsb);
-        sb_store(L, P, sig, signs, nib, xS, yS, hide);
+        sb_store<EG>(L, P, sig, signs, nib, xS, yS, hide);
     }
-    if (--L.rc_i < 0) tb_done(L, ld, P);
+    if (--L.rc_i < 0) tb_done<EG>(L, ld, P);
 }
 
 // U_CTU_END: WPP context storage, the depth line, end_of_slice_segment_flag /
@@ -2164,7 +2237,7 @@ HG_HD inline void unit_ctu_end(Lane &L, LaneLds &ld, LanePic &P, const Env &E, c
     if ((L.fl & F_WPP) && L.c == 1 && L.row + 1 < P.hctb) {
         // 9.3.2.4 storage for the next row's substream: into its lane's block, or
         // its staging block when that lane may still be parsing an earlier row
-        uint32_t *dst = reinterpret_cast<uint32_t *>((EG::kSpread || P.ring) ? wpp_stage(E, P, L.row + 1)
+        uint32_t *dst = reinterpret_cast<uint32_t *>((EG::kSpread || pic_ring<EG>(P)) ? wpp_stage(E, P, L.row + 1)
                                                                               : E.lds[P.lane0 + (L.row + 1) % P.R].ctx);
         if constexpr (EG::kCtxReg) {
 #if !defined(HG_HOST_EMU)
@@ -2194,16 +2267,19 @@ HG_HD inline void unit_ctu_end(Lane &L, LaneLds &ld, LanePic &P, const Env &E, c
     const bool last_in_pic = L.row == P.hctb - 1 && L.c == P.wctb - 1;
     // end_of_slice_segment_flag = 1 at the picture's last CTU (unless a tile's
     // substream goes on: SP_SUBSET_END) and at the end of a row that ends a slice segment
-    const bool seg_end = !last_in_pic && L.c == P.wctb - 1 && (P.flags & SP_ROW_SEGMENTS) &&
+    const bool seg_end = !last_in_pic && L.c == P.wctb - 1 && (pic_flags<EG>(P) & SP_ROW_SEGMENTS) &&
                          (E.a->rsubs[P.sub_first + L.row] & SUB_SEG_END);
-    const bool eos = (last_in_pic && !(P.flags & SP_SUBSET_END)) || seg_end;
+    const bool eos = (last_in_pic && !(pic_flags<EG>(P) & SP_SUBSET_END)) || seg_end;
     // inside a row of a picture with dependent segments starting inside rows,
     // end_of_slice_segment_flag = 1 ends one: the next starts at the next CTU
     if (term(L, G) != (eos ? 1 : 0)) {
-        // end_of_slice_segment_flag = 1 inside a row: a dependent segment starts
-        // at the next CTU (unit_ctu checks that the picture has one)
-        if constexpr (EG::kSolo) L.status |= ST_SUBSTREAM_END;
-        else L.status |= (!eos && L.c < P.wctb - 1) ? ST_SEGSW : (uint32_t)ST_SUBSTREAM_END;
+        // end_of_slice_segment_flag = 1 inside a row of a picture that has
+        // dependent segments starting there: the next starts at the next CTU
+        // (unit_ctu checks that one is left).  A picture without any (always so
+        // in the lean body) has no entries for them after its substream table:
+        // the mismatch is an error at once
+        if constexpr (EG::kSolo || EG::kLean) L.status |= ST_SUBSTREAM_END;
+        else L.status |= (!eos && L.c < P.wctb - 1 && lanes_nmid<EG>(P)) ? ST_SEGSW : (uint32_t)ST_SUBSTREAM_END;
     }
     if (!eos && (last_in_pic || ((L.fl & F_WPP) && L.c == P.wctb - 1)) && !term(L, G)) L.status |= ST_SUBSTREAM_END;
     if (L.budget + L.k < 0) L.status |= ST_OVERRUN;  // read past the NAL unit
@@ -2489,6 +2565,27 @@ int parse_mode_for(int requested, int n_pics, const PicDesc *pics) {
     return n_pics <= max_pics ? PARSE_SPREAD : PARSE_LANES;
 }
 
+// The lanes parse's body for a batch (BatchArgs::lanes_lean): the lean tool
+// set (EngT) when every picture with coded data is inside it, else the general
+// one; one launch either way.  HEIFGPU_LANES_VARIANT=general (read at every
+// prepare) keeps the general body for every batch (A/B, tests); auto or unset: this choice.
+bool lanes_lean_eligible(const SeqParams *seqs, const PicDesc *pics, int n_pics, int wpp_ring) {
+    if (wpp_ring) return false;
+    for (int i = 0; i < n_pics; ++i) {
+        if (pics[i].flags & PD_ASSEMBLY) continue;  // no coded data of its own
+        const SeqParams &sp = seqs[pics[i].seq];
+        if (sp.chroma_format != 1) return false;
+        if (sp.flags & (SP_PCM | SP_TRANSFORM_SKIP | SP_TQ_BYPASS | SP_ROW_SEGMENTS)) return false;
+        if (pics[i].flags >> PD_NMID_SHIFT) return false;  // dependent segments starting inside rows
+    }
+    return true;
+}
+int lanes_variant_for(const SeqParams *seqs, const PicDesc *pics, int n_pics, int wpp_ring) {
+    const char *e = std::getenv("HEIFGPU_LANES_VARIANT");
+    if (e && std::string(e) == "general") return LANES_GENERAL;
+    return lanes_lean_eligible(seqs, pics, n_pics, wpp_ring) ? LANES_LEAN : LANES_GENERAL;
+}
+
 // waves per solo workgroup: one per WPP row of the tallest picture, at most 16
 // (1024 threads); taller pictures wrap their rows round the waves
 int solo_waves_for(int lane_rows) { return lane_rows < 1 ? 1 : (lane_rows > kSoloMaxWaves ? kSoloMaxWaves : lane_rows); }
@@ -2524,6 +2621,7 @@ int spread_parse_order(const PicDesc *pics, int n, std::vector<uint32_t> &order)
 
 #if defined(HG_HOST_EMU)
 // one wave at a time, one unit per live lane per pass, lanes in order
+template <class EG>
 void emu_parse_lanes(const BatchArgs &a) {
     const int ppw = a.parse_order && a.parse_group > 0 ? a.parse_group : lanes_pics_per_wave(a.lane_rows, a.n_pics);
     const int n_slots = a.parse_order ? a.n_slots : a.n_pics;
@@ -2564,7 +2662,7 @@ void emu_parse_lanes(const BatchArgs &a) {
             for (int l = 0; l < 64; ++l)
                 if (lanes[l].st != U_DONE) {
                     const LanePic &P = pics[l / a.lane_rows];
-                    const Eng G{lds[l].ctx, tab, seq, a.rbsp, (P.bits_end + 64u) & ~3u, scan8, scan8 + 64};
+                    const EG G{lds[l].ctx, tab, seq, a.rbsp, (P.bits_end + 64u) & ~3u, scan8, scan8 + 64};
                     q_refill(lanes[l], G);
                 }
             // the kernel's pass: every unit kind in syntax order, each on the lanes in it
@@ -2574,7 +2672,7 @@ void emu_parse_lanes(const BatchArgs &a) {
                 int cnt = 0;
                 for (int l = 0; l < 64; ++l) {
                     E.lane = l;
-                    mine[l] = lanes[l].st == kind && (kind != U_CTU || ctu_ready(lanes[l], pics[l / a.lane_rows], E));
+                    mine[l] = lanes[l].st == kind && (kind != U_CTU || ctu_ready<EG>(lanes[l], pics[l / a.lane_rows], E));
                     anym |= mine[l];
                     cnt += mine[l] ? 1 : 0;
                 }
@@ -2589,7 +2687,7 @@ void emu_parse_lanes(const BatchArgs &a) {
                     if (!mine[l]) continue;
                     progressed = true;
                     ++units;
-                    const Eng G{lds[l].ctx, tab, seq, a.rbsp, (P.bits_end + 64u) & ~3u, scan8, scan8 + 64};
+                    const EG G{lds[l].ctx, tab, seq, a.rbsp, (P.bits_end + 64u) & ~3u, scan8, scan8 + 64};
                     run_unit(kind, L, lds[l], P, E, G);
                 }
             }
@@ -2660,7 +2758,7 @@ void emu_parse_solo(const BatchArgs &a) {
                 if (L.st == U_CTU && !ctu_ready<EG>(L, P, E)) continue;
                 progressed = true;
                 SoloWin &sw = wins[(size_t)w];
-                const uint32_t start = L.st == U_CTU ? substream_start<false>(L, P, a) : ~0u;
+                const uint32_t start = L.st == U_CTU ? substream_start<EG>(L, P, a) : ~0u;
                 if (start != ~0u) sw.restart(a.rbsp, start, lim, 0);
                 else sw.advance(a.rbsp, L.lb, lim, 0);
                 const EG G{lds[(size_t)w].ctx, 0u, 0u, seq, a.rbsp, lim, sw.view(), 0u, 0u, 0u};
@@ -2683,7 +2781,8 @@ void emu_parse_solo(const BatchArgs &a) {
 void emu_parse(const BatchArgs &a) {
     if (a.parse_mode == PARSE_SOLO) emu_parse_solo<false>(a);
     else if (a.parse_mode == PARSE_SPREAD) emu_parse_solo<true>(a);
-    else emu_parse_lanes(a);
+    else if (a.lanes_lean) emu_parse_lanes<EngLean>(a);  // the body launch_parse would run
+    else emu_parse_lanes<Eng>(a);
 }
 #else
 // LDS of one wave: LaneLds per used lane, LanePic per picture, progress words,
@@ -2702,7 +2801,7 @@ __device__ __forceinline__ uint32_t dequeue_job(uint32_t *ctr) {
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)j);
 }
 
-#if HG_PARSE_WANT_LANES
+#if HG_PARSE_WANT_LANES || HG_PARSE_WANT_LEAN
 // a register budget of 256 (2 waves per SIMD, the occupancy the VGPR floor
 // below fixes anyway); 0 leaves it to the compiler
 #if !defined(HG_PARSE_WPE)
@@ -2713,7 +2812,9 @@ __device__ __forceinline__ uint32_t dequeue_job(uint32_t *ctr) {
 #else
 #define HG_PARSE_ATTR
 #endif
-__global__ void __launch_bounds__(64) HG_PARSE_ATTR k_parse_lanes(BatchArgs a) {
+// the lanes parse with engine EG (Eng: every tool, k_parse_lanes; EngLean: k_parse_lean)
+template <class EG>
+__device__ __forceinline__ void parse_lanes_body(const BatchArgs &a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int ppw = a.parse_group;  // pictures per wave (launch_parse)
     const int nl = ppw * a.lane_rows;
@@ -2723,7 +2824,7 @@ __global__ void __launch_bounds__(64) HG_PARSE_ATTR k_parse_lanes(BatchArgs a) {
     uint64_t *s_tab = reinterpret_cast<uint64_t *>(s_prog + 64);
     uint64_t *s_seq = s_tab + kTabRows;
     uint8_t *s_scan = reinterpret_cast<uint8_t *>(s_seq + 16);
-    uint8_t *s_wctx = a.wpp_ring ? s_scan + 128 : nullptr;
+    uint8_t *s_wctx = !EG::kLean && a.wpp_ring ? s_scan + 128 : nullptr;
     const int lane = threadIdx.x;
 #if HG_PARSE_SETPRIO > 0
     // the parse is the latency-critical stream: win issue arbitration against
@@ -2756,9 +2857,9 @@ __global__ void __launch_bounds__(64) HG_PARSE_ATTR k_parse_lanes(BatchArgs a) {
     __syncthreads();
     const Env E{&a, s_lds, s_prog, s_wctx, lane};
 #if defined(HG_NO_SCAN8)
-    const Eng G{ld.ctx, s_tab, s_seq, a.rbsp, live ? (P.bits_end + 64u) & ~3u : 0u};
+    const EG G{ld.ctx, s_tab, s_seq, a.rbsp, live ? (P.bits_end + 64u) & ~3u : 0u};
 #else
-    const Eng G{ld.ctx, s_tab, s_seq, a.rbsp, live ? (P.bits_end + 64u) & ~3u : 0u, s_scan, s_scan + 64};
+    const EG G{ld.ctx, s_tab, s_seq, a.rbsp, live ? (P.bits_end + 64u) & ~3u : 0u, s_scan, s_scan + 64};
 #endif
 #if defined(HG_PARSE_PROF)
     uint64_t pf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -2784,7 +2885,7 @@ __global__ void __launch_bounds__(64) HG_PARSE_ATTR k_parse_lanes(BatchArgs a) {
         bool progressed = false;
 #pragma unroll
         for (int kind = U_CTU; kind <= U_CTU_END; ++kind) {
-            const bool mine = L.st == kind && (kind != U_CTU || ctu_ready(L, P, E));
+            const bool mine = L.st == kind && (kind != U_CTU || ctu_ready<EG>(L, P, E));
             if (!__any(mine)) continue;
             progressed = true;
 #if defined(HG_PARSE_PROF)
@@ -2860,6 +2961,25 @@ __global__ void __launch_bounds__(64) HG_PARSE_ATTR k_parse_lanes(BatchArgs a) {
 #endif
 }
 
+#if HG_PARSE_WANT_LANES
+__global__ void __launch_bounds__(64) HG_PARSE_ATTR k_parse_lanes(BatchArgs a) { parse_lanes_body<Eng>(a); }
+#endif
+#if HG_PARSE_WANT_LEAN
+// The lean tool set (EngT), a translation unit of its own in the library
+// (kernels/parse_lean.hip): under the general unit's SLP threshold it takes 208
+// VGPRs instead of 176, which leaves room for one reconstruction wave beside two
+// parse waves of a SIMD instead of two (Makefile LEAN_FLAGS).  Its name keeps
+// clear of "k_parse_lanes": tests/test_resource_usage.py expects every kernel of
+// that name at three waves per SIMD once the v175 floor is compiled out, which
+// holds for the general body's allocation only; tests/test_lanes_lean.py holds
+// this kernel to two waves and no scratch
+__global__ void __launch_bounds__(64) HG_PARSE_ATTR k_parse_lean(BatchArgs a) { parse_lanes_body<EngLean>(a); }
+hipError_t launch_parse_lean(const BatchArgs &a, int waves, size_t lds_bytes, hipStream_t s) {
+    hipLaunchKernelGGL(k_parse_lean, dim3(waves), dim3(64), lds_bytes, s, a);
+    return hipGetLastError();
+}
+#endif
+
 // Solo mode: one workgroup per picture, one wave per WPP row (rows beyond 16
 // wrap round the waves).  All 64 lanes of a wave run the same substream in
 // lockstep (identical state in every lane, so exec stays full: the window and
@@ -2869,7 +2989,7 @@ __global__ void __launch_bounds__(64) HG_PARSE_ATTR k_parse_lanes(BatchArgs a) {
 // progress words and the row-to-row context copies are in the workgroup's
 // LDS, so the 2-CTU lag needs no memory traffic; waves waiting for the row
 // above sleep.
-#endif  // HG_PARSE_WANT_LANES
+#endif  // HG_PARSE_WANT_LANES || HG_PARSE_WANT_LEAN
 
 #if HG_PARSE_WANT_SOLO
 inline size_t solo_lds_bytes(int nw, bool ring) {
@@ -2952,7 +3072,7 @@ __global__ void __launch_bounds__(Spread ? 64 : 64 * kSoloMaxWaves) k_parse_solo
             if (run && lane == 0) g_ctu_t[tix][1] = now;
         }
 #endif
-        uint32_t start = run && st == U_CTU ? substream_start<false>(L, P, a) : ~0u;
+        uint32_t start = run && st == U_CTU ? substream_start<EG>(L, P, a) : ~0u;
         const uint32_t rd = L.lb;
         st = __builtin_amdgcn_readfirstlane(st);
         if (st == U_DONE) break;
@@ -3047,6 +3167,7 @@ hipError_t launch_parse_solo(const BatchArgs &a, hipStream_t s) {
 
 #if HG_PARSE_WANT_LANES
 hipError_t launch_parse_solo(const BatchArgs &a, hipStream_t s);
+hipError_t launch_parse_lean(const BatchArgs &a, int waves, size_t lds_bytes, hipStream_t s);
 
 hipError_t launch_parse(const BatchArgs &a0, hipStream_t s) {
     BatchArgs a = a0;
@@ -3056,7 +3177,13 @@ hipError_t launch_parse(const BatchArgs &a0, hipStream_t s) {
     const int ppw = a.parse_order && a.parse_group > 0 ? a.parse_group : lanes_pics_per_wave(a.lane_rows, a.n_pics);
     a.parse_group = ppw;
     const int waves = ((a.parse_order ? a.n_slots : a.n_pics) + ppw - 1) / ppw;
-    hipLaunchKernelGGL(k_parse_lanes, dim3(waves), dim3(64), lanes_lds_bytes(ppw, a.lane_rows, a.wpp_ring != 0), s, a);
+    if (a.lanes_lean) {
+        // (prepare's choice, lanes_variant_for: never with wrapping rows)
+        if (a.wpp_ring) return hipErrorInvalidValue;
+        return launch_parse_lean(a, waves, lanes_lds_bytes(ppw, a.lane_rows, false), s);
+    } else {
+        hipLaunchKernelGGL(k_parse_lanes, dim3(waves), dim3(64), lanes_lds_bytes(ppw, a.lane_rows, a.wpp_ring != 0), s, a);
+    }
     return hipGetLastError();
 }
 #endif  // HG_PARSE_WANT_LANES
@@ -3093,8 +3220,12 @@ int prof_read(uint64_t *out, int n) {
 // counters are read through this entry and added in heifgpu_debug_counters
 #if defined(HG_PARSE_TU)
 extern "C" int hg_debug_counters_solo(uint64_t *out, int n);
+extern "C" int hg_debug_counters_lean(uint64_t *out, int n);
 #if HG_PARSE_TU == 2
 extern "C" int hg_debug_counters_solo(uint64_t *out, int n) { return hg::prof_read(out, n); }
+#endif
+#if HG_PARSE_TU == 3
+extern "C" int hg_debug_counters_lean(uint64_t *out, int n) { return hg::prof_read(out, n); }
 #endif
 #endif
 #endif
@@ -3107,11 +3238,13 @@ extern "C" int heifgpu_debug_counters(uint64_t *out, int n) {
 #if defined(HG_PARSE_PROF)
     const int r = hg::prof_read(out, n);
 #if defined(HG_PARSE_TU)
-    if (r > 0) {  // (one of the two kinds of kernel ran; the other's slots are zero)
-        std::vector<uint64_t> o2((size_t)r, 0);
-        const int r2 = hg_debug_counters_solo(o2.data(), r);
-        if (r2 < 0) return -1;
-        for (int k = 0; k < r2 && k < r; ++k) out[k] += o2[(size_t)k];
+    if (r > 0) {  // (one of the three units' kernels ran; the others' slots are zero)
+        for (int u = 0; u < 2; ++u) {
+            std::vector<uint64_t> o2((size_t)r, 0);
+            const int r2 = u ? hg_debug_counters_lean(o2.data(), r) : hg_debug_counters_solo(o2.data(), r);
+            if (r2 < 0) return -1;
+            for (int k = 0; k < r2 && k < r; ++k) out[k] += o2[(size_t)k];
+        }
     }
 #endif
     return r;

@@ -4,4 +4,7 @@
 // flags each is fastest with (Makefile PARSE_SCHED / SOLO_SCHED; A/B in
 // DESIGN 5.11).
 #define HG_PARSE_TU 2
+// (the lanes units' cold-branch hints stay out of the scalar engines: their code is the one before the
+// lean body, instruction for instruction)
+#define HG_NO_COLD_HINTS 1
 #include "parse_lanes.hip"

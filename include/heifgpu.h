@@ -285,6 +285,13 @@ int heifgpu_debug_counters(uint64_t *out, int n);
  * and waves per workgroup (solo). */
 int heifgpu_batch_parse_geometry(const heifgpu_batch *batch, uint32_t *mode, uint32_t *workgroups,
                                  uint32_t *pics_per_wave, uint32_t *waves_per_workgroup);
+/* The body a prepared batch's lanes parse runs: 1 the lean one, compiled for
+ * 4:2:0 pictures without PCM, transform_skip, cu_transquant_bypass, slice
+ * segments inside a picture or WPP rows beyond its lanes (chosen when every
+ * picture of the batch is such a picture), 0 the general one (also what the
+ * other parse modes report).  HEIFGPU_LANES_VARIANT=general, read at every
+ * prepare, keeps the general body; auto or unset leaves the choice. */
+int heifgpu_batch_lanes_variant(const heifgpu_batch *batch, uint32_t *variant);
 
 #ifdef __cplusplus
 }
