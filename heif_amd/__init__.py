@@ -87,6 +87,14 @@ class HeifImage:
         _lib.check(lib.heifgpu_image_get_info(self._h, ctypes.byref(info)))
         return info
 
+    @property
+    def display(self) -> _lib.DisplayInfo:
+        """How the image is shown (heifgpu_image_get_display): displayed size,
+        the folded clap / irot / imir map, the alpha auxiliary item."""
+        d = _lib.DisplayInfo()
+        _lib.check(lib.heifgpu_image_get_display(self._h, ctypes.byref(d)))
+        return d
+
     def tile_params(self, tile: int) -> dict:
         """Parsed SPS/PPS/slice-header fields of grid tile `tile` (row-major)."""
         tp = _lib.TileParams()
@@ -117,6 +125,7 @@ class DecodedImage:
     cb: Optional["object"]  # (ceil(H/2), ceil(W/2)) for 4:2:0
     cr: Optional["object"]
     info: _lib.ImageInfo
+    image: Optional["HeifImage"] = None  # the parsed image (its display map; DecodeContext.render)
 
 
 class DecodeContext:
@@ -166,6 +175,8 @@ class DecodeContext:
             dt = torch.uint8 if inf.bytes_per_sample == 1 else torch.int16
             pl = [buf[o:o + h * w * inf.bytes_per_sample].view(dt).view(h, w) for o, h, w in offs]
             outs.append(DecodedImage(pl[0], pl[1] if len(pl) > 1 else None, pl[2] if len(pl) > 1 else None, inf))
+        for o, im in zip(outs, images):
+            o.image = im
         return outs, buf
 
     def alloc_outputs(self, images: Sequence[HeifImage]) -> List[DecodedImage]:
@@ -181,7 +192,7 @@ class DecodeContext:
                 ch, cw = chroma_dims(inf)
                 cb = torch.empty((ch, cw), dtype=dt, device=dev)
                 cr = torch.empty((ch, cw), dtype=dt, device=dev)
-            outs.append(DecodedImage(y, cb, cr, inf))
+            outs.append(DecodedImage(y, cb, cr, inf, im))
         return outs
 
     @staticmethod
@@ -268,6 +279,47 @@ class DecodeContext:
         _lib.check(lib.heifgpu_ycbcr_to_rgb(self._h, ctypes.byref(inf), planes, ctypes.c_void_p(rgb.data_ptr()),
                                             rgb.stride(0), ctypes.c_void_p(stream)))
         return rgb
+
+
+    def render(self, outs: Sequence[DecodedImage], fmt: str = "rgb8",
+               alphas: Optional[Sequence[Optional[DecodedImage]]] = None, stream: Optional[int] = None):
+        """Display-ready pixels of a batch of decoded images with ONE
+        heifgpu_render_batch call (one kernel launch): a list of (H', W', C)
+        device tensors, C = 3 or 4, uint8 for "rgb8" / "rgba8" and int16 (like
+        the 16-bit planes) for "rgb16" / "rgba16", with every image's clap /
+        irot / imir applied.  alphas[i] is the decoded alpha image of outs[i]
+        (None = opaque).  The images come from alloc_outputs (they carry their
+        parsed HeifImage)."""
+        torch = self._torch
+        n = len(outs)
+        f = _lib.PIX_FORMATS[fmt]
+        ch, wide = (4 if f & 1 else 3), f >= _lib.PIX_RGB16
+        if any(o.image is None for o in outs) or (alphas is not None and any(a is not None and a.image is None for a in alphas)):
+            raise ValueError("render needs images that carry their HeifImage (alloc_outputs)")
+        if alphas is not None and len(alphas) != n:
+            raise ValueError("alphas must have one entry per image")
+        dev = torch.device("cuda", self.device)
+        res, surf = [], (_lib.Surface * max(n, 1))()
+        for i, o in enumerate(outs):
+            d = o.image.display
+            t = torch.empty((d.out_height, d.out_width, ch), dtype=torch.int16 if wide else torch.uint8, device=dev)
+            surf[i].pixels = t.data_ptr()
+            surf[i].pitch = t.stride(0) * t.element_size()
+            res.append(t)
+        imgs = (ctypes.c_void_p * max(n, 1))(*[o.image._h.value for o in outs])
+        aimgs = aplanes = None
+        if alphas is not None:
+            aimgs = (ctypes.c_void_p * max(n, 1))(*[a.image._h.value if a is not None else None for a in alphas])
+            aplanes = (_lib.Planes * max(n, 1))()
+            for i, a in enumerate(alphas):
+                if a is not None:
+                    aplanes[i].plane[0] = a.y.data_ptr()
+                    aplanes[i].pitch[0] = a.y.stride(0) * a.y.element_size()
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(lib.heifgpu_render_batch(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f, surf,
+                                            ctypes.c_void_p(stream)))
+        return res
 
 
 def ipc_export(tensor) -> bytes:
@@ -380,6 +432,20 @@ class HeicDecoder:
     def decode_rgb(cls, data: bytes, device: int = 0, item_id: int = 0):
         """decode() then YCbCr -> RGB8 with the irot rotation (libheif's default output)."""
         return cls.context(device).to_rgb(cls.decode(data, device, item_id))
+
+    @classmethod
+    def decode_display(cls, data: bytes, fmt: Optional[str] = None, device: int = 0):
+        """The picture a viewer shows: decodes the primary image and, when it
+        has one (display.alpha_item_id), its alpha plane, then renders
+        (DecodeContext.render) with clap / irot / imir applied.  fmt None picks
+        RGBA when there is alpha and 16 bits when the bit depth is above 8."""
+        ctx = cls.context(device)
+        out = cls.decode(data, device)
+        aid = out.image.display.alpha_item_id
+        alpha = cls.decode(data, device, aid) if aid else None
+        if fmt is None:
+            fmt = ("rgba" if alpha is not None else "rgb") + ("16" if out.info.bit_depth > 8 else "8")
+        return ctx.render([out], fmt, [alpha] if alpha is not None else None)[0]
 
     @classmethod
     def decode(cls, data: bytes, device: int = 0, item_id: int = 0) -> DecodedImage:

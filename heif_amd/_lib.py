@@ -121,6 +121,24 @@ class IpcHandle(ctypes.Structure):
     _fields_ = [("handle", ctypes.c_uint8 * 64), ("offset", ctypes.c_uint64)]
 
 
+class DisplayInfo(ctypes.Structure):
+    """heifgpu_display_info: displayed size, the folded clap / irot / imir map
+    (output pixel (ox, oy) shows decoded sample (m0*ox + m1*oy + t0, m2*ox + m3*oy + t1))
+    and the alpha auxiliary image."""
+    _fields_ = [("out_width", ctypes.c_uint32), ("out_height", ctypes.c_uint32),
+                ("m", ctypes.c_int32 * 4), ("t", ctypes.c_int32 * 2),
+                ("n_transforms", ctypes.c_uint32), ("alpha_item_id", ctypes.c_uint32),
+                ("alpha_premultiplied", ctypes.c_uint32)]
+
+
+class Surface(ctypes.Structure):
+    """heifgpu_surface: interleaved output pixels on the device, bytes per row."""
+    _fields_ = [("pixels", ctypes.c_void_p), ("pitch", ctypes.c_int32)]
+
+
+PIX_RGB8, PIX_RGBA8, PIX_RGB16, PIX_RGBA16 = 0, 1, 2, 3
+PIX_FORMATS = {"rgb8": PIX_RGB8, "rgba8": PIX_RGBA8, "rgb16": PIX_RGB16, "rgba16": PIX_RGBA16}
+
 PARSE_AUTO, PARSE_LANES, PARSE_SOLO, PARSE_SPREAD = 0, 1, 2, 3
 PARSE_ROWS = 4  # ABI 5 only; removed in ABI 6 (prepare answers HEIFGPU_E_UNSUPPORTED)
 PARSE_MODES = {"auto": PARSE_AUTO, "lanes": PARSE_LANES, "solo": PARSE_SOLO, "spread": PARSE_SPREAD}
@@ -138,6 +156,7 @@ EXPORTS = (
     "heifgpu_image_parse_item", "heifgpu_ycbcr_to_rgb", "heifgpu_batch_prepare_ex", "heifgpu_gather_tiles",
     "heifgpu_image_parse_many", "heifgpu_batch_parse_geometry", "heifgpu_ipc_export", "heifgpu_ipc_open",
     "heifgpu_ipc_close", "heifgpu_batch_status_previous", "heifgpu_abi_version", "heifgpu_batch_lanes_variant",
+    "heifgpu_image_get_display", "heifgpu_render_batch",
 )
 
 
@@ -209,6 +228,8 @@ def _load() -> ctypes.CDLL:
         "heifgpu_ipc_open": (I32, [I32, P(IpcHandle), P(VP)]),
         "heifgpu_ipc_close": (I32, [VP]),
         "heifgpu_batch_lanes_variant": (I32, [VP, P(U32)]),
+        "heifgpu_image_get_display": (I32, [VP, P(DisplayInfo)]),
+        "heifgpu_render_batch": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), U32, P(Surface), VP]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     optional = {"heifgpu_batch_lanes_variant"}

@@ -29,6 +29,11 @@ struct heifgpu_image {
 static_assert(sizeof(heifgpu_image_info) == 80, "heifgpu_image_info: 20 x uint32");
 static_assert(sizeof(heifgpu_planes) == 40, "heifgpu_planes: 3 pointers + 3 int32 (+ padding)");
 static_assert(sizeof(heifgpu_batch_opts) == 20, "heifgpu_batch_opts: 5 x uint32");
+static_assert(sizeof(heifgpu_display_info) == 44, "heifgpu_display_info: 11 x 32 bits");
+static_assert(sizeof(heifgpu_surface) == 16, "heifgpu_surface: pointer + int32 (+ padding)");
+static_assert(HEIFGPU_PIX_RGB8 == RENDER_RGB8 && HEIFGPU_PIX_RGBA8 == RENDER_RGBA8 && HEIFGPU_PIX_RGB16 == RENDER_RGB16 &&
+                  HEIFGPU_PIX_RGBA16 == RENDER_RGBA16,
+              "pixel formats");
 static_assert(sizeof(heifgpu_ipc_handle) == 72, "heifgpu_ipc_handle: 64-byte HIP handle + uint64 offset");
 static_assert(HEIFGPU_PARSE_AUTO == PARSE_AUTO && HEIFGPU_PARSE_LANES == PARSE_LANES && HEIFGPU_PARSE_SOLO == PARSE_SOLO &&
                   HEIFGPU_PARSE_SPREAD == PARSE_SPREAD,
@@ -53,6 +58,7 @@ static_assert(sizeof(heifgpu_tile_params) == 55 * 4 + 64 * 4, "heifgpu_tile_para
 // step and three sets win (same-box pairs at 20 steps: 18.56 / 18.49 vs
 // 17.86 / 17.77 Gpix/s, profiles/r03d/ab_pipeline_sets.txt).
 constexpr int kTimingSlots = 32;
+struct RenderRing;  // heifgpu_render_batch's descriptor staging (below)
 struct heifgpu_ctx {
     int device = 0;
     bool timing = false;
@@ -69,6 +75,7 @@ struct heifgpu_ctx {
     hipEvent_t tev[kTimingSlots][10] = {};
     int timed_calls = 0, folded = 0;
     double acc[6] = {};
+    RenderRing *render = nullptr;  // created by the first heifgpu_render_batch
 };
 
 namespace {
@@ -178,6 +185,25 @@ struct PinnedBuf {
 };
 
 }  // namespace
+
+// heifgpu_render_batch's descriptors travel through a ring of slots, each a
+// pinned host image, a device array and an event recorded behind the kernel
+// that reads them: a call never rewrites descriptors that an earlier call's
+// copy or kernel may still read (the host waits only when the ring wraps).
+constexpr int kRenderSlots = 4;
+struct RenderRing {
+    struct Slot {
+        PinnedBuf host;
+        DevBuf<RenderDesc> dev;
+        hipEvent_t done = nullptr;
+        bool pending = false;
+    } slot[kRenderSlots];
+    int next = 0;
+    ~RenderRing() {
+        for (Slot &s : slot)
+            if (s.done) (void)hipEventDestroy(s.done);
+    }
+};
 
 // outputs of one k_parse run (see heifgpu_ctx)
 struct ParseSet {
@@ -478,6 +504,112 @@ int heifgpu_ycbcr_to_rgb(heifgpu_ctx *ctx, const heifgpu_image_info *info, const
     return HEIFGPU_OK;
 }
 
+int heifgpu_image_get_display(const heifgpu_image *img, heifgpu_display_info *out) {
+    if (!img || !out) return fail(HEIFGPU_E_INVALID, "null argument");
+    const ParsedImage &p = img->img;
+    std::memset(out, 0, sizeof(*out));
+    out->out_width = p.display.out_width;
+    out->out_height = p.display.out_height;
+    for (int k = 0; k < 4; ++k) out->m[k] = p.display.m[k];
+    out->t[0] = p.display.t[0];
+    out->t[1] = p.display.t[1];
+    out->n_transforms = p.display.n_transforms;
+    out->alpha_item_id = p.alpha_item_id;
+    out->alpha_premultiplied = p.alpha_premultiplied;
+    return HEIFGPU_OK;
+}
+
+int heifgpu_render_batch(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                         const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                         const heifgpu_surface *out, void *stream) {
+    if (!ctx || !imgs || !in || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    const bool wide = format >= HEIFGPU_PIX_RGB16, with_alpha = (format & 1) != 0;
+    const int bpp = (with_alpha ? 4 : 3) * (wide ? 2 : 1);
+    std::vector<RenderDesc> descs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
+        heifgpu_image_info info;
+        heifgpu_image_get_info(imgs[i], &info);
+        const DisplayMap &dm = imgs[i]->img.display;
+        if (!in[i].plane[0] || !out[i].pixels) return fail(HEIFGPU_E_INVALID, "missing plane or surface");
+        if (info.chroma_format_idc && (!in[i].plane[1] || !in[i].plane[2]))
+            return fail(HEIFGPU_E_INVALID, "missing chroma plane");
+        if (info.bit_depth < 8 || info.bit_depth > (wide ? 12u : 16u)) return fail(HEIFGPU_E_INVALID, "bit depth");
+        if (bps && bps != int(info.bytes_per_sample))
+            return fail(HEIFGPU_E_UNSUPPORTED, "images of 1-byte and 2-byte samples in one render call");
+        bps = int(info.bytes_per_sample);
+        if (int64_t(out[i].pitch) < int64_t(bpp) * dm.out_width)
+            return fail(HEIFGPU_E_INVALID, "surface pitch smaller than the output row");
+        if (wide && ((reinterpret_cast<uintptr_t>(out[i].pixels) | uint32_t(out[i].pitch)) & 1))
+            return fail(HEIFGPU_E_INVALID, "16-bit surface not 2-byte aligned");
+        // the map's corners inside the decoded planes (parse_heic built it so; the kernel reads unchecked)
+        for (int c = 0; c < 4; ++c) {
+            const int64_t ox = (c & 1) ? int64_t(dm.out_width) - 1 : 0, oy = (c & 2) ? int64_t(dm.out_height) - 1 : 0;
+            const int64_t x = dm.m[0] * ox + dm.m[1] * oy + dm.t[0], y = dm.m[2] * ox + dm.m[3] * oy + dm.t[1];
+            if (x < 0 || y < 0 || x >= int64_t(info.width) || y >= int64_t(info.height))
+                return fail(HEIFGPU_E_INVALID, "display map outside the decoded image");
+        }
+        RenderDesc &d = descs[i];
+        d = RenderDesc{};
+        for (int k = 0; k < 3; ++k) {
+            d.plane[k] = reinterpret_cast<uint64_t>(in[i].plane[k]);
+            d.pitch[k] = in[i].pitch[k];
+        }
+        d.out = reinterpret_cast<uint64_t>(out[i].pixels);
+        d.out_pitch = out[i].pitch;
+        d.out_w = int32_t(dm.out_width);
+        d.out_h = int32_t(dm.out_height);
+        for (int k = 0; k < 4; ++k) d.m[k] = dm.m[k];
+        d.t[0] = dm.t[0];
+        d.t[1] = dm.t[1];
+        d.swap = dm.m[0] == 0;
+        const int tw = d.swap ? kRenderTile : kRenderRowW, th = d.swap ? kRenderTile : kRenderRowH;
+        d.tiles_x = (d.out_w + tw - 1) / tw;
+        d.tiles = d.tiles_x * ((d.out_h + th - 1) / th);
+        max_tiles = std::max(max_tiles, d.tiles);
+        d.chroma = int32_t(info.chroma_format_idc);
+        const int depth = wide ? int(info.bit_depth) : 8;  // the depth the arithmetic runs at
+        d.shift = int32_t(info.bit_depth) - depth;
+        render_coefs(info.matrix_coeffs, info.full_range != 0, depth, d);
+        if (with_alpha && alpha_imgs && alpha_imgs[i]) {
+            if (!alpha_in || !alpha_in[i].plane[0]) return fail(HEIFGPU_E_INVALID, "missing alpha plane");
+            heifgpu_image_info ai;
+            heifgpu_image_get_info(alpha_imgs[i], &ai);
+            if (ai.width != info.width || ai.height != info.height)
+                return fail(HEIFGPU_E_UNSUPPORTED, "alpha image of another size than its colour image");
+            if (int(ai.bytes_per_sample) != bps)
+                return fail(HEIFGPU_E_UNSUPPORTED, "images of 1-byte and 2-byte samples in one render call");
+            d.alpha = reinterpret_cast<uint64_t>(alpha_in[i].plane[0]);
+            d.alpha_pitch = alpha_in[i].pitch[0];
+            d.alpha_bps = int32_t(ai.bytes_per_sample);
+            d.alpha_shift = int32_t(ai.bit_depth) - depth;  // right when positive, left when negative
+        }
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->render) {
+        auto ring = std::make_unique<RenderRing>();
+        for (RenderRing::Slot &sl : ring->slot) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+        ctx->render = ring.release();
+    }
+    RenderRing::Slot &sl = ctx->render->slot[ctx->render->next];
+    ctx->render->next = (ctx->render->next + 1) % kRenderSlots;
+    if (sl.pending) HIP_TRY(hipEventSynchronize(sl.done));  // the call that used this slot last
+    sl.pending = false;
+    const size_t bytes = n * sizeof(RenderDesc);
+    HIP_TRY(sl.host.reserve(bytes));
+    HIP_TRY(sl.dev.alloc(n));
+    std::memcpy(sl.host.p, descs.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_render(sl.dev.p, int(n), max_tiles, int(format), bps, s));  // the one launch
+    HIP_TRY(hipEventRecord(sl.done, s));
+    sl.pending = true;
+    return HEIFGPU_OK;
+}
+
 void heifgpu_image_free(heifgpu_image *img) { delete img; }
 
 int heifgpu_create(int device, heifgpu_ctx **out) {
@@ -533,6 +665,7 @@ void heifgpu_destroy(heifgpu_ctx *ctx) {
     if (ctx->recon) (void)hipStreamDestroy(ctx->recon);
     if (ctx->upload) (void)hipStreamDestroy(ctx->upload);
     if (ctx->prep) (void)hipStreamDestroy(ctx->prep);
+    delete ctx->render;
     delete ctx;
 }
 

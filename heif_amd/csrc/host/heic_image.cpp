@@ -2,6 +2,7 @@
 #include "heic_image.hpp"
 
 #include <algorithm>
+#include <cstring>
 #include <map>
 
 namespace hg {
@@ -113,6 +114,66 @@ void check_segments(TileJob &job, const ParamSet &ps) {
 }
 
 }  // namespace
+
+namespace {
+// new[oy][ox] = cur[a * (ox, oy) + b]: composes the step behind the map so far
+void display_step(DisplayMap &d, const int32_t a[4], const int32_t b[2], uint32_t w, uint32_t h) {
+    const int32_t m[4] = {d.m[0] * a[0] + d.m[1] * a[2], d.m[0] * a[1] + d.m[1] * a[3],
+                          d.m[2] * a[0] + d.m[3] * a[2], d.m[2] * a[1] + d.m[3] * a[3]};
+    const int32_t t[2] = {d.m[0] * b[0] + d.m[1] * b[1] + d.t[0], d.m[2] * b[0] + d.m[3] * b[1] + d.t[1]};
+    for (int k = 0; k < 4; ++k) d.m[k] = m[k];
+    d.t[0] = t[0];
+    d.t[1] = t[1];
+    d.out_width = w;
+    d.out_height = h;
+    ++d.n_transforms;
+}
+int64_t floor_div(int64_t a, int64_t b) {  // b > 0
+    return a >= 0 ? a / b : -((-a + b - 1) / b);
+}
+}  // namespace
+
+void display_clap(DisplayMap &d, const uint8_t *q, size_t len) {
+    if (len < 32) throw HeifError("clap too short");
+    int64_t f[8];
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t v = (uint32_t(q[4 * k]) << 24) | (uint32_t(q[4 * k + 1]) << 16) | (uint32_t(q[4 * k + 2]) << 8) | q[4 * k + 3];
+        // the offsets' numerators are signed; a denominator with the top bit set counts as negative
+        f[k] = (k == 0 || k == 2) ? int64_t(v) : int64_t(int32_t(v));
+    }
+    for (int k = 1; k < 8; k += 2)
+        if (f[k] <= 0) throw HeifError("clap: zero or negative denominator");
+    const int64_t W = d.out_width, H = d.out_height;
+    // round_half_up(n / d) = floor((2n + d) / 2d), exact in int64 (|n|, d < 2^32, W, H < 2^32)
+    const int64_t cw = floor_div(2 * f[0] + f[1], 2 * f[1]), ch = floor_div(2 * f[2] + f[3], 2 * f[3]);
+    if (cw < 1 || ch < 1) throw HeifError("clap: empty clean aperture");
+    if (cw > W || ch > H) throw HeifError("clap: clean aperture outside the image");
+    const int64_t left = floor_div(2 * f[4] + (W - cw) * f[5] + f[5], 2 * f[5]);
+    const int64_t top = floor_div(2 * f[6] + (H - ch) * f[7] + f[7], 2 * f[7]);
+    if (left < 0 || top < 0 || left + cw > W || top + ch > H) throw HeifError("clap: clean aperture outside the image");
+    const int32_t a[4] = {1, 0, 0, 1}, b[2] = {int32_t(left), int32_t(top)};
+    display_step(d, a, b, uint32_t(cw), uint32_t(ch));
+}
+
+void display_irot(DisplayMap &d, uint32_t quarter_turns) {
+    const uint32_t n = d.n_transforms;
+    for (uint32_t k = 0; k < (quarter_turns & 3); ++k) {
+        // np.rot90(img)[oy][ox] = img[ox][W - 1 - oy]
+        const int32_t a[4] = {0, -1, 1, 0}, b[2] = {int32_t(d.out_width) - 1, 0};
+        display_step(d, a, b, d.out_height, d.out_width);
+    }
+    d.n_transforms = n + 1;  // one box, whatever its angle
+}
+
+void display_imir(DisplayMap &d, uint32_t axis) {
+    if (axis & 1) {
+        const int32_t a[4] = {1, 0, 0, -1}, b[2] = {0, int32_t(d.out_height) - 1};
+        display_step(d, a, b, d.out_width, d.out_height);
+    } else {
+        const int32_t a[4] = {-1, 0, 0, 1}, b[2] = {int32_t(d.out_width) - 1, 0};
+        display_step(d, a, b, d.out_width, d.out_height);
+    }
+}
 
 ParsedImage parse_heic(const uint8_t *data, size_t len, uint32_t item_id) {
     HeifReader reader(data, len);
@@ -256,6 +317,38 @@ ParsedImage parse_heic(const uint8_t *data, size_t len, uint32_t item_id) {
     }
     if (img.out_width > img.cols * img.tile_width || img.out_height > img.rows * img.tile_height)
         throw HeifError("grid output larger than its tiles");
+
+    // display geometry: the transformative properties in the order ipma lists them
+    // (ISO/IEC 23008-12 6.5: a reader applies them in that order), several of a kind allowed
+    img.display.out_width = img.out_width;
+    img.display.out_height = img.out_height;
+    for (uint32_t idx : pi->properties) {
+        if (idx == 0 || idx > heif.properties.size()) continue;
+        const Property &p = heif.properties[idx - 1];
+        if (p.type == fourcc('c', 'l', 'a', 'p')) display_clap(img.display, data + p.offset, p.length);
+        else if (p.type == fourcc('i', 'r', 'o', 't') && p.length >= 1) display_irot(img.display, data[p.offset] & 3u);
+        else if (p.type == fourcc('i', 'm', 'i', 'r') && p.length >= 1) display_imir(img.display, data[p.offset] & 1u);
+    }
+    // alpha: the first auxiliary image of this item whose auxC (FullBox, then the
+    // zero-terminated aux_type URN) names an alpha plane; other auxiliaries (a gain
+    // map, depth) are passed over
+    static const char *const kAlphaUrn[2] = {"urn:mpeg:hevc:2015:auxid:1", "urn:mpeg:mpegB:cicp:systems:auxiliary:alpha"};
+    for (const auto &r : heif.references) {
+        if (r.type != fourcc('a', 'u', 'x', 'l') || img.alpha_item_id) continue;
+        if (std::find(r.to.begin(), r.to.end(), img.item_id) == r.to.end()) continue;
+        const ItemInfo *ai = heif.item_info_by_item_id(r.from);
+        const Property *ac = ai ? heif.item_property(*ai, fourcc('a', 'u', 'x', 'C')) : nullptr;
+        if (!ac || ac->length < 4) continue;
+        const char *urn = reinterpret_cast<const char *>(data + ac->offset + 4);
+        const size_t ulen = strnlen(urn, ac->length - 4);
+        for (const char *want : kAlphaUrn)
+            if (ulen == std::strlen(want) && std::memcmp(urn, want, ulen) == 0) img.alpha_item_id = r.from;
+    }
+    if (img.alpha_item_id)
+        for (const auto &r : heif.references)
+            if (r.type == fourcc('p', 'r', 'e', 'm') && r.from == img.item_id &&
+                std::find(r.to.begin(), r.to.end(), img.alpha_item_id) != r.to.end())
+                img.alpha_premultiplied = 1;
     return img;
 }
 

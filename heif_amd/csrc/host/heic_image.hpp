@@ -29,6 +29,25 @@ struct TileJob {
     int param = 0;
 };
 
+// Output pixel (ox, oy) of the displayed image shows decoded sample
+// (m[0]*ox + m[1]*oy + t[0], m[2]*ox + m[3]*oy + t[1]); m is a signed permutation matrix.
+struct DisplayMap {
+    uint32_t out_width = 0, out_height = 0;
+    int32_t m[4] = {1, 0, 0, 1}, t[2] = {0, 0};
+    uint32_t n_transforms = 0;
+};
+// The three transformative item properties as steps of a DisplayMap that starts as
+// the identity over the decoded W x H image (ISO/IEC 23008-12 6.5.9 / .10 / .12).
+// The conventions, in this one place ("parity unpinned": neither the reference nor
+// anything else at hand renders them):
+//   clap: img[top:top+ch, left:left+cw]; payload = 8 x 32-bit (width N/D, height N/D,
+//         horizOff N/D, vertOff N/D; offsets signed), sizes and offsets rounded half up
+//   irot: np.rot90(img, k), anticlockwise
+//   imir: axis 0 = vertical axis, img[:, ::-1]; axis 1 = horizontal axis, img[::-1, :]
+void display_clap(DisplayMap &d, const uint8_t *payload, size_t len);  // throws HeifError
+void display_irot(DisplayMap &d, uint32_t quarter_turns);
+void display_imir(DisplayMap &d, uint32_t axis);
+
 struct ParsedImage {
     // move-only: the tiles' payload views point into `coded`, whose buffer a move keeps
     ParsedImage() = default;
@@ -46,6 +65,11 @@ struct ParsedImage {
     uint32_t nclx_matrix = 0, nclx_full_range = 0;
     uint32_t rows = 1, cols = 1, out_width = 0, out_height = 0;
     uint32_t tile_width = 0, tile_height = 0, coded_bytes = 0;
+    // the item's transformative properties (clap / irot / imir) in ipma order, folded
+    DisplayMap display;
+    // first 'auxl' image of the decoded item whose auxC names an alpha plane (0: none);
+    // a 'prem' reference from the item to it is reported, nothing is un-premultiplied
+    uint32_t alpha_item_id = 0, alpha_premultiplied = 0;
 };
 
 // Throws HeifError (parse) or UnsupportedError (valid stream, tool outside this path).

@@ -107,6 +107,57 @@ inline void color_coefs(uint32_t matrix, bool full, ColorArgs &c) {
     c.cr_g = fx(2.0 * kr * (1.0 - kr) / kg * cs);
 }
 
+// k_render (render.hip): one descriptor per image of a heifgpu_render_batch call.
+// Output pixel (ox, oy) shows decoded sample (m[0]*ox + m[1]*oy + t[0],
+// m[2]*ox + m[3]*oy + t[1]); the host has checked that the whole output maps
+// inside the w x h planes.
+enum : int { RENDER_RGB8 = 0, RENDER_RGBA8 = 1, RENDER_RGB16 = 2, RENDER_RGBA16 = 3 };
+constexpr int kRenderTile = 64;                   // axis-swapping images: 64 x 64 output pixels per workgroup
+constexpr int kRenderRowW = 256, kRenderRowH = 16;  // the others: 256 x 16
+struct RenderDesc {
+    uint64_t plane[3];  // Y, Cb, Cr (device)
+    uint64_t alpha;     // the alpha image's luma plane, 0 = opaque
+    uint64_t out;       // interleaved pixels (device)
+    int32_t pitch[3], alpha_pitch, out_pitch;  // bytes
+    int32_t out_w, out_h;
+    int32_t m[4], t[2];
+    int32_t tiles_x, tiles;  // the image's tiles (of its path's shape) along x and in all
+    int32_t swap;            // m[0] == 0: output x runs along source y (staged through LDS)
+    int32_t chroma, shift;   // chroma_format_idc; samples >> shift before the arithmetic (8-bit formats: depth - 8)
+    int32_t alpha_bps, alpha_shift;  // alpha sample bytes; a >> alpha_shift, or a << -alpha_shift
+    int32_t yoff, cmid, maxv;        // luma offset, chroma centre, clip (255, or (1 << depth) - 1)
+    int32_t ys, cr_r, cb_g, cr_g, cb_b;  // 16.16, as ColorArgs
+};
+// ColorArgs coefficients at bit depth `depth`: color_coefs itself at 8; above it the
+// offsets and the limited-range scales of that depth, ((1 << B) - 1) / (219 << (B - 8)) and
+// ((1 << B) - 1) / (224 << (B - 8)), rounded to 16.16 the same way
+inline void render_coefs(uint32_t matrix, bool full, int depth, RenderDesc &d) {
+    ColorArgs c{};
+    color_coefs(matrix, full, c);
+    if (depth > 8) {
+        double kr = 0.299, kb = 0.114;
+        if (matrix == 1) kr = 0.2126, kb = 0.0722;
+        else if (matrix == 9) kr = 0.2627, kb = 0.0593;
+        const double kg = 1.0 - kr - kb, top = double((1 << depth) - 1);
+        const double ys = full ? 1.0 : top / double(219 << (depth - 8)), cs = full ? 1.0 : top / double(224 << (depth - 8));
+        auto fx = [](double v) { return (int32_t)(v * 65536.0 + 0.5); };
+        c.yoff = full ? 0 : 16 << (depth - 8);
+        c.ys = fx(ys);
+        c.cr_r = fx(2.0 * (1.0 - kr) * cs);
+        c.cb_b = fx(2.0 * (1.0 - kb) * cs);
+        c.cb_g = fx(2.0 * kb * (1.0 - kb) / kg * cs);
+        c.cr_g = fx(2.0 * kr * (1.0 - kr) / kg * cs);
+    }
+    d.yoff = c.yoff;
+    d.ys = c.ys;
+    d.cr_r = c.cr_r;
+    d.cb_g = c.cb_g;
+    d.cr_g = c.cr_g;
+    d.cb_b = c.cb_b;
+    d.cmid = 1 << (depth - 1);
+    d.maxv = (1 << depth) - 1;
+}
+
 // parse modes (BatchArgs::parse_mode; heifgpu_batch_opts::parse_mode)
 // (4 was r05's row waves, HEIFGPU_PARSE_ROWS: removed in ABI 6, prepare answers HEIFGPU_E_UNSUPPORTED)
 enum : int { PARSE_AUTO = 0, PARSE_LANES = 1, PARSE_SOLO = 2, PARSE_SPREAD = 3 };
@@ -179,6 +230,9 @@ void emu_sao_out(const BatchArgs &a);
 hipError_t launch_rbsp(const BatchArgs &a, hipStream_t s);
 hipError_t launch_ycbcr_rgb(const ColorArgs &c, int bytes_per_sample, hipStream_t s);
 hipError_t launch_gather_tiles(const GatherArgs &g, hipStream_t s);
+// one launch over (max_tiles, n_images); descs on the device
+hipError_t launch_render(const RenderDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                         hipStream_t s);
 hipError_t launch_parse(const BatchArgs &a, hipStream_t s);
 hipError_t launch_transform(const BatchArgs &a, hipStream_t s);
 hipError_t launch_intra(const BatchArgs &a, hipStream_t s);

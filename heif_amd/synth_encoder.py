@@ -323,6 +323,74 @@ def single_heic(p: SynthParams, seed: int = 0, layout: Optional[BoxLayout] = Non
     return _assemble(items, 1, props, [(1, [1, 2])], b"", b"", layout)
 
 
+# ---- display properties (ISO/IEC 14496-12 clap; ISO/IEC 23008-12 irot, imir, auxC)
+ALPHA_URN_HEVC = "urn:mpeg:hevc:2015:auxid:1"
+ALPHA_URN_MPEGB = "urn:mpeg:mpegB:cicp:systems:auxiliary:alpha"
+
+
+def clap_box(width_n: int, width_d: int, height_n: int, height_d: int, horiz_off_n: int, horiz_off_d: int,
+             vert_off_n: int, vert_off_d: int) -> bytes:
+    """CleanApertureBox: eight 32-bit fields (values are written modulo 2^32, so a
+    negative offset numerator, or a deliberately negative denominator, fits)."""
+    return _box(b"clap", b"".join(_be(v, 4) for v in (width_n, width_d, height_n, height_d, horiz_off_n, horiz_off_d,
+                                                       vert_off_n, vert_off_d)))
+
+
+def irot_box(quarter_turns: int) -> bytes:
+    return _box(b"irot", bytes([quarter_turns & 3]))
+
+
+def imir_box(axis: int) -> bytes:
+    return _box(b"imir", bytes([axis & 1]))
+
+
+def nclx_box(primaries: int, transfer: int, matrix: int, full_range: bool) -> bytes:
+    return _box(b"colr", b"nclx" + struct.pack(">HHHB", primaries, transfer, matrix, 0x80 if full_range else 0))
+
+
+def auxc_box(urn: str) -> bytes:
+    return _fbox(b"auxC", 0, 0, urn.encode() + b"\0")
+
+
+@dataclasses.dataclass
+class AuxImage:
+    """An auxiliary image item of display_heic: its picture, the aux_type URN of
+    its auxC, and whether the primary points at it with a 'prem' reference."""
+    params: SynthParams
+    seed: int = 1
+    urn: str = ALPHA_URN_HEVC
+    premultiplied: bool = False
+
+
+def display_heic(p: SynthParams, seed: int = 0, transforms: Tuple[bytes, ...] = (), aux: Tuple[AuxImage, ...] = (),
+                 colr: Optional[bytes] = None, layout: Optional[BoxLayout] = None) -> bytes:
+    """single_heic plus what a viewer needs: `transforms` (property boxes from
+    clap_box / irot_box / imir_box, or raw bytes) are associated with the
+    primary after hvcC and ispe in the order given, which is the order a reader
+    applies them in; `colr` (nclx_box) goes in front of them.  Every `aux`
+    entry becomes an item of its own with hvcC, ispe and auxC, an 'auxl'
+    reference to the primary and, when premultiplied, a 'prem' reference from
+    the primary."""
+    props = [hvcc(p, *parameter_sets(p)), _ispe(p.width - p.conf_right, p.height - p.conf_bottom)]
+    primary_idx = [1, 2]
+    for box in ([colr] if colr else []) + list(transforms):
+        props.append(box)
+        primary_idx.append(len(props))
+    items = [(1, b"hvc1", picture_item(p, seed))]
+    assoc = [(1, primary_idx)]
+    refs = b""
+    for k, a in enumerate(aux):
+        iid = 2 + k
+        q = a.params
+        props += [hvcc(q, *parameter_sets(q)), _ispe(q.width - q.conf_right, q.height - q.conf_bottom), auxc_box(a.urn)]
+        assoc.append((iid, [len(props) - 2, len(props) - 1, len(props)]))
+        items.append((iid, b"hvc1", picture_item(q, a.seed)))
+        refs += _box(b"auxl", struct.pack(">HHH", iid, 1, 1))
+        if a.premultiplied:
+            refs += _box(b"prem", struct.pack(">HHH", 1, 1, iid))
+    return _assemble(items, 1, props, assoc, _fbox(b"iref", 0, 0, refs) if refs else b"", b"", layout)
+
+
 # BASELINE config 5: 8K 10-bit Main-10 grid, 15 x 9 tiles of 512x512
 CONFIG5 = dict(out_w=7680, out_h=4320, params=SynthParams(bit_depth=10))
 # Control workload of config-4 geometry whose 48 grid tiles are all distinct

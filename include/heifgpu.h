@@ -239,6 +239,67 @@ int heifgpu_ipc_close(void *dev_ptr);
 int heifgpu_ycbcr_to_rgb(heifgpu_ctx *ctx, const heifgpu_image_info *info, const heifgpu_planes *in, void *rgb,
                          int32_t rgb_pitch, void *stream);
 
+/* ---- display-ready output: clap / irot / imir, alpha, 8 or 16 bits, batched --
+ * (added within ABI 6: new entry points only.)
+ * heifgpu_image_get_display (host only, no device) reports how the decoded
+ * image is shown.  The item's transformative properties are applied in the
+ * order its 'ipma' entry lists them (ISO/IEC 23008-12 6.5; several of a kind
+ * are legal) and folded into one map: output pixel (ox, oy) shows decoded sample
+ *     src_x = m[0]*ox + m[1]*oy + t[0],   src_y = m[2]*ox + m[3]*oy + t[1],
+ * m one of the eight signed permutation matrices.  'clap' is the crop
+ * img[top:top+ch, left:left+cw] with cw = round_half_up(widthN/widthD),
+ * left = round_half_up(horizOffN/horizOffD + (W - cw)/2) (same for ch, top; W x H
+ * the image at that point of the chain; exact integer arithmetic); a zero or
+ * negative denominator, an empty rectangle or one not inside W x H fails the
+ * parse (HEIFGPU_E_PARSE).  'irot' turns anticlockwise by 90 degrees per unit.
+ * 'imir' axis 0 mirrors about a vertical axis (left and right swap), axis 1
+ * about a horizontal one.  alpha_item_id is the first 'auxl' image of the item
+ * whose 'auxC' type is urn:mpeg:hevc:2015:auxid:1 or
+ * urn:mpeg:mpegB:cicp:systems:auxiliary:alpha (a gain map or depth map is not
+ * alpha; heifgpu_image_info.aux_item_id still is the first 'auxl' of any
+ * type); alpha_premultiplied reports a 'prem' reference, nothing is
+ * un-premultiplied. */
+typedef struct {
+    uint32_t out_width, out_height;   /* displayed size */
+    int32_t  m[4], t[2];              /* output -> source map, above */
+    uint32_t n_transforms;            /* clap / irot / imir boxes folded in */
+    uint32_t alpha_item_id;           /* 0: none */
+    uint32_t alpha_premultiplied;
+} heifgpu_display_info;
+int heifgpu_image_get_display(const heifgpu_image *img, heifgpu_display_info *out);
+
+enum { HEIFGPU_PIX_RGB8 = 0, HEIFGPU_PIX_RGBA8 = 1, HEIFGPU_PIX_RGB16 = 2, HEIFGPU_PIX_RGBA16 = 3 };
+typedef struct { void *pixels; int32_t pitch; } heifgpu_surface;   /* device, caller-owned, bytes per row */
+/* Renders n decoded images (in[i]: planes as written by heifgpu_batch_decode
+ * for imgs[i]) into out[i] as interleaved R,G,B(,A) through each image's display
+ * map, with ONE kernel launch whatever n and the sizes are.  The images may
+ * differ in size, orientation, chroma format and matrix; their samples (and
+ * those of the alpha images) must all be 1 byte or all 2 bytes wide, and n is
+ * at most 65535.  Asynchronous on `stream`; calls issued back to back each keep
+ * their own descriptors (a ring of staging slots; a call waits on the host
+ * only for the call four before it).
+ * 8-bit formats: exactly heifgpu_ycbcr_to_rgb's arithmetic (samples shifted
+ * down to 8 bits), so HEIFGPU_PIX_RGB8 of an image whose only transform is
+ * 'irot' is byte-identical to it.  16-bit formats: native-endian uint16 at the
+ * image's own bit depth B (8..12), computed at that depth: luma offset
+ * 16 << (B-8) (limited range) or 0, chroma centre 1 << (B-1), limited-range
+ * scales ((1<<B)-1) / (219<<(B-8)) and ((1<<B)-1) / (224<<(B-8)) rounded to
+ * 16.16 the same way, clip to (1<<B)-1; pixels and pitch must be even.
+ * Alpha (RGBA formats): alpha_imgs NULL or alpha_imgs[i] NULL stores the
+ * maximum (255, or (1<<B)-1).  Otherwise alpha_in[i].plane[0] is the decoded
+ * luma of alpha_imgs[i] (bit depth Ba, full range), addressed through the
+ * colour image's map: 8-bit formats store a >> (Ba-8); 16-bit formats store a
+ * shifted to depth B (a << (B-Ba) or a >> (Ba-B): exact only when Ba == B).
+ * An alpha image whose decoded size differs from its colour image's is
+ * HEIFGPU_E_UNSUPPORTED, reported before anything is launched.  The RGB
+ * formats ignore the alpha arguments.  4:0:0 gives R = G = B.  A pitch below
+ * the row size is HEIFGPU_E_INVALID. */
+int heifgpu_render_batch(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                         const heifgpu_planes *in,
+                         const heifgpu_image *const *alpha_imgs,
+                         const heifgpu_planes *alpha_in,
+                         uint32_t format, const heifgpu_surface *out, void *stream);
+
 /* ---- host test hooks (reference unit-test surface) -------------------- */
 size_t heifgpu_remove_emulation_prevention(const uint8_t *in, size_t n, uint8_t *out); /* rbsp_reader.rs:11-39 */
 int heifgpu_read_ue(const uint8_t *buf, size_t n, uint32_t *val);                      /* rbsp_reader.rs:87-99 */
