@@ -306,6 +306,17 @@ class DecodeContext:
             surf[i].pixels = t.data_ptr()
             surf[i].pitch = t.stride(0) * t.element_size()
             res.append(t)
+        imgs, aimgs, aplanes = self._render_args(outs, alphas)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(lib.heifgpu_render_batch(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f, surf,
+                                            ctypes.c_void_p(stream)))
+        return res
+
+    @staticmethod
+    def _render_args(outs, alphas):
+        """The image handles and the alpha arguments of a render call."""
+        n = len(outs)
         imgs = (ctypes.c_void_p * max(n, 1))(*[o.image._h.value for o in outs])
         aimgs = aplanes = None
         if alphas is not None:
@@ -315,11 +326,63 @@ class DecodeContext:
                 if a is not None:
                     aplanes[i].plane[0] = a.y.data_ptr()
                     aplanes[i].pitch[0] = a.y.stride(0) * a.y.element_size()
+        return imgs, aimgs, aplanes
+
+    def render_scaled(self, outs: Sequence[DecodedImage], size, mode: str = "cover", fmt: str = "rgb8",
+                      alphas: Optional[Sequence[Optional[DecodedImage]]] = None, windows=None,
+                      stream: Optional[int] = None):
+        """render() onto a smaller grid: the exact area average of a window of
+        every displayed picture, with ONE heifgpu_render_batch_scaled call (one
+        kernel launch).  size = (h, w) is the box; mode "cover" (a centred
+        window of the box's aspect fills it), "stretch" (the whole picture
+        fills it) or "contain" (the whole picture, its aspect kept, fits in
+        it), through heifgpu_scale_fit.  windows[i] = (x, y, w, h) in displayed
+        coordinates replaces the mode's window; the output is then `size`
+        exactly.  Returns ONE (N, h, w, C) device tensor when every output has
+        the same size (cover, stretch, windows), whose slices are the surfaces,
+        and a list of (h_i, w_i, C) tensors for "contain".  Dtypes, fmt and
+        alphas as in render()."""
+        torch = self._torch
+        n = len(outs)
+        f = _lib.PIX_FORMATS[fmt]
+        ch, wide = (4 if f & 1 else 3), f >= _lib.PIX_RGB16
+        if mode not in _lib.FIT_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(_lib.FIT_MODES)}")
+        if any(o.image is None for o in outs) or (alphas is not None and any(a is not None and a.image is None for a in alphas)):
+            raise ValueError("render_scaled needs images that carry their HeifImage (alloc_outputs)")
+        if alphas is not None and len(alphas) != n:
+            raise ValueError("alphas must have one entry per image")
+        if windows is not None and len(windows) != n:
+            raise ValueError("windows must have one entry per image")
+        bh, bw = int(size[0]), int(size[1])
+        scales = (_lib.Scale * max(n, 1))()
+        for i, o in enumerate(outs):
+            if windows is not None:
+                x, y, w, h = (int(v) for v in windows[i])
+                scales[i] = _lib.Scale(bw, bh, x, y, w, h)
+            else:
+                d = o.image.display
+                _lib.check(lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_MODES[mode], ctypes.byref(scales[i])))
+        dev = torch.device("cuda", self.device)
+        dt = torch.int16 if wide else torch.uint8
+        if windows is not None or mode != "contain":
+            whole = torch.empty((n, bh, bw, ch), dtype=dt, device=dev)
+            res = [whole[i] for i in range(n)]
+        else:
+            whole = None
+            res = [torch.empty((scales[i].out_height, scales[i].out_width, ch), dtype=dt, device=dev) for i in range(n)]
+        if n == 0:
+            return whole if whole is not None else res
+        surf = (_lib.Surface * n)()
+        for i, t in enumerate(res):
+            surf[i].pixels = t.data_ptr()
+            surf[i].pitch = t.stride(0) * t.element_size()
+        imgs, aimgs, aplanes = self._render_args(outs, alphas)
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(lib.heifgpu_render_batch(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f, surf,
-                                            ctypes.c_void_p(stream)))
-        return res
+        _lib.check(lib.heifgpu_render_batch_scaled(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f,
+                                                   scales, surf, ctypes.c_void_p(stream)))
+        return whole if whole is not None else res
 
 
 def ipc_export(tensor) -> bytes:
@@ -434,18 +497,24 @@ class HeicDecoder:
         return cls.context(device).to_rgb(cls.decode(data, device, item_id))
 
     @classmethod
-    def decode_display(cls, data: bytes, fmt: Optional[str] = None, device: int = 0):
+    def decode_display(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, size=None,
+                       mode: str = "contain"):
         """The picture a viewer shows: decodes the primary image and, when it
         has one (display.alpha_item_id), its alpha plane, then renders
         (DecodeContext.render) with clap / irot / imir applied.  fmt None picks
-        RGBA when there is alpha and 16 bits when the bit depth is above 8."""
+        RGBA when there is alpha and 16 bits when the bit depth is above 8.
+        size = (h, w) renders it into that box instead (DecodeContext.render_scaled
+        with `mode`); None is the full size."""
         ctx = cls.context(device)
         out = cls.decode(data, device)
         aid = out.image.display.alpha_item_id
         alpha = cls.decode(data, device, aid) if aid else None
         if fmt is None:
             fmt = ("rgba" if alpha is not None else "rgb") + ("16" if out.info.bit_depth > 8 else "8")
-        return ctx.render([out], fmt, [alpha] if alpha is not None else None)[0]
+        alphas = [alpha] if alpha is not None else None
+        if size is not None:
+            return ctx.render_scaled([out], size, mode, fmt, alphas)[0]
+        return ctx.render([out], fmt, alphas)[0]
 
     @classmethod
     def decode(cls, data: bytes, device: int = 0, item_id: int = 0) -> DecodedImage:

@@ -136,6 +136,17 @@ class Surface(ctypes.Structure):
     _fields_ = [("pixels", ctypes.c_void_p), ("pitch", ctypes.c_int32)]
 
 
+class Scale(ctypes.Structure):
+    """heifgpu_scale: rendered size and the window of the displayed picture it
+    shows (width == height == 0: the whole picture)."""
+    _fields_ = [("out_width", ctypes.c_uint32), ("out_height", ctypes.c_uint32),
+                ("x", ctypes.c_uint32), ("y", ctypes.c_uint32),
+                ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
+
+
+FIT_STRETCH, FIT_CONTAIN, FIT_COVER = 0, 1, 2
+FIT_MODES = {"stretch": FIT_STRETCH, "contain": FIT_CONTAIN, "cover": FIT_COVER}
+
 PIX_RGB8, PIX_RGBA8, PIX_RGB16, PIX_RGBA16 = 0, 1, 2, 3
 PIX_FORMATS = {"rgb8": PIX_RGB8, "rgba8": PIX_RGBA8, "rgb16": PIX_RGB16, "rgba16": PIX_RGBA16}
 
@@ -156,7 +167,7 @@ EXPORTS = (
     "heifgpu_image_parse_item", "heifgpu_ycbcr_to_rgb", "heifgpu_batch_prepare_ex", "heifgpu_gather_tiles",
     "heifgpu_image_parse_many", "heifgpu_batch_parse_geometry", "heifgpu_ipc_export", "heifgpu_ipc_open",
     "heifgpu_ipc_close", "heifgpu_batch_status_previous", "heifgpu_abi_version", "heifgpu_batch_lanes_variant",
-    "heifgpu_image_get_display", "heifgpu_render_batch",
+    "heifgpu_image_get_display", "heifgpu_render_batch", "heifgpu_scale_fit", "heifgpu_render_batch_scaled",
 )
 
 
@@ -230,6 +241,9 @@ def _load() -> ctypes.CDLL:
         "heifgpu_batch_lanes_variant": (I32, [VP, P(U32)]),
         "heifgpu_image_get_display": (I32, [VP, P(DisplayInfo)]),
         "heifgpu_render_batch": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), U32, P(Surface), VP]),
+        "heifgpu_scale_fit": (I32, [P(DisplayInfo), U32, U32, U32, P(Scale)]),
+        "heifgpu_render_batch_scaled": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), U32, P(Scale), P(Surface),
+                                              VP]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     optional = {"heifgpu_batch_lanes_variant"}

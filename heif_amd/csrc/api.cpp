@@ -186,7 +186,7 @@ struct PinnedBuf {
 
 }  // namespace
 
-// heifgpu_render_batch's descriptors travel through a ring of slots, each a
+// heifgpu_render_batch's (and heifgpu_render_batch_scaled's) descriptors travel through a ring of slots, each a
 // pinned host image, a device array and an event recorded behind the kernel
 // that reads them: a call never rewrites descriptors that an earlier call's
 // copy or kernel may still read (the host waits only when the ring wraps).
@@ -195,6 +195,7 @@ struct RenderRing {
     struct Slot {
         PinnedBuf host;
         DevBuf<RenderDesc> dev;
+        DevBuf<ScaleDesc> sdev;  // heifgpu_render_batch_scaled's
         hipEvent_t done = nullptr;
         bool pending = false;
     } slot[kRenderSlots];
@@ -519,76 +520,70 @@ int heifgpu_image_get_display(const heifgpu_image *img, heifgpu_display_info *ou
     return HEIFGPU_OK;
 }
 
-int heifgpu_render_batch(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
-                         const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
-                         const heifgpu_surface *out, void *stream) {
-    if (!ctx || !imgs || !in || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
-    if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
-    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+// What heifgpu_render_batch and heifgpu_render_batch_scaled check and fill alike for
+// image i: dm is the map the kernel reads through (for the scaled call the window is
+// folded in; dm.out_width x out_height is then the window), ow x oh the size written.
+static int render_desc_fill(size_t i, const heifgpu_image *const *imgs, const heifgpu_planes *in,
+                            const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                            const heifgpu_surface *out, const DisplayMap &dm, uint32_t ow, uint32_t oh, int &bps,
+                            RenderDesc &d) {
     const bool wide = format >= HEIFGPU_PIX_RGB16, with_alpha = (format & 1) != 0;
     const int bpp = (with_alpha ? 4 : 3) * (wide ? 2 : 1);
-    std::vector<RenderDesc> descs(n);
-    int bps = 0, max_tiles = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
-        heifgpu_image_info info;
-        heifgpu_image_get_info(imgs[i], &info);
-        const DisplayMap &dm = imgs[i]->img.display;
-        if (!in[i].plane[0] || !out[i].pixels) return fail(HEIFGPU_E_INVALID, "missing plane or surface");
-        if (info.chroma_format_idc && (!in[i].plane[1] || !in[i].plane[2]))
-            return fail(HEIFGPU_E_INVALID, "missing chroma plane");
-        if (info.bit_depth < 8 || info.bit_depth > (wide ? 12u : 16u)) return fail(HEIFGPU_E_INVALID, "bit depth");
-        if (bps && bps != int(info.bytes_per_sample))
-            return fail(HEIFGPU_E_UNSUPPORTED, "images of 1-byte and 2-byte samples in one render call");
-        bps = int(info.bytes_per_sample);
-        if (int64_t(out[i].pitch) < int64_t(bpp) * dm.out_width)
-            return fail(HEIFGPU_E_INVALID, "surface pitch smaller than the output row");
-        if (wide && ((reinterpret_cast<uintptr_t>(out[i].pixels) | uint32_t(out[i].pitch)) & 1))
-            return fail(HEIFGPU_E_INVALID, "16-bit surface not 2-byte aligned");
-        // the map's corners inside the decoded planes (parse_heic built it so; the kernel reads unchecked)
-        for (int c = 0; c < 4; ++c) {
-            const int64_t ox = (c & 1) ? int64_t(dm.out_width) - 1 : 0, oy = (c & 2) ? int64_t(dm.out_height) - 1 : 0;
-            const int64_t x = dm.m[0] * ox + dm.m[1] * oy + dm.t[0], y = dm.m[2] * ox + dm.m[3] * oy + dm.t[1];
-            if (x < 0 || y < 0 || x >= int64_t(info.width) || y >= int64_t(info.height))
-                return fail(HEIFGPU_E_INVALID, "display map outside the decoded image");
-        }
-        RenderDesc &d = descs[i];
-        d = RenderDesc{};
-        for (int k = 0; k < 3; ++k) {
-            d.plane[k] = reinterpret_cast<uint64_t>(in[i].plane[k]);
-            d.pitch[k] = in[i].pitch[k];
-        }
-        d.out = reinterpret_cast<uint64_t>(out[i].pixels);
-        d.out_pitch = out[i].pitch;
-        d.out_w = int32_t(dm.out_width);
-        d.out_h = int32_t(dm.out_height);
-        for (int k = 0; k < 4; ++k) d.m[k] = dm.m[k];
-        d.t[0] = dm.t[0];
-        d.t[1] = dm.t[1];
-        d.swap = dm.m[0] == 0;
-        const int tw = d.swap ? kRenderTile : kRenderRowW, th = d.swap ? kRenderTile : kRenderRowH;
-        d.tiles_x = (d.out_w + tw - 1) / tw;
-        d.tiles = d.tiles_x * ((d.out_h + th - 1) / th);
-        max_tiles = std::max(max_tiles, d.tiles);
-        d.chroma = int32_t(info.chroma_format_idc);
-        const int depth = wide ? int(info.bit_depth) : 8;  // the depth the arithmetic runs at
-        d.shift = int32_t(info.bit_depth) - depth;
-        render_coefs(info.matrix_coeffs, info.full_range != 0, depth, d);
-        if (with_alpha && alpha_imgs && alpha_imgs[i]) {
-            if (!alpha_in || !alpha_in[i].plane[0]) return fail(HEIFGPU_E_INVALID, "missing alpha plane");
-            heifgpu_image_info ai;
-            heifgpu_image_get_info(alpha_imgs[i], &ai);
-            if (ai.width != info.width || ai.height != info.height)
-                return fail(HEIFGPU_E_UNSUPPORTED, "alpha image of another size than its colour image");
-            if (int(ai.bytes_per_sample) != bps)
-                return fail(HEIFGPU_E_UNSUPPORTED, "images of 1-byte and 2-byte samples in one render call");
-            d.alpha = reinterpret_cast<uint64_t>(alpha_in[i].plane[0]);
-            d.alpha_pitch = alpha_in[i].pitch[0];
-            d.alpha_bps = int32_t(ai.bytes_per_sample);
-            d.alpha_shift = int32_t(ai.bit_depth) - depth;  // right when positive, left when negative
-        }
+    heifgpu_image_info info;
+    heifgpu_image_get_info(imgs[i], &info);
+    if (!in[i].plane[0] || !out[i].pixels) return fail(HEIFGPU_E_INVALID, "missing plane or surface");
+    if (info.chroma_format_idc && (!in[i].plane[1] || !in[i].plane[2]))
+        return fail(HEIFGPU_E_INVALID, "missing chroma plane");
+    if (info.bit_depth < 8 || info.bit_depth > (wide ? 12u : 16u)) return fail(HEIFGPU_E_INVALID, "bit depth");
+    if (bps && bps != int(info.bytes_per_sample))
+        return fail(HEIFGPU_E_UNSUPPORTED, "images of 1-byte and 2-byte samples in one render call");
+    bps = int(info.bytes_per_sample);
+    if (int64_t(out[i].pitch) < int64_t(bpp) * ow)
+        return fail(HEIFGPU_E_INVALID, "surface pitch smaller than the output row");
+    if (wide && ((reinterpret_cast<uintptr_t>(out[i].pixels) | uint32_t(out[i].pitch)) & 1))
+        return fail(HEIFGPU_E_INVALID, "16-bit surface not 2-byte aligned");
+    // the map's corners inside the decoded planes (parse_heic built it so; the kernel reads unchecked)
+    for (int c = 0; c < 4; ++c) {
+        const int64_t ox = (c & 1) ? int64_t(dm.out_width) - 1 : 0, oy = (c & 2) ? int64_t(dm.out_height) - 1 : 0;
+        const int64_t x = dm.m[0] * ox + dm.m[1] * oy + dm.t[0], y = dm.m[2] * ox + dm.m[3] * oy + dm.t[1];
+        if (x < 0 || y < 0 || x >= int64_t(info.width) || y >= int64_t(info.height))
+            return fail(HEIFGPU_E_INVALID, "display map outside the decoded image");
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    d = RenderDesc{};
+    for (int k = 0; k < 3; ++k) {
+        d.plane[k] = reinterpret_cast<uint64_t>(in[i].plane[k]);
+        d.pitch[k] = in[i].pitch[k];
+    }
+    d.out = reinterpret_cast<uint64_t>(out[i].pixels);
+    d.out_pitch = out[i].pitch;
+    d.out_w = int32_t(ow);
+    d.out_h = int32_t(oh);
+    for (int k = 0; k < 4; ++k) d.m[k] = dm.m[k];
+    d.t[0] = dm.t[0];
+    d.t[1] = dm.t[1];
+    d.swap = dm.m[0] == 0;
+    d.chroma = int32_t(info.chroma_format_idc);
+    const int depth = wide ? int(info.bit_depth) : 8;  // the depth the arithmetic runs at
+    d.shift = int32_t(info.bit_depth) - depth;
+    render_coefs(info.matrix_coeffs, info.full_range != 0, depth, d);
+    if (with_alpha && alpha_imgs && alpha_imgs[i]) {
+        if (!alpha_in || !alpha_in[i].plane[0]) return fail(HEIFGPU_E_INVALID, "missing alpha plane");
+        heifgpu_image_info ai;
+        heifgpu_image_get_info(alpha_imgs[i], &ai);
+        if (ai.width != info.width || ai.height != info.height)
+            return fail(HEIFGPU_E_UNSUPPORTED, "alpha image of another size than its colour image");
+        if (int(ai.bytes_per_sample) != bps)
+            return fail(HEIFGPU_E_UNSUPPORTED, "images of 1-byte and 2-byte samples in one render call");
+        d.alpha = reinterpret_cast<uint64_t>(alpha_in[i].plane[0]);
+        d.alpha_pitch = alpha_in[i].pitch[0];
+        d.alpha_bps = int32_t(ai.bytes_per_sample);
+        d.alpha_shift = int32_t(ai.bit_depth) - depth;  // right when positive, left when negative
+    }
+    return HEIFGPU_OK;
+}
+
+// The next slot of the context's descriptor ring, drained of the call that used it last.
+static int render_ring_slot(heifgpu_ctx *ctx, RenderRing::Slot **out) {
     HIP_TRY(hipSetDevice(ctx->device));
     if (!ctx->render) {
         auto ring = std::make_unique<RenderRing>();
@@ -599,12 +594,140 @@ int heifgpu_render_batch(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, siz
     ctx->render->next = (ctx->render->next + 1) % kRenderSlots;
     if (sl.pending) HIP_TRY(hipEventSynchronize(sl.done));  // the call that used this slot last
     sl.pending = false;
+    *out = &sl;
+    return HEIFGPU_OK;
+}
+
+int heifgpu_render_batch(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                         const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                         const heifgpu_surface *out, void *stream) {
+    if (!ctx || !imgs || !in || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    std::vector<RenderDesc> descs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
+        const DisplayMap &dm = imgs[i]->img.display;
+        RenderDesc &d = descs[i];
+        if (int rc = render_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, out, dm, dm.out_width, dm.out_height,
+                                      bps, d))
+            return rc;
+        const int tw = d.swap ? kRenderTile : kRenderRowW, th = d.swap ? kRenderTile : kRenderRowH;
+        d.tiles_x = (d.out_w + tw - 1) / tw;
+        d.tiles = d.tiles_x * ((d.out_h + th - 1) / th);
+        max_tiles = std::max(max_tiles, d.tiles);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RenderRing::Slot *slot = nullptr;
+    if (int rc = render_ring_slot(ctx, &slot)) return rc;
+    RenderRing::Slot &sl = *slot;
     const size_t bytes = n * sizeof(RenderDesc);
     HIP_TRY(sl.host.reserve(bytes));
     HIP_TRY(sl.dev.alloc(n));
     std::memcpy(sl.host.p, descs.data(), bytes);
     HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(launch_render(sl.dev.p, int(n), max_tiles, int(format), bps, s));  // the one launch
+    HIP_TRY(hipEventRecord(sl.done, s));
+    sl.pending = true;
+    return HEIFGPU_OK;
+}
+
+// round_half_up(n / d) = floor((2n + d) / 2d); n, d < 2^32
+static uint64_t round_div(uint64_t n, uint64_t d) { return (2 * n + d) / (2 * d); }
+
+int heifgpu_scale_fit(const heifgpu_display_info *d, uint32_t box_w, uint32_t box_h, uint32_t mode, heifgpu_scale *out) {
+    if (!d || !out) return fail(HEIFGPU_E_INVALID, "null argument");
+    if (!box_w || !box_h) return fail(HEIFGPU_E_INVALID, "empty box");
+    if (mode > HEIFGPU_FIT_COVER) return fail(HEIFGPU_E_INVALID, "fit mode");
+    if (!d->out_width || !d->out_height) return fail(HEIFGPU_E_INVALID, "empty picture");
+    const uint64_t dw = d->out_width, dh = d->out_height, bw = box_w, bh = box_h;
+    heifgpu_scale s{};
+    s.out_width = box_w;
+    s.out_height = box_h;  // STRETCH; x = y = width = height = 0: the whole picture
+    const bool wider = dw * bh >= dh * bw;  // the picture is at least as wide as the box, relatively
+    if (mode == HEIFGPU_FIT_CONTAIN) {
+        if (wider) s.out_height = uint32_t(std::max<uint64_t>(1, round_div(dh * bw, dw)));
+        else s.out_width = uint32_t(std::max<uint64_t>(1, round_div(dw * bh, dh)));
+    } else if (mode == HEIFGPU_FIT_COVER) {
+        s.width = d->out_width;
+        s.height = d->out_height;
+        if (wider) {
+            s.width = uint32_t(std::max<uint64_t>(1, round_div(dh * bw, bh)));
+            s.x = (d->out_width - s.width) / 2;
+        } else {
+            s.height = uint32_t(std::max<uint64_t>(1, round_div(dw * bh, bw)));
+            s.y = (d->out_height - s.height) / 2;
+        }
+    }
+    *out = s;
+    return HEIFGPU_OK;
+}
+
+int heifgpu_render_batch_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                                const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                                const heifgpu_scale *scale, const heifgpu_surface *out, void *stream) {
+    // (the context is looked at last: every check of the arguments answers without one)
+    if (!imgs || !in || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    std::vector<ScaleDesc> descs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
+        DisplayMap dm = imgs[i]->img.display;
+        const heifgpu_scale &sc = scale[i];
+        if (!sc.out_width || !sc.out_height || sc.out_width > 65535 || sc.out_height > 65535)
+            return fail(HEIFGPU_E_INVALID, "rendered size outside 1..65535");
+        if (sc.width || sc.height) {
+            if (!sc.width || !sc.height || sc.x >= dm.out_width || sc.y >= dm.out_height ||
+                sc.width > dm.out_width - sc.x || sc.height > dm.out_height - sc.y)
+                return fail(HEIFGPU_E_INVALID, "window empty or outside the displayed picture");
+            display_window(dm, sc.x, sc.y, sc.width, sc.height);
+        }
+        if (dm.out_width > 65535 || dm.out_height > 65535)
+            return fail(HEIFGPU_E_UNSUPPORTED, "window side above 65535");  // (the 32-bit line sums of the kernel)
+        ScaleDesc &sd = descs[i];
+        sd = ScaleDesc{};
+        RenderDesc &d = sd.r;
+        if (int rc = render_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, out, dm, sc.out_width, sc.out_height,
+                                      bps, d))
+            return rc;
+        // the source's axes: a runs along its y, b along its x (kernels.hpp)
+        const int32_t cw = int32_t(dm.out_width), ch = int32_t(dm.out_height);
+        if (d.swap) {
+            sd.ca = cw, sd.oa = d.out_w, sd.ma = d.m[2], sd.ta = d.t[1];
+            sd.cb = ch, sd.ob = d.out_h, sd.mb = d.m[1], sd.tb = d.t[0];
+            // 64 pixels along the output's x (store_row); along its y as many as keep the footprint
+            // within a chunk of kScaleCols source columns, 16 at the least
+            sd.na = kScaleTile, sd.nb = kScaleTile;
+            while (sd.nb > 16 && int64_t(sd.nb) * sd.cb > int64_t(kScaleCols) * sd.ob) sd.nb /= 2;
+        } else {
+            sd.ca = ch, sd.oa = d.out_h, sd.ma = d.m[3], sd.ta = d.t[1];
+            sd.cb = cw, sd.ob = d.out_w, sd.mb = d.m[0], sd.tb = d.t[0];
+            // as many columns as fill a chunk of kScaleCols source columns, 64 at ratios from 4 up
+            sd.na = kScaleRowsA;
+            sd.nb = 64;
+            while (sd.nb < 256 && int64_t(2 * sd.nb) * sd.cb <= int64_t(kScaleCols) * sd.ob) sd.nb *= 2;
+        }
+        for (sd.nb_log2 = 4; (1 << sd.nb_log2) < sd.nb;) ++sd.nb_log2;
+        sd.den = 2 * uint64_t(cw) * uint64_t(ch);
+        sd.inv_den = 1.0 / double(sd.den);
+        d.tiles_x = (sd.ob + sd.nb - 1) / sd.nb;
+        d.tiles = d.tiles_x * ((sd.oa + sd.na - 1) / sd.na);
+        max_tiles = std::max(max_tiles, d.tiles);
+    }
+    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RenderRing::Slot *slot = nullptr;
+    if (int rc = render_ring_slot(ctx, &slot)) return rc;
+    RenderRing::Slot &sl = *slot;
+    const size_t bytes = n * sizeof(ScaleDesc);
+    HIP_TRY(sl.host.reserve(bytes));
+    HIP_TRY(sl.sdev.alloc(n));
+    std::memcpy(sl.host.p, descs.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(sl.sdev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_render_scaled(sl.sdev.p, int(n), max_tiles, int(format), bps, s));  // the one launch
     HIP_TRY(hipEventRecord(sl.done, s));
     sl.pending = true;
     return HEIFGPU_OK;

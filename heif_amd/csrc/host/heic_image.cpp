@@ -175,6 +175,11 @@ void display_imir(DisplayMap &d, uint32_t axis) {
     }
 }
 
+void display_window(DisplayMap &d, uint32_t x, uint32_t y, uint32_t w, uint32_t h) {
+    const int32_t a[4] = {1, 0, 0, 1}, b[2] = {int32_t(x), int32_t(y)};
+    display_step(d, a, b, w, h);
+}
+
 ParsedImage parse_heic(const uint8_t *data, size_t len, uint32_t item_id) {
     HeifReader reader(data, len);
     Heif heif = reader.read();

@@ -47,6 +47,9 @@ struct DisplayMap {
 void display_clap(DisplayMap &d, const uint8_t *payload, size_t len);  // throws HeifError
 void display_irot(DisplayMap &d, uint32_t quarter_turns);
 void display_imir(DisplayMap &d, uint32_t axis);
+// the window img[y:y+h, x:x+w] of the displayed picture as one more step, a clap given
+// directly (heifgpu_render_batch_scaled; the caller has checked that it lies inside)
+void display_window(DisplayMap &d, uint32_t x, uint32_t y, uint32_t w, uint32_t h);
 
 struct ParsedImage {
     // move-only: the tiles' payload views point into `coded`, whose buffer a move keeps

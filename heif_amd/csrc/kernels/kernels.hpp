@@ -158,6 +158,26 @@ inline void render_coefs(uint32_t matrix, bool full, int depth, RenderDesc &d) {
     d.maxv = (1 << depth) - 1;
 }
 
+// k_render_scaled (render.hip): one descriptor per image of a heifgpu_render_batch_scaled
+// call.  r is the image's RenderDesc with the window folded into m / t (window
+// pixel (i, j) shows decoded sample (m[0]*i + m[1]*j + t[0], m[2]*i + m[3]*j + t[1]))
+// and out_w x out_h the rendered size.  The kernel works in the source's axes:
+// axis "a" is the output axis the source's y runs along (the output's y unless
+// r.swap), axis "b" the one the source's x runs along.  Window index k of axis a
+// is source row ma * k + ta, of axis b source column mb * k + tb.
+constexpr int kScaleCols = 512;                   // source columns of one chunk: 2 per thread
+constexpr int kScaleRowsA = 8, kScaleTile = 64;   // a-lines per workgroup: 8 (axes kept), 64 (axes swapped)
+struct ScaleDesc {
+    RenderDesc r;
+    int32_t ca, cb;      // window size along a, b (1..65535)
+    int32_t oa, ob;      // rendered size along a, b (1..65535)
+    int32_t ma, ta, mb, tb;
+    int32_t na, nb, nb_log2;  // the workgroup's tile: na a-lines x nb b-lines (nb a power of two, 16..256)
+    int32_t pad;
+    uint64_t den;        // 2 * ca * cb
+    double inv_den;      // 1 / den (the quotient's estimate; corrected exactly)
+};
+
 // parse modes (BatchArgs::parse_mode; heifgpu_batch_opts::parse_mode)
 // (4 was r05's row waves, HEIFGPU_PARSE_ROWS: removed in ABI 6, prepare answers HEIFGPU_E_UNSUPPORTED)
 enum : int { PARSE_AUTO = 0, PARSE_LANES = 1, PARSE_SOLO = 2, PARSE_SPREAD = 3 };
@@ -233,6 +253,8 @@ hipError_t launch_gather_tiles(const GatherArgs &g, hipStream_t s);
 // one launch over (max_tiles, n_images); descs on the device
 hipError_t launch_render(const RenderDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
                          hipStream_t s);
+hipError_t launch_render_scaled(const ScaleDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                                hipStream_t s);
 hipError_t launch_parse(const BatchArgs &a, hipStream_t s);
 hipError_t launch_transform(const BatchArgs &a, hipStream_t s);
 hipError_t launch_intra(const BatchArgs &a, hipStream_t s);

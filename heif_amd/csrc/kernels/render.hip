@@ -27,6 +27,10 @@
 // one dword each (bytes when the row is not 4-byte aligned or the four are
 // incomplete).  RGB16 packs 2 pixels → 3 dwords the same way; RGBA stores its
 // own 4 or 8 bytes.
+//
+// k_render_scaled (heifgpu_render_batch_scaled), further down, writes the exact
+// area average of a window of the same picture onto another grid; it shares
+// convert()'s arithmetic and store_row.
 #include "kernels.hpp"
 
 namespace hg {
@@ -190,7 +194,266 @@ void launch_fmt(const RenderDesc *descs, dim3 grid, int format, hipStream_t s) {
     }
 }
 
+// ---- k_render_scaled: the same pictures, area-averaged onto a smaller (or any
+// other) grid in the same launch (heifgpu_render_batch_scaled) -----------------
+// R = round_half_up(sum_j sum_i wy(Y,j) wx(X,i) D[j][i] / (cw ch)) over the
+// converted pixels D of the window (include/heifgpu.h states the weights), all
+// in integers.  The sum is separable and is taken in the source's axes, so the
+// same code serves the eight orientations: axis a is the output axis the
+// source's y runs along, axis b the one its x runs along (ScaleDesc).
+//
+// A workgroup (256 threads) owns na x nb output pixels: 8 rows x 64 / 128 / 256
+// columns for maps that keep the axes, 64 columns x 16 / 32 / 64 rows for maps
+// that swap them (nb picked by the host so that the tile's footprint along b
+// comes close to one chunk below; store_row wants 64 pixels along the output's x).  For every a-line of its tile it walks the line's source footprint in
+// chunks of 512 source columns:
+//   1. lanes along the source's x, two adjacent columns (one 4:2:0 / 4:2:2
+//      chroma sample) per thread, mirrored or not: a thread walks its columns
+//      down the line's source rows, converts each sample with convert()'s
+//      arithmetic and adds weight_a * channel into 32-bit sums (at most
+//      65535 * 4095).  The loads of four rows are issued before the first is
+//      used; a chroma row is fetched once for the luma rows it serves.  The
+//      sums go to LDS, one plane of 512 dwords per channel.
+//   2. lanes along b, the channels spread over the waves: an output pixel adds
+//      weight_b * column sum over its columns of the chunk into a 64-bit sum
+//      kept across chunks (the whole sum reaches 4095 * cw * ch > 2^32).
+// Both footprints are walked by loops, so LDS (8 KiB of column sums, 16.25 or
+// 32.5 KiB of results) does not depend on the ratio.  The rounded quotient
+// comes from a double-precision estimate corrected exactly in integers.  The
+// tile's pixels wait in LDS, packed as Px, and leave through store_row with
+// lanes along the output's x (for swapped axes that read is the transpose,
+// pitch 65 dwords as in k_render).
+constexpr int kScaleRowGroup = 4;  // source rows whose loads are issued together
+
+// sample() through a global-address-space pointer (global_load, not flat_load: its
+// wait does not also count LDS traffic)
+template <typename T>
+__device__ __forceinline__ int sample_g(uint64_t plane, int32_t pitch, int x, int y) {
+    typedef const T __attribute__((address_space(1))) *gptr;
+    return (int)*(gptr)(plane + (size_t)y * (size_t)pitch + (size_t)x * sizeof(T));
+}
+
+struct ScaleChroma {
+    int cb[2], cr[2];  // as loaded, for a thread's two columns
+};
+
+// convert()'s arithmetic for the two columns of one source row (samples as loaded),
+// weighted into the column sums; every product has factors below 2^23
+template <int FMT>
+__device__ __forceinline__ void scale_acc(const RenderDesc &d, const int (&ys)[2], const ScaleChroma &cc,
+                                          const int (&al)[2], uint32_t w, uint32_t (&acc)[2][4]) {
+    int tr[2] = {0, 0}, tg[2] = {0, 0}, tb[2] = {0, 0};  // the chroma terms of R, G, B
+    if (d.chroma) {
+        const int n = chroma_sx(d.chroma) ? 1 : 2;  // a subsampled pair shares its sample: one set of products
+        for (int c = 0; c < n; ++c) {
+            const int cb = (cc.cb[c] >> d.shift) - d.cmid, cr = (cc.cr[c] >> d.shift) - d.cmid;
+            tr[c] = __mul24(d.cr_r, cr);
+            tg[c] = __mul24(d.cb_g, cb) + __mul24(d.cr_g, cr);
+            tb[c] = __mul24(d.cb_b, cb);
+        }
+        if (n == 1) tr[1] = tr[0], tg[1] = tg[0], tb[1] = tb[0];
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const int yv = __mul24(d.ys, (ys[c] >> d.shift) - d.yoff) + 32768;
+        const int R = min(max((yv + tr[c]) >> 16, 0), d.maxv);
+        const int G = min(max((yv - tg[c]) >> 16, 0), d.maxv);
+        const int B = min(max((yv + tb[c]) >> 16, 0), d.maxv);
+        acc[c][0] += __umul24(w, (uint32_t)R);
+        acc[c][1] += __umul24(w, (uint32_t)G);
+        acc[c][2] += __umul24(w, (uint32_t)B);
+        if (FMT & 1) {
+            int A = d.maxv;  // opaque
+            if (d.alpha) A = d.alpha_shift >= 0 ? al[c] >> d.alpha_shift : al[c] << -d.alpha_shift;
+            acc[c][3] += __umul24(w, (uint32_t)A);
+        }
+    }
+}
+
+// Stage 1 for one thread: its two source columns x0, x1 down the window rows [ka0, ka1)
+// of output line a, weighted.  The loads of kScaleRowGroup rows are issued before the
+// first of them is used (rows past the end load the last one again and are skipped); a chroma
+// row is loaded when the walk enters it and serves the luma rows that follow in it.
+template <typename Pel, int FMT>
+__device__ __forceinline__ void scale_columns(const ScaleDesc &s, int x0, int x1, int ka0, int ka1, uint32_t alo,
+                                              uint32_t ahi, uint32_t (&sum)[2][4]) {
+    constexpr int G = kScaleRowGroup;
+    const RenderDesc &d = s.r;
+    const int sx = chroma_sx(d.chroma), sy = chroma_sy(d.chroma);
+    const uint32_t oa = (uint32_t)s.oa;
+    ScaleChroma cc = {{0, 0}, {0, 0}};  // the chroma row in use
+    int in_yc = -1;                      // its number
+    for (int k0 = ka0; k0 < ka1; k0 += G) {
+        int ly[G][2], la[G][2];
+        ScaleChroma lc[G];
+        bool enter[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int y = s.ma * min(k0 + g, ka1 - 1) + s.ta;
+            ly[g][0] = sample_g<Pel>(d.plane[0], d.pitch[0], x0, y);
+            ly[g][1] = sample_g<Pel>(d.plane[0], d.pitch[0], x1, y);
+            enter[g] = false;
+            lc[g] = ScaleChroma{{0, 0}, {0, 0}};
+            if (d.chroma) {
+                const int yc = y >> sy;
+                enter[g] = yc != in_yc;  // (uniform)
+                if (enter[g]) {
+                    in_yc = yc;
+                    lc[g].cb[0] = sample_g<Pel>(d.plane[1], d.pitch[1], x0 >> sx, yc);
+                    lc[g].cr[0] = sample_g<Pel>(d.plane[2], d.pitch[2], x0 >> sx, yc);
+                    if (!sx) {
+                        lc[g].cb[1] = sample_g<Pel>(d.plane[1], d.pitch[1], x1, yc);
+                        lc[g].cr[1] = sample_g<Pel>(d.plane[2], d.pitch[2], x1, yc);
+                    }
+                }
+            }
+            la[g][0] = la[g][1] = 0;
+            if ((FMT & 1) && d.alpha) {
+                if (d.alpha_bps == 2) {
+                    la[g][0] = sample_g<uint16_t>(d.alpha, d.alpha_pitch, x0, y);
+                    la[g][1] = sample_g<uint16_t>(d.alpha, d.alpha_pitch, x1, y);
+                } else {
+                    la[g][0] = sample_g<uint8_t>(d.alpha, d.alpha_pitch, x0, y);
+                    la[g][1] = sample_g<uint8_t>(d.alpha, d.alpha_pitch, x1, y);
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int k = k0 + g;
+            if (k >= ka1) break;  // (uniform; the repeated rows past the end were loaded for nothing)
+            if (enter[g]) cc = lc[g];
+            const uint32_t w = min((uint32_t)(k + 1) * oa, ahi) - max((uint32_t)k * oa, alo);
+            scale_acc<FMT>(d, ly[g], cc, la[g], w, sum);
+        }
+    }
+}
+
+template <typename Pel, int FMT>
+__global__ void __launch_bounds__(256) k_render_scaled(const ScaleDesc *descs) {
+    constexpr bool WIDE = FMT >= RENDER_RGB16;
+    constexpr int NCH = (FMT & 1) ? 4 : 3;
+    constexpr int RES = kScaleTile * (kScaleTile + 1);  // dwords: 64 lines of pitch 65 (>= 8 lines of pitch 256)
+    __shared__ uint32_t colsum[4 * kScaleCols];
+    __shared__ uint32_t res[(WIDE ? 2 : 1) * RES];
+    const ScaleDesc s = descs[blockIdx.y];
+    const RenderDesc &d = s.r;
+    if ((int)blockIdx.x >= d.tiles) return;  // (a smaller image of the batch: the whole workgroup leaves)
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int a0 = ((int)blockIdx.x / d.tiles_x) * s.na, b0 = ((int)blockIdx.x % d.tiles_x) * s.nb;
+    const int a1 = min(a0 + s.na, s.oa), b1 = min(b0 + s.nb, s.ob);
+    const uint32_t ca = (uint32_t)s.ca, cb = (uint32_t)s.cb, oa = (uint32_t)s.oa, ob = (uint32_t)s.ob;
+    const int lp = d.swap ? kScaleTile + 1 : 256;  // pitch of the result tile in dwords
+    // the tile's footprint along b: window indices [kb0, kb1), source columns [xmin, xmax)
+    // (products of two sides stay below 2^32: every side is at most 65535)
+    const int kb0 = (int)((uint32_t)b0 * cb / ob), kb1 = (int)(((uint32_t)b1 * cb + ob - 1) / ob);
+    const int xmin = s.mb > 0 ? s.tb + kb0 : s.tb - (kb1 - 1);
+    const int xmax = s.mb > 0 ? s.tb + kb1 : s.tb - kb0 + 1;
+    // stage 2: this thread's output line along b and its channels c0, c0 + cstep, ...
+    const int bl = t & (s.nb - 1), c0 = t >> s.nb_log2, cstep = 256 >> s.nb_log2;
+    const bool bvalid = b0 + bl < b1;
+    const uint32_t blo = (uint32_t)(b0 + bl) * cb, bhi = blo + cb;  // its interval on the grid of 1 / (ob * cb)
+    const int kl = bvalid ? (int)(blo / ob) : 0, kh = bvalid ? (int)((bhi + ob - 1) / ob) : 0;
+
+    for (int a = a0; a < a1; ++a) {
+        const uint32_t alo = (uint32_t)a * ca, ahi = alo + ca;
+        const int ka0 = (int)(alo / oa), ka1 = (int)((ahi + oa - 1) / oa);
+        uint64_t acc[4] = {0, 0, 0, 0};
+        for (int xs = xmin & ~1; xs < xmax; xs += kScaleCols) {
+            const int x0 = xs + 2 * t;
+            if (x0 < xmax) {
+                // a column outside the footprint repeats its neighbour and is never read back
+                const int x0c = max(x0, xmin), x1c = min(x0 + 1, xmax - 1);
+                uint32_t sum[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+                scale_columns<Pel, FMT>(s, x0c, x1c, ka0, ka1, alo, ahi, sum);
+#pragma unroll
+                for (int c = 0; c < NCH; ++c)
+                    reinterpret_cast<uint2 *>(colsum + c * kScaleCols)[t] = make_uint2(sum[0][c], sum[1][c]);
+            }
+            __syncthreads();
+            if (bvalid) {
+                // the chunk's columns as window indices: [kc, kc + 512)
+                const int kc = s.mb > 0 ? xs - s.tb : s.tb - xs - (kScaleCols - 1);
+                const int k_lo = max(kl, kc), k_hi = min(kh, kc + kScaleCols);
+                for (int k = k_lo; k < k_hi; ++k) {
+                    const uint32_t w = min((uint32_t)(k + 1) * ob, bhi) - max((uint32_t)k * ob, blo);
+                    const int idx = s.mb * k + s.tb - xs;
+#pragma unroll
+                    for (int ci = 0; ci < 4; ++ci) {
+                        const int c = c0 + ci * cstep;
+                        if (c < NCH) acc[ci] += (uint64_t)w * colsum[c * kScaleCols + idx];
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        if (bvalid) {
+#pragma unroll
+            for (int ci = 0; ci < 4; ++ci) {
+                const int c = c0 + ci * cstep;
+                if (c >= 4) continue;
+                uint32_t q = 0;  // (the RGB formats keep a zero where alpha would be: store_row packs over it)
+                if (c < NCH) {
+                    const uint64_t num = 2 * acc[ci] + (s.den >> 1);
+                    q = (uint32_t)((double)num * s.inv_den);
+                    const int64_t rem = (int64_t)(num - (uint64_t)q * s.den);
+                    if (rem < 0) --q;
+                    else if (rem >= (int64_t)s.den) ++q;
+                }
+                const int at = (a - a0) * lp + bl;
+                if (WIDE) reinterpret_cast<uint16_t *>(res)[2 * ((c >> 1) * RES + at) + (c & 1)] = (uint16_t)q;
+                else reinterpret_cast<uint8_t *>(res)[4 * at + c] = (uint8_t)q;
+            }
+        }
+    }
+    __syncthreads();
+    // write: lanes along the output's x, 64 pixels of a row per wave and step
+    const Px none = {0, 0};
+    if (!d.swap) {
+        const int segs = s.nb >> 6;
+        for (int u = wave; u < (a1 - a0) * segs; u += 4) {
+            const int al = u / segs, oxw = b0 + (u % segs) * 64;
+            if (oxw >= d.out_w) continue;
+            const bool valid = oxw + lane < d.out_w;
+            Px p = none;
+            if (valid) {
+                p.lo = res[al * lp + (oxw - b0) + lane];
+                if (WIDE) p.hi = res[RES + al * lp + (oxw - b0) + lane];
+            }
+            store_row<FMT>(d, a0 + al, oxw, lane, p, valid);
+        }
+    } else {
+        const bool valid = a0 + lane < d.out_w;
+        for (int oy = b0 + wave; oy < b1; oy += 4) {
+            Px p = none;
+            if (valid) {
+                p.lo = res[lane * lp + (oy - b0)];
+                if (WIDE) p.hi = res[RES + lane * lp + (oy - b0)];
+            }
+            store_row<FMT>(d, oy, a0, lane, p, valid);
+        }
+    }
+}
+
+template <typename Pel>
+void launch_scaled_fmt(const ScaleDesc *descs, dim3 grid, int format, hipStream_t s) {
+    switch (format) {
+    case RENDER_RGB8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB8>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGBA8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA8>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGB16: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB16>), grid, dim3(256), 0, s, descs); break;
+    default: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA16>), grid, dim3(256), 0, s, descs); break;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_render_scaled(const ScaleDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                                hipStream_t s) {
+    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
+    if (bytes_per_sample == 1) launch_scaled_fmt<uint8_t>(descs, grid, format, s);
+    else launch_scaled_fmt<uint16_t>(descs, grid, format, s);
+    return hipGetLastError();
+}
 
 hipError_t launch_render(const RenderDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
                          hipStream_t s) {

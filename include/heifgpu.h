@@ -300,6 +300,58 @@ int heifgpu_render_batch(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, siz
                          const heifgpu_planes *alpha_in,
                          uint32_t format, const heifgpu_surface *out, void *stream);
 
+/* ---- scaled render: a window of the displayed picture, area-averaged --------
+ * (added within ABI 6: new entry points only.)
+ * Let D be the displayed picture of an image in the chosen format, exactly what
+ * heifgpu_render_batch writes (dw x dh = heifgpu_display_info.out_width x
+ * out_height).  A heifgpu_scale names a window (cx, cy, cw, ch) of D and a
+ * rendered size ow x oh; the result R is the exact area average of the window
+ * on that grid, per channel (alpha is averaged like a colour, nothing is
+ * premultiplied), in integers:
+ *     wx(X, i) = max(0, min((i+1)*ow, (X+1)*cw) - max(i*ow, X*cw))     i in [0, cw)
+ *     wy(Y, j) = max(0, min((j+1)*oh, (Y+1)*ch) - max(j*oh, Y*ch))     j in [0, ch)
+ *     acc      = sum_j sum_i wy(Y,j) * wx(X,i) * D[cy + j][cx + i][c]
+ *     R[Y][X][c] = floor((2*acc + cw*ch) / (2*cw*ch))                  (round half up)
+ * with no intermediate rounding (acc is a 64-bit sum).  ow == cw and oh == ch
+ * gives the window of D byte for byte; integer ratios give the rounded mean of
+ * each block; enlargement follows the same formula.  The average is taken over
+ * converted pixels, not over the YCbCr planes. */
+typedef struct {
+    uint32_t out_width, out_height;   /* rendered size, each 1..65535 */
+    uint32_t x, y, width, height;     /* window of the displayed picture, in its coordinates;
+                                         width == 0 && height == 0: the whole picture */
+} heifgpu_scale;
+enum { HEIFGPU_FIT_STRETCH = 0, HEIFGPU_FIT_CONTAIN = 1, HEIFGPU_FIT_COVER = 2 };
+/* The spec that shows a dw x dh picture (d->out_width x out_height) in a
+ * box_w x box_h box (host only, no device; exact 64-bit integers, round =
+ * round half up):
+ * STRETCH: the whole picture to box_w x box_h.
+ * CONTAIN: the whole picture; if dw*box_h >= dh*box_w: ow = box_w,
+ *   oh = max(1, round(dh*box_w / dw)); otherwise oh = box_h,
+ *   ow = max(1, round(dw*box_h / dh)).
+ * COVER: box_w x box_h out of a centred window of the box's aspect; if
+ *   dw*box_h >= dh*box_w: height = dh, width = max(1, round(dh*box_w / box_h)),
+ *   x = (dw - width) / 2 rounded down, y = 0; otherwise width = dw,
+ *   height = max(1, round(dw*box_h / box_w)), x = 0, y = (dh - height) / 2.
+ * A zero box side or an unknown mode is HEIFGPU_E_INVALID. */
+int heifgpu_scale_fit(const heifgpu_display_info *d, uint32_t box_w, uint32_t box_h, uint32_t mode,
+                      heifgpu_scale *out);
+/* heifgpu_render_batch with a heifgpu_scale per image: out[i] receives
+ * scale[i].out_width x out_height pixels.  Everything not named here is as in
+ * heifgpu_render_batch (formats, alpha rules, mixed batches, n <= 65535, the
+ * descriptor ring shared with it, ONE kernel launch whatever the sizes and
+ * ratios).  All checks run before anything is launched: a window that is empty
+ * (other than the 0, 0 "whole" form) or not inside dw x dh, a rendered side of
+ * 0 or above 65535 and a pitch below the rendered row are HEIFGPU_E_INVALID; a
+ * window side above 65535 is HEIFGPU_E_UNSUPPORTED.  Tuned for reduction;
+ * identity and enlargement are exact but slower than heifgpu_render_batch. */
+int heifgpu_render_batch_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                const heifgpu_planes *in,
+                                const heifgpu_image *const *alpha_imgs,
+                                const heifgpu_planes *alpha_in,
+                                uint32_t format, const heifgpu_scale *scale,
+                                const heifgpu_surface *out, void *stream);
+
 /* ---- host test hooks (reference unit-test surface) -------------------- */
 size_t heifgpu_remove_emulation_prevention(const uint8_t *in, size_t n, uint8_t *out); /* rbsp_reader.rs:11-39 */
 int heifgpu_read_ue(const uint8_t *buf, size_t n, uint32_t *val);                      /* rbsp_reader.rs:87-99 */

@@ -13,7 +13,20 @@ the runs.  GB/s counts the algorithmic bytes (1.5 read + 3 written per pixel);
 the share is of the 8.0 TB/s HBM3E peak.  RGBA16 of a 10-bit batch (3 bytes
 read, 8 written per pixel) is reported alone: it has no earlier counterpart.
 
-usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json]
+--scaled measures the scaled render instead (heifgpu_render_batch_scaled,
+DESIGN 5.17), on the same images, at rotation 0 and 3, the variants alternated
+in one process in each of the --runs runs:
+  full      heifgpu_render_batch RGB8 at full size (the kernel before it, unchanged)
+  cover512  heifgpu_render_batch_scaled RGB8, COVER to 512 x 384
+  cover224  the same to 224 x 224
+  torch     for the record: the route without it, `full`, a float conversion and
+            torch.nn.functional.interpolate(mode="area") to 512 x 384, image by
+            image (the float copy of a whole batch would not fit)
+GB/s over algorithmic bytes: 1.5 read per source pixel of the window plus the
+output bytes.  The condition of 5.17: cover512 and cover224 no slower than
+`full` at the same rotation beyond the measured spread (max - min over runs).
+
+usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json] [--scaled]
 """
 import argparse
 import ctypes
@@ -59,13 +72,107 @@ def summary(ms_runs, bytes_per_batch):
             "share_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 4)}
 
 
+def scaled_main(args):
+    n = args.images
+    dev = torch.device("cuda", 0)
+    ctx = H.DecodeContext(0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    golden = (ROOT / "tests" / "golden" / "halfmoonbay.heic").read_bytes()
+    g = torch.Generator(device=dev).manual_seed(1)
+    ys = [torch.randint(0, 256, (HGT, W), generator=g, device=dev, dtype=torch.int32).to(torch.uint8) for _ in range(n)]
+    cs = [[torch.randint(0, 256, (HGT // 2, W // 2), generator=g, device=dev, dtype=torch.int32).to(torch.uint8)
+           for _ in range(n)] for _ in range(2)]
+    planes = (_lib.Planes * n)()
+    for i in range(n):
+        for c, t in enumerate((ys[i], cs[0][i], cs[1][i])):
+            planes[i].plane[c] = t.data_ptr()
+            planes[i].pitch[c] = t.stride(0) * t.element_size()
+    result = {"images": n, "width": W, "height": HGT, "reps": args.reps, "runs": args.runs,
+              "device": torch.cuda.get_device_name(0), "hbm_peak_GBps": HBM_PEAK_GBS, "rgb8": {}}
+    for rot in (0, 3):
+        img = H.HeifImage.parse(forced_rotation(golden, rot))
+        d = img.display
+        imgs = (ctypes.c_void_p * n)(*[img._h.value] * n)
+        full_out = [torch.empty((d.out_height, d.out_width, 3), dtype=torch.uint8, device=dev) for _ in range(n)]
+        full_surf = (_lib.Surface * n)()
+        for i, t in enumerate(full_out):
+            full_surf[i].pixels, full_surf[i].pitch = t.data_ptr(), t.stride(0)
+
+        def full():
+            _lib.check(_lib.lib.heifgpu_render_batch(ctx._h, imgs, n, planes, None, None, _lib.PIX_RGB8, full_surf, stream))
+
+        def scaled_variant(bw, bh):
+            sc = (_lib.Scale * n)()
+            for i in range(n):
+                _lib.check(_lib.lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_COVER, ctypes.byref(sc[i])))
+            out = torch.empty((n, bh, bw, 3), dtype=torch.uint8, device=dev)
+            surf = (_lib.Surface * n)()
+            for i in range(n):
+                surf[i].pixels, surf[i].pitch = out[i].data_ptr(), out[i].stride(0)
+
+            def run():
+                _lib.check(_lib.lib.heifgpu_render_batch_scaled(ctx._h, imgs, n, planes, None, None, _lib.PIX_RGB8, sc,
+                                                                surf, stream))
+            window_px = (sc[0].width or d.out_width) * (sc[0].height or d.out_height)
+            return run, out, sc, n * (window_px * 1.5 + bw * bh * 3)
+
+        cover512, out512, sc512, bytes512 = scaled_variant(512, 384)
+        cover224, out224, sc224, bytes224 = scaled_variant(224, 224)
+        small = torch.empty((n, 3, 384, 512), dtype=torch.float32, device=dev)
+
+        def torch_route():
+            full()
+            for i in range(n):
+                s = sc512[i]
+                win = full_out[i][s.y:s.y + s.height, s.x:s.x + s.width].permute(2, 0, 1)[None].float()
+                small[i] = torch.nn.functional.interpolate(win, size=(384, 512), mode="area")[0]
+
+        variants = (("full", full, n * W * HGT * 4.5), ("cover512", cover512, bytes512),
+                    ("cover224", cover224, bytes224), ("torch", torch_route, n * W * HGT * 4.5))
+        for _, fn, _ in variants:  # warm-up
+            fn()
+        torch.cuda.synchronize()
+        # for the record, how far the float route is from the exact average: at a non-integer ratio
+        # interpolate(mode="area") gives every source pixel a window touches the same weight, whole
+        # (on these noise planes that is levels, not rounding; tests/test_scale_gpu.py pins the exact result)
+        diff = (small.permute(0, 2, 3, 1) - out512.float()).abs()
+        agree = {"mean_abs_diff_vs_torch": round(float(diff.mean()), 4), "max_abs_diff_vs_torch": round(float(diff.max()), 4)}
+        ms = {name: [] for name, _, _ in variants}
+        for _ in range(args.runs):
+            for name, fn, _ in variants:
+                ms[name].append(timed(fn, args.reps if name != "torch" else max(1, args.reps // 10)))
+        r = {name: summary(ms[name], nbytes) for name, _, nbytes in variants}
+        r["torch"].pop("GBps"), r["torch"].pop("share_of_hbm_peak")  # no algorithmic byte count of its own
+        for name in ("full", "cover512", "cover224", "torch"):
+            r[name]["spread_ms"] = round(r[name]["ms_max"] - r[name]["ms_min"], 4)
+        for name in ("cover512", "cover224"):
+            spread = max(r[name]["spread_ms"], r["full"]["spread_ms"])
+            r[name]["minus_full_ms"] = round(r[name]["ms_per_batch"] - r["full"]["ms_per_batch"], 4)
+            r[name]["of_full"] = round(r[name]["ms_per_batch"] / r["full"]["ms_per_batch"], 4)
+            r[name]["no_slower_than_full_beyond_spread"] = bool(r[name]["ms_per_batch"] <= r["full"]["ms_per_batch"] + spread)
+        r["cover512"]["torch_over_it"] = round(r["torch"]["ms_per_batch"] / r["cover512"]["ms_per_batch"], 2)
+        r["cover512"].update(agree)
+        result["rgb8"][f"rotation_{rot}"] = r
+        print(f"rotation {rot}: " + ", ".join(f"{name} {r[name]['ms_per_batch']:.3f} ms (spread {r[name]['spread_ms']:.3f})"
+                                              for name, _, _ in variants), flush=True)
+        del full_out, out512, out224, small
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=128)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--scaled", action="store_true", help="measure heifgpu_render_batch_scaled (see above)")
     args = ap.parse_args()
+    if args.scaled:
+        return scaled_main(args)
     n = args.images
     dev = torch.device("cuda", 0)
     ctx = H.DecodeContext(0)
