@@ -185,7 +185,21 @@ enum Unit : int {
     U_TB,       // next TB of the TU: record, or residual_coding header  7.3.8.11
     U_SB,       // one 4x4 sub-block of residual_coding                  7.3.8.11
     U_CTU_END,  // end_of_slice_segment_flag / end_of_subset_one_bit     7.3.8.1
+    // (vector engines) a finished TB: its record, then the next TB / tree node /
+    // CU end (tb_done).  Numbered last, so the kinds before it keep their counter
+    // slots; it runs between U_SB and U_CTU_END (pass_kind)
+    U_TBD,
 };
+// One pass of the lanes parse: every unit kind in syntax order.  U_TB (a TB
+// without coefficients) and U_SB (a TB's last sub-block) only mark the lane
+// U_TBD, so the record store, the tree walks and the CU's QpY rows run once per
+// pass for the lanes of both origins, not once inside each unit.  tb_done
+// leaves a lane in U_TB, U_TT or U_CQT (all earlier in the order: the next
+// pass, as when the units called it) or in U_CTU_END (later: the same pass).
+constexpr int kPassKinds = 8;
+// kind of the pass's step i: U_CTU .. U_SB, U_TBD, U_CTU_END (arithmetic, not a
+// table: the kernel's unrolled pass loop needs each step's kind as a constant)
+HG_HD constexpr int pass_kind(int i) { return i < U_SB ? i + 1 : (i == U_SB ? (int)U_TBD : (int)U_CTU_END); }
 
 // Lane.fl bits
 enum : uint32_t {
@@ -273,6 +287,31 @@ struct Lane {
     } while (0)
 #else
 #define HG_SB_T(L, i, t0) ((void)0)
+#endif
+
+// Emulation only (HEIFGPU_LANES_STATS prints them per wave): how often the parse
+// took the paths that the small pictures of tests/lanes_units_cases.py are
+// chosen for, so the test can tell that a picture reaches the path it names
+enum Cov : int {
+    COV_TB_LUMA,                      // + log2 - 2: coded luma TBs of 4, 8, 16, 32
+    COV_TB_CHROMA = COV_TB_LUMA + 4,  // + log2 - 2: coded chroma TBs
+    COV_NXN = COV_TB_CHROMA + 4,      // NxN CUs (four PBs)
+    COV_NXN_MPM,                      // their PBs with an MPM: + mpm_idx (0, 1, 2)
+    COV_NXN_REM = COV_NXN_MPM + 3,    // and with rem_intra_luma_pred_mode
+    COV_DQP,                          // cu_qp_delta_abs
+    COV_DQP_EG0,                      // with the EG0 suffix
+    COV_LAST_SUFFIX,                  // last_sig_coeff_{x,y}_suffix
+    COV_CODED_AFTER_EMPTY,            // a coded Cb TB after the TU's coefficient-free luma TB
+    COV_CU_ENDS_IN_SB,                // a CU's last TB ending in a sub-block (not in U_TB)
+    COV_TSKIP,                        // transform_skip_flag = 1
+    COV_LAST_CTX5,                    // a last_sig_coeff prefix of 9 (32x32 luma: its fifth context)
+    COV_N
+};
+#if defined(HG_HOST_EMU)
+long g_cov[COV_N];
+#define HG_COV(i) (++g_cov[i])
+#else
+#define HG_COV(i) ((void)0)
 #endif
 
 // bytes of n lane blocks, rounded up so the LanePic after them stays 16-byte aligned
@@ -1052,6 +1091,22 @@ HG_HD inline int byp_unary(Lane &L, const EG &G, int m) {
     return p;
 }
 
+// (vector engines) one PB's mode bins in ONE division, without a branch on
+// prev_intra_luma_pred_flag: the next 5 bypass bins are divided out unconsumed;
+// rem_intra_luma_pred_mode is all five, mpm_idx (TR, cMax 2: 0, 10, 11) the
+// first one or two (a prefix of a long-division quotient is the quotient of
+// the shorter division, as in byp_rem).  Returns mpm_idx or the remainder.
+template <class EG>
+HG_HD inline int byp_luma_mode(Lane &L, const EG &G, int prev) {
+    const uint32_t q5 = div_range(L.value >> (L.k - 5), L.range);  // k >= 8 on entry
+    const int used = prev ? 1 + (int)(q5 >> 4) : 5;
+    const uint32_t q = q5 >> (5 - used);
+    L.k -= used;
+    L.value -= (q * L.range) << L.k;
+    if (L.k < 8) vfill(L, G);
+    return (int)(prev ? q - (q >> 1) : q);  // mpm_idx: bins 0 -> 0, 10 -> 1, 11 -> 2
+}
+
 // DecodeTerminate (arithmetic.rs:159-169)
 template <class EG>
 HG_HD inline int term(Lane &L, const EG &G) {
@@ -1572,14 +1627,27 @@ HG_HD inline void unit_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     }
     const int np = nxn ? 4 : 1;
     const int pb = nxn ? 1 << (L.ql - 1) : 1 << L.ql;
+    if (nxn) HG_COV(COV_NXN);
     int prev = 0;
-    for (int i = 0; i < np; ++i) prev |= dec(L, G, CTX_PREV_INTRA) << i;
+    if constexpr (!EG::kSolo) {
+        // the 1 or 4 bins share one context: read once, decided in a register, stored once
+        uint32_t t = ctx_ld(L, G, CTX_PREV_INTRA);
+        for (int i = 0; i < np; ++i) prev |= dec_t(L, G, t & 0x7fu, t) << i;
+        ctx_st(L, G, CTX_PREV_INTRA, t & 0x7fu);
+    } else {
+        for (int i = 0; i < np; ++i) prev |= dec(L, G, CTX_PREV_INTRA) << i;
+    }
     int modes = 0;
     for (int i = 0; i < np; ++i) {
         const int p = (prev >> i) & 1;
         int mpm = 0, rem = 0;
-        if (p) mpm = byp(L, G) ? (byp(L, G) ? 2 : 1) : 0;
-        else rem = (int)byp_bits(L, G, 5);
+        if constexpr (EG::kSolo) {
+            if (p) mpm = byp(L, G) ? (byp(L, G) ? 2 : 1) : 0;
+            else rem = (int)byp_bits(L, G, 5);
+        } else {
+            mpm = rem = byp_luma_mode(L, G, p);
+        }
+        if (nxn) HG_COV(p ? COV_NXN_MPM + mpm : COV_NXN_REM);
         const int xPb = L.qx + (i & 1) * pb, yPb = L.qy + (i >> 1) * pb;
         const int m = derive_luma_mode(L, ld, xPb, yPb, p, mpm, rem);
         modes |= m << (8 * i);
@@ -1651,8 +1719,20 @@ HG_HD inline void unit_tt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     const bool cbf_c = HG_PIC_CHROMA(P) == 0 ? false : (chroma4 ? pc != 0 : cbf != 0);
     if (((L.fl & F_CBF_L) || cbf_c) && (pic_flags<EG>(P) & SP_CU_QP_DELTA) && !(L.fl & F_DQP_CODED)) {
         int v = 0;  // cu_qp_delta_abs: TR prefix (cMax 5), EG0 suffix
-        while (v < 5 && dec(L, G, CTX_CU_QP_DELTA + (v == 0 ? 0 : 1))) ++v;
+        if constexpr (!EG::kSolo) {
+            // the first bin's context, then one context for bins 2 to 5: read once, stored once
+            v = dec(L, G, CTX_CU_QP_DELTA);
+            if (v) {
+                uint32_t t = ctx_ld(L, G, CTX_CU_QP_DELTA + 1);
+                while (v < 5 && dec_t(L, G, t & 0x7fu, t)) ++v;
+                ctx_st(L, G, CTX_CU_QP_DELTA + 1, t & 0x7fu);
+            }
+        } else {
+            while (v < 5 && dec(L, G, CTX_CU_QP_DELTA + (v == 0 ? 0 : 1))) ++v;
+        }
+        HG_COV(COV_DQP);
         if (v == 5) {
+            HG_COV(COV_DQP_EG0);
             int ones = 0;
             bool bad = false;
             while (byp(L, G)) {
@@ -1729,6 +1809,7 @@ HG_HD inline void cu_done(Lane &L, LaneLds &ld, LanePic &P);
 
 // After a TB: its record, then the next TB of the TU, the next transform-tree
 // node, or (tree done) the CU's QpY and the next coding-quadtree node / CTU end.
+// (Vector engines: the U_TBD step of the pass; scalar engines: from U_TB / U_SB.)
 template <class EG>
 HG_HD inline void tb_done(Lane &L, LaneLds &ld, LanePic &P) {
     tu_emit<EG>(L, P);
@@ -1795,8 +1876,9 @@ HG_HD inline void cu_done(Lane &L, LaneLds &ld, LanePic &P) {
     L.st = U_CTU_END;
 }
 
-// U_TB: TB tb_t of the TU; without coefficients it is done here, otherwise
-// residual_coding's header (transform_skip_flag, last position) is parsed
+// U_TB: TB tb_t of the TU; without coefficients it is done (vector engines: it
+// goes to the pass's U_TBD step), otherwise residual_coding's header
+// (transform_skip_flag, last position) is parsed
 template <class EG>
 HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     const int t = L.tb_t;
@@ -1839,21 +1921,29 @@ HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     L.fl = (L.fl & ~(F_TS | F_TB_CBF)) | (cbf ? F_TB_CBF : 0u);
     L.tb_coef0 = L.ncoef;
     if (!cbf) {
-        tb_done<EG>(L, ld, P);
+        if constexpr (EG::kSolo) tb_done<EG>(L, ld, P);
+        else L.st = U_TBD;
         return;
     }
     // residual_coding header (7.3.8.11)
     const int l2 = L.tb_log2, n = 1 << l2, cidx = comp;
+    HG_COV((cidx ? COV_TB_CHROMA : COV_TB_LUMA) + l2 - 2);
+    if (t == 1 && !(L.fl & F_CBF_L)) HG_COV(COV_CODED_AFTER_EMPTY);
     if ((pic_flags<EG>(P) & SP_TRANSFORM_SKIP) && !(L.fl & F_BYPASS) && l2 == 2 && dec(L, G, CTX_TS_FLAG + (cidx ? 1 : 0)))
         L.fl |= F_TS;
+    if (L.fl & F_TS) HG_COV(COV_TSKIP);
     // last_sig_coeff_{x,y}_prefix (decoder.rs:109-130), suffixes
     const int cmax = (l2 << 1) - 1;
     const int off = cidx == 0 ? 3 * (l2 - 2) + ((l2 - 1) >> 2) : 15;
     const int shift = cidx == 0 ? (l2 + 1) >> 2 : l2 - 2;
     int px = 0, py = 0;
+    // (a register word of the prefix's up to five contexts, read and stored once,
+    // measured no faster than these per-bin LDS bytes: DESIGN 5.18)
     while (px < cmax && dec(L, G, CTX_LAST_X + off + (px >> shift))) ++px;
     while (py < cmax && dec(L, G, CTX_LAST_Y + off + (py >> shift))) ++py;
     int lx = px, ly = py;
+    if (px > 3 || py > 3) HG_COV(COV_LAST_SUFFIX);
+    if (px > 8 || py > 8) HG_COV(COV_LAST_CTX5);
     if (px > 3) {
         const int k = (px >> 1) - 1;
         lx = (1 << k) * (2 + (px & 1)) + (int)byp_bits(L, G, k);
@@ -2227,7 +2317,13 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         HG_SB_T(L, 3, tsb);
         sb_store<EG>(L, P, sig, signs, nib, xS, yS, hide);
     }
-    if (--L.rc_i < 0) tb_done<EG>(L, ld, P);
+    if (--L.rc_i < 0) {
+        // (the TU at the CU's bottom right corner, its last TB)
+        if (L.tb_t + 1 >= L.tb_n && L.tx + (1 << L.tl) == L.qx + (1 << L.ql) && L.ty + (1 << L.tl) == L.qy + (1 << L.ql))
+            HG_COV(COV_CU_ENDS_IN_SB);
+        if constexpr (EG::kSolo) tb_done<EG>(L, ld, P);
+        else L.st = U_TBD;
+    }
 }
 
 // U_CTU_END: WPP context storage, the depth line, end_of_slice_segment_flag /
@@ -2344,6 +2440,9 @@ HG_HD inline void run_unit(int kind, Lane &L, LaneLds &ld, LanePic &P, const Env
     case U_CQT: unit_cqt(L, ld, P, G); break;
     case U_CTU: unit_ctu(L, ld, P, E, G); break;
     case U_CTU_END: unit_ctu_end(L, ld, P, E, G); break;
+    case U_TBD:  // (vector engines only: the scalar ones finish a TB inside U_TB / U_SB)
+        if constexpr (!EG::kSolo) tb_done<EG>(L, ld, P);
+        break;
     default: break;
     }
 }
@@ -2638,10 +2737,18 @@ void emu_parse_lanes(const BatchArgs &a) {
     uint32_t prog[64];
     static const bool stats = std::getenv("HEIFGPU_LANES_STATS") != nullptr;
     // modelling knob (emulation only): the unit kinds of one pass, in order, as
-    // digits (default "1234567": U_CTU .. U_CTU_END once)
+    // digits (default "12345687", pass_kind: U_CTU .. U_SB, U_TBD, U_CTU_END once);
+    // characters that name no unit kind are ignored
     static const std::string order = [] {
         const char *e = std::getenv("HEIFGPU_EMU_PASS_ORDER");
-        return std::string(e && *e ? e : "1234567");
+        std::string o;
+        if (e && *e) {
+            for (const char *c = e; *c; ++c)
+                if (*c >= '0' + U_CTU && *c <= '0' + U_TBD) o += *c;
+        } else {
+            for (int i = 0; i < kPassKinds; ++i) o += (char)('0' + pass_kind(i));
+        }
+        return o;
     }();
     for (int w = 0; w < waves; ++w) {
         for (int l = 0; l < 64; ++l) {
@@ -2654,7 +2761,7 @@ void emu_parse_lanes(const BatchArgs &a) {
             if (!live) lanes[l].st = U_DONE;
         }
         Env E{&a, lds.data(), prog, a.wpp_ring ? wctx.data() : nullptr, 0};
-        long passes = 0, units = 0, kruns = 0, kr[8] = {}, ku[8] = {};
+        long passes = 0, units = 0, kruns = 0, kr[U_TBD + 1] = {}, ku[U_TBD + 1] = {};
         for (;; ++passes) {
             bool any = false, progressed = false;
             for (int l = 0; l < 64; ++l) any |= lanes[l].st != U_DONE;
@@ -2705,9 +2812,11 @@ void emu_parse_lanes(const BatchArgs &a) {
             printf("wave %d: %ld passes, %.1f units per pass, %ld kind runs, %.2f units per kind run\n", w, passes,
                    (double)units / passes, kruns, (double)units / kruns);
             printf("  runs");
-            for (int k = U_CTU; k <= U_CTU_END; ++k) printf(" %ld", kr[k]);
+            for (int k = U_CTU; k <= U_TBD; ++k) printf(" %ld", kr[k]);
             printf("\n  units");
-            for (int k = U_CTU; k <= U_CTU_END; ++k) printf(" %ld", ku[k]);
+            for (int k = U_CTU; k <= U_TBD; ++k) printf(" %ld", ku[k]);
+            printf("\n  paths");  // (Cov, counted since the last wave)
+            for (int k = 0; k < COV_N; ++k) printf(" %ld", g_cov[k]), g_cov[k] = 0;
             printf("\n");
         }
     }
@@ -2868,7 +2977,7 @@ __device__ __forceinline__ void parse_lanes_body(const BatchArgs &a) {
 #endif
 #if defined(HG_PARSE_PROF)
     uint64_t pw = 0;                                // the passes' start (pass_wait, q_refill)
-    uint32_t kc[U_CTU_END] = {0, 0, 0, 0, 0, 0, 0};  // passes that ran each unit kind
+    uint32_t kc[U_TBD] = {0, 0, 0, 0, 0, 0, 0, 0};  // passes that ran each unit kind
 #endif
     for (uint32_t pass = 0;; ++pass) {
         if (!__any(L.st != U_DONE)) break;
@@ -2883,10 +2992,12 @@ __device__ __forceinline__ void parse_lanes_body(const BatchArgs &a) {
         // one pass: every unit kind in syntax order, each run by the lanes in it
         // (a uniform loop: the units are never linearised into one divergent region)
         bool progressed = false;
-#pragma unroll
-        for (int kind = U_CTU; kind <= U_CTU_END; ++kind) {
+        // (a lambda per step, not a loop over pass_kind: each step's kind has to be a
+        // constant, and the optimizer does not unroll the loop once it has eight steps)
+        auto step = [&](auto kind_c) __attribute__((always_inline)) {
+            constexpr int kind = decltype(kind_c)::value;
             const bool mine = L.st == kind && (kind != U_CTU || ctu_ready<EG>(L, P, E));
-            if (!__any(mine)) continue;
+            if (!__any(mine)) return;
             progressed = true;
 #if defined(HG_PARSE_PROF)
             ++kc[kind - 1];
@@ -2896,9 +3007,19 @@ __device__ __forceinline__ void parse_lanes_body(const BatchArgs &a) {
             if (mine) run_unit(kind, L, ld, P, E, G);
 #if defined(HG_PARSE_PROF)
             const uint64_t t2 = __builtin_amdgcn_s_memtime();
-            pf[kind <= U_CTU ? 2 : kind <= U_TT ? 3 : kind - 1] += t2 - t1;
+            // (U_TBD with the TB unit: its no-cbf path held that code before)
+            pf[kind <= U_CTU ? 2 : kind <= U_TT ? 3 : kind == U_TBD ? 4 : kind - 1] += t2 - t1;
 #endif
-        }
+        };
+        step(std::integral_constant<int, pass_kind(0)>{});
+        step(std::integral_constant<int, pass_kind(1)>{});
+        step(std::integral_constant<int, pass_kind(2)>{});
+        step(std::integral_constant<int, pass_kind(3)>{});
+        step(std::integral_constant<int, pass_kind(4)>{});
+        step(std::integral_constant<int, pass_kind(5)>{});
+        step(std::integral_constant<int, pass_kind(6)>{});
+        step(std::integral_constant<int, pass_kind(7)>{});
+        static_assert(kPassKinds == 8, "one step per kind of the pass");
 #if defined(HG_PARSE_PROF)
         ++pf[1];
 #endif
@@ -2944,14 +3065,15 @@ __device__ __forceinline__ void parse_lanes_body(const BatchArgs &a) {
                                      ((uint64_t)(p1 & 0xffffu) << 32) | ((uint64_t)(p2 & 0xffffu) << 48);
             // the wave's own breakdown (tools/wave_times.py): s_memtime cycles of the
             // wave, per unit kind group (pf[2..6]), of the pass starts, the lanes x
-            // units / 4, and the passes that ran each unit kind (16 bits each)
+            // units / 4, and the passes that ran each unit kind (16 bits each; U_TBD's
+            // above the pass starts' 48 bits)
             if (blockIdx.x < (unsigned)kWaveRecCap) {
                 uint64_t *r = &g_ctu_t[kWaveRec + blockIdx.x][0];
                 uint64_t *r2 = &g_ctu_t[kWaveRec + kWaveRecCap + blockIdx.x][0];
                 uint64_t *r3 = &g_ctu_t[kWaveRec + 2 * kWaveRecCap + blockIdx.x][0];
                 r[0] = pf[0], r[1] = pf[2], r[2] = pf[3];
                 r2[0] = pf[4], r2[1] = pf[5], r2[2] = pf[6];
-                r3[0] = pw;
+                r3[0] = (pw & 0xffffffffffffull) | ((uint64_t)std::min<uint32_t>(kc[7], 0xffffu) << 48);
                 r3[1] = (uint64_t)kc[0] | ((uint64_t)kc[1] << 16) | ((uint64_t)kc[2] << 32) | ((uint64_t)kc[3] << 48);
                 r3[2] = (uint64_t)kc[4] | ((uint64_t)kc[5] << 16) | ((uint64_t)kc[6] << 32) |
                         (std::min<uint64_t>(pf[7] >> 2, 0xffffu) << 48);

@@ -82,9 +82,11 @@ def main():
         if b[0] == 0:
             continue
         kc = [(b[7] >> s) & 0xffff for s in (0, 16, 32, 48)] + [(b[8] >> s) & 0xffff for s in (0, 16, 32)]
+        # ("tb" holds the TB-completion step's cycles too; its passes ride above the pass starts' 48 bits)
         r["cycles"] = {"wave": b[0], "ctu": b[1], "tree": b[2], "tb": b[3], "sb": b[4], "ctu_end": b[5],
-                       "pass_start": b[6]}
+                       "pass_start": b[6] & ((1 << 48) - 1)}
         r["kind_passes"] = dict(zip(KINDS, kc))
+        r["kind_passes"]["tbd"] = b[6] >> 48
         r["lane_units"] = 4 * (b[8] >> 48)
         if sb:  # header, sig loop, greater1/2, signs + remainders + record (cycles, one lane per run), sig bins
             r["sb_phases"] = dict(zip(["head", "sig", "g1g2", "rest", "sig_bins"], b[9:14]))
