@@ -384,6 +384,96 @@ class DecodeContext:
                                                    scales, surf, ctypes.c_void_p(stream)))
         return whole if whole is not None else res
 
+    def render_tensor(self, outs: Sequence[DecodedImage], size, mode: str = "cover", dtype=None, layout: str = "chw",
+                      mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), src: str = "rgb8", windows=None,
+                      flips=None, alphas: Optional[Sequence[Optional[DecodedImage]]] = None, scale_bias=None,
+                      stream: Optional[int] = None):
+        """render_scaled() as a loader wants it: crop, flip and normalise into
+        float elements with ONE heifgpu_render_batch_tensor call (one kernel
+        launch).  With R the integers render_scaled(fmt=src) gives, flipped
+        (flips[i] & 1 reverses the columns, & 2 the rows), every element is
+        float32(R) * a[c] + b[c] in float32 (two roundings), rounded to `dtype`
+        (torch.float16 by default, float32 or bfloat16).  a and b come from
+        scale_bias=(a, b), or from mean / std (one per channel; four for an
+        RGBA src): a = float32(1 / (maxv * std)), b = float32(-mean / std),
+        maxv = 255 for the 8-bit sources and (1 << B) - 1 for the 16-bit ones
+        (pictures of different bit depths B then have no common a, b: ValueError).
+        layout "chw" returns ONE (N, C, h, w) tensor, "hwc" ONE (N, h, w, C)
+        tensor, for cover, stretch and windows; "contain" returns a list of
+        (C, h_i, w_i) or (h_i, w_i, C) tensors.  size, mode, windows and alphas
+        as in render_scaled()."""
+        torch = self._torch
+        n = len(outs)
+        f = _lib.PIX_FORMATS[src]
+        ch, wide = (4 if f & 1 else 3), f >= _lib.PIX_RGB16
+        dtype = torch.float16 if dtype is None else dtype
+        elems = {torch.float32: _lib.ELEM_F32, torch.float16: _lib.ELEM_F16, torch.bfloat16: _lib.ELEM_BF16}
+        if dtype not in elems:
+            raise ValueError(f"dtype {dtype!r}: torch.float32, torch.float16 or torch.bfloat16")
+        if layout not in _lib.LAYOUTS:
+            raise ValueError(f"layout {layout!r}: one of {sorted(_lib.LAYOUTS)}")
+        if mode not in _lib.FIT_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(_lib.FIT_MODES)}")
+        if any(o.image is None for o in outs) or (alphas is not None and any(a is not None and a.image is None for a in alphas)):
+            raise ValueError("render_tensor needs images that carry their HeifImage (alloc_outputs)")
+        for name, v in (("alphas", alphas), ("windows", windows), ("flips", flips)):
+            if v is not None and len(v) != n:
+                raise ValueError(f"{name} must have one entry per image")
+        if flips is not None and any(int(v) not in (0, 1, 2, 3) for v in flips):
+            raise ValueError("flips[i] is 0, 1 (columns), 2 (rows) or 3 (both)")
+        tf = _lib.TensorFormat(src=f, elem=elems[dtype], layout=_lib.LAYOUTS[layout])
+        if scale_bias is not None:
+            a, b = ([float(v) for v in part] for part in scale_bias)
+            if len(a) != ch or len(b) != ch:
+                raise ValueError(f"scale_bias needs {ch} scales and {ch} biases for {src}")
+        else:
+            mean, std = [float(v) for v in mean], [float(v) for v in std]
+            if len(mean) != ch or len(std) != ch:
+                raise ValueError(f"mean and std need {ch} entries for {src}")
+            depths = {int(o.info.bit_depth) for o in outs} if wide else {8}
+            if len(depths) > 1:
+                raise ValueError(f"pictures of bit depths {sorted(depths)} share no scale for {src}: pass scale_bias")
+            maxv = float((1 << depths.pop()) - 1) if depths else 255.0
+            a, b = [1.0 / (maxv * s) for s in std], [-m / s for m, s in zip(mean, std)]  # in double, rounded once below
+        for c in range(ch):
+            tf.a[c], tf.b[c] = a[c], b[c]
+        bh, bw = int(size[0]), int(size[1])
+        scales = (_lib.Scale * max(n, 1))()
+        for i, o in enumerate(outs):
+            if windows is not None:
+                x, y, w, h = (int(v) for v in windows[i])
+                scales[i] = _lib.Scale(bw, bh, x, y, w, h)
+            else:
+                d = o.image.display
+                _lib.check(lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_MODES[mode], ctypes.byref(scales[i])))
+        dev = torch.device("cuda", self.device)
+        chw = layout == "chw"
+
+        def shape(h, w):
+            return (ch, h, w) if chw else (h, w, ch)
+
+        if windows is not None or mode != "contain":
+            whole = torch.empty((n,) + shape(bh, bw), dtype=dtype, device=dev)
+            res = [whole[i] for i in range(n)]
+        else:
+            whole = None
+            res = [torch.empty(shape(scales[i].out_height, scales[i].out_width), dtype=dtype, device=dev)
+                   for i in range(n)]
+        if n == 0:
+            return whole if whole is not None else res
+        surf = (_lib.TensorSurface * n)()
+        for i, t in enumerate(res):
+            surf[i].data = t.data_ptr()
+            surf[i].stride_c = t.stride(0) * t.element_size() if chw else 0
+            surf[i].stride_y = t.stride(1 if chw else 0) * t.element_size()
+        fl = None if flips is None else (ctypes.c_uint32 * n)(*[int(v) for v in flips])
+        imgs, aimgs, aplanes = self._render_args(outs, alphas)
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(lib.heifgpu_render_batch_tensor(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes,
+                                                   ctypes.byref(tf), scales, fl, surf, ctypes.c_void_p(stream)))
+        return whole if whole is not None else res
+
 
 def ipc_export(tensor) -> bytes:
     """heifgpu_ipc_export of a device tensor's storage: 72 bytes another
@@ -515,6 +605,20 @@ class HeicDecoder:
         if size is not None:
             return ctx.render_scaled([out], size, mode, fmt, alphas)[0]
         return ctx.render([out], fmt, alphas)[0]
+
+    @classmethod
+    def decode_tensor(cls, data: bytes, size, mode: str = "cover", device: int = 0, flip: int = 0, **kw):
+        """decode_display(size=) as a normalised float tensor: decodes the
+        primary image (and its alpha plane when `src` is an RGBA format and the
+        file has one), then DecodeContext.render_tensor of that one picture:
+        (C, h, w), or (h, w, C) for layout="hwc".  dtype, layout, mean, std, src
+        and scale_bias go through to render_tensor."""
+        ctx = cls.context(device)
+        out = cls.decode(data, device)
+        aid = out.image.display.alpha_item_id
+        rgba = kw.get("src", "rgb8").startswith("rgba")
+        alphas = [cls.decode(data, device, aid)] if aid and rgba else None
+        return ctx.render_tensor([out], size, mode, flips=[flip], alphas=alphas, **kw)[0]
 
     @classmethod
     def decode(cls, data: bytes, device: int = 0, item_id: int = 0) -> DecodedImage:

@@ -144,6 +144,22 @@ class Scale(ctypes.Structure):
                 ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
 
 
+class TensorFormat(ctypes.Structure):
+    """heifgpu_tensor_format: the integer format the picture is rendered in, the
+    element type and layout it is written as, and out = R * a[c] + b[c]."""
+    _fields_ = [("src", ctypes.c_uint32), ("elem", ctypes.c_uint32), ("layout", ctypes.c_uint32),
+                ("a", ctypes.c_float * 4), ("b", ctypes.c_float * 4)]
+
+
+class TensorSurface(ctypes.Structure):
+    """heifgpu_tensor_surface: one image's elements on the device, strides in bytes."""
+    _fields_ = [("data", ctypes.c_void_p), ("stride_c", ctypes.c_int64), ("stride_y", ctypes.c_int64)]
+
+
+ELEM_F32, ELEM_F16, ELEM_BF16 = 0, 1, 2
+LAYOUT_CHW, LAYOUT_HWC = 0, 1
+LAYOUTS = {"chw": LAYOUT_CHW, "hwc": LAYOUT_HWC}
+
 FIT_STRETCH, FIT_CONTAIN, FIT_COVER = 0, 1, 2
 FIT_MODES = {"stretch": FIT_STRETCH, "contain": FIT_CONTAIN, "cover": FIT_COVER}
 
@@ -168,6 +184,7 @@ EXPORTS = (
     "heifgpu_image_parse_many", "heifgpu_batch_parse_geometry", "heifgpu_ipc_export", "heifgpu_ipc_open",
     "heifgpu_ipc_close", "heifgpu_batch_status_previous", "heifgpu_abi_version", "heifgpu_batch_lanes_variant",
     "heifgpu_image_get_display", "heifgpu_render_batch", "heifgpu_scale_fit", "heifgpu_render_batch_scaled",
+    "heifgpu_render_batch_tensor",
 )
 
 
@@ -244,6 +261,8 @@ def _load() -> ctypes.CDLL:
         "heifgpu_scale_fit": (I32, [P(DisplayInfo), U32, U32, U32, P(Scale)]),
         "heifgpu_render_batch_scaled": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), U32, P(Scale), P(Surface),
                                               VP]),
+        "heifgpu_render_batch_tensor": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), P(TensorFormat), P(Scale),
+                                              P(U32), P(TensorSurface), VP]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     optional = {"heifgpu_batch_lanes_variant"}

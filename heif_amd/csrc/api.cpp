@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
@@ -186,8 +187,8 @@ struct PinnedBuf {
 
 }  // namespace
 
-// heifgpu_render_batch's (and heifgpu_render_batch_scaled's) descriptors travel through a ring of slots, each a
-// pinned host image, a device array and an event recorded behind the kernel
+// heifgpu_render_batch's (and heifgpu_render_batch_scaled's / _tensor's) descriptors travel through a ring of slots,
+// each a pinned host image, a device array and an event recorded behind the kernel
 // that reads them: a call never rewrites descriptors that an earlier call's
 // copy or kernel may still read (the host waits only when the ring wraps).
 constexpr int kRenderSlots = 4;
@@ -196,6 +197,7 @@ struct RenderRing {
         PinnedBuf host;
         DevBuf<RenderDesc> dev;
         DevBuf<ScaleDesc> sdev;  // heifgpu_render_batch_scaled's
+        DevBuf<TensorDesc> tdev;  // heifgpu_render_batch_tensor's
         hipEvent_t done = nullptr;
         bool pending = false;
     } slot[kRenderSlots];
@@ -523,6 +525,7 @@ int heifgpu_image_get_display(const heifgpu_image *img, heifgpu_display_info *ou
 // What heifgpu_render_batch and heifgpu_render_batch_scaled check and fill alike for
 // image i: dm is the map the kernel reads through (for the scaled call the window is
 // folded in; dm.out_width x out_height is then the window), ow x oh the size written.
+// out == nullptr (heifgpu_render_batch_tensor): the caller checks and fills its own output.
 static int render_desc_fill(size_t i, const heifgpu_image *const *imgs, const heifgpu_planes *in,
                             const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
                             const heifgpu_surface *out, const DisplayMap &dm, uint32_t ow, uint32_t oh, int &bps,
@@ -531,16 +534,16 @@ static int render_desc_fill(size_t i, const heifgpu_image *const *imgs, const he
     const int bpp = (with_alpha ? 4 : 3) * (wide ? 2 : 1);
     heifgpu_image_info info;
     heifgpu_image_get_info(imgs[i], &info);
-    if (!in[i].plane[0] || !out[i].pixels) return fail(HEIFGPU_E_INVALID, "missing plane or surface");
+    if (!in[i].plane[0] || (out && !out[i].pixels)) return fail(HEIFGPU_E_INVALID, "missing plane or surface");
     if (info.chroma_format_idc && (!in[i].plane[1] || !in[i].plane[2]))
         return fail(HEIFGPU_E_INVALID, "missing chroma plane");
     if (info.bit_depth < 8 || info.bit_depth > (wide ? 12u : 16u)) return fail(HEIFGPU_E_INVALID, "bit depth");
     if (bps && bps != int(info.bytes_per_sample))
         return fail(HEIFGPU_E_UNSUPPORTED, "images of 1-byte and 2-byte samples in one render call");
     bps = int(info.bytes_per_sample);
-    if (int64_t(out[i].pitch) < int64_t(bpp) * ow)
+    if (out && int64_t(out[i].pitch) < int64_t(bpp) * ow)
         return fail(HEIFGPU_E_INVALID, "surface pitch smaller than the output row");
-    if (wide && ((reinterpret_cast<uintptr_t>(out[i].pixels) | uint32_t(out[i].pitch)) & 1))
+    if (out && wide && ((reinterpret_cast<uintptr_t>(out[i].pixels) | uint32_t(out[i].pitch)) & 1))
         return fail(HEIFGPU_E_INVALID, "16-bit surface not 2-byte aligned");
     // the map's corners inside the decoded planes (parse_heic built it so; the kernel reads unchecked)
     for (int c = 0; c < 4; ++c) {
@@ -554,8 +557,10 @@ static int render_desc_fill(size_t i, const heifgpu_image *const *imgs, const he
         d.plane[k] = reinterpret_cast<uint64_t>(in[i].plane[k]);
         d.pitch[k] = in[i].pitch[k];
     }
-    d.out = reinterpret_cast<uint64_t>(out[i].pixels);
-    d.out_pitch = out[i].pitch;
+    if (out) {
+        d.out = reinterpret_cast<uint64_t>(out[i].pixels);
+        d.out_pitch = out[i].pitch;
+    }
     d.out_w = int32_t(ow);
     d.out_h = int32_t(oh);
     for (int k = 0; k < 4; ++k) d.m[k] = dm.m[k];
@@ -664,6 +669,57 @@ int heifgpu_scale_fit(const heifgpu_display_info *d, uint32_t box_w, uint32_t bo
     return HEIFGPU_OK;
 }
 
+// What heifgpu_render_batch_scaled and heifgpu_render_batch_tensor check and fill alike
+// for image i: the window, then `flip` (bit 0: columns, bit 1: rows of the rendered
+// picture, which is the mirrored window rendered: the weights are symmetric) as further
+// steps of the display map, render_desc_fill through that map, and the tile geometry.
+static int scale_desc_fill(size_t i, const heifgpu_image *const *imgs, const heifgpu_planes *in,
+                           const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                           const heifgpu_scale &sc, uint32_t flip, const heifgpu_surface *out, int &bps, ScaleDesc &sd) {
+    if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
+    DisplayMap dm = imgs[i]->img.display;
+    if (!sc.out_width || !sc.out_height || sc.out_width > 65535 || sc.out_height > 65535)
+        return fail(HEIFGPU_E_INVALID, "rendered size outside 1..65535");
+    if (sc.width || sc.height) {
+        if (!sc.width || !sc.height || sc.x >= dm.out_width || sc.y >= dm.out_height ||
+            sc.width > dm.out_width - sc.x || sc.height > dm.out_height - sc.y)
+            return fail(HEIFGPU_E_INVALID, "window empty or outside the displayed picture");
+        display_window(dm, sc.x, sc.y, sc.width, sc.height);
+    }
+    if (flip & 1) display_imir(dm, 0);
+    if (flip & 2) display_imir(dm, 1);
+    if (dm.out_width > 65535 || dm.out_height > 65535)
+        return fail(HEIFGPU_E_UNSUPPORTED, "window side above 65535");  // (the 32-bit line sums of the kernel)
+    sd = ScaleDesc{};
+    RenderDesc &d = sd.r;
+    if (int rc = render_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, out, dm, sc.out_width, sc.out_height, bps,
+                                  d))
+        return rc;
+    // the source's axes: a runs along its y, b along its x (kernels.hpp)
+    const int32_t cw = int32_t(dm.out_width), ch = int32_t(dm.out_height);
+    if (d.swap) {
+        sd.ca = cw, sd.oa = d.out_w, sd.ma = d.m[2], sd.ta = d.t[1];
+        sd.cb = ch, sd.ob = d.out_h, sd.mb = d.m[1], sd.tb = d.t[0];
+        // 64 pixels along the output's x (store_row); along its y as many as keep the footprint
+        // within a chunk of kScaleCols source columns, 16 at the least
+        sd.na = kScaleTile, sd.nb = kScaleTile;
+        while (sd.nb > 16 && int64_t(sd.nb) * sd.cb > int64_t(kScaleCols) * sd.ob) sd.nb /= 2;
+    } else {
+        sd.ca = ch, sd.oa = d.out_h, sd.ma = d.m[3], sd.ta = d.t[1];
+        sd.cb = cw, sd.ob = d.out_w, sd.mb = d.m[0], sd.tb = d.t[0];
+        // as many columns as fill a chunk of kScaleCols source columns, 64 at ratios from 4 up
+        sd.na = kScaleRowsA;
+        sd.nb = 64;
+        while (sd.nb < 256 && int64_t(2 * sd.nb) * sd.cb <= int64_t(kScaleCols) * sd.ob) sd.nb *= 2;
+    }
+    for (sd.nb_log2 = 4; (1 << sd.nb_log2) < sd.nb;) ++sd.nb_log2;
+    sd.den = 2 * uint64_t(cw) * uint64_t(ch);
+    sd.inv_den = 1.0 / double(sd.den);
+    d.tiles_x = (sd.ob + sd.nb - 1) / sd.nb;
+    d.tiles = d.tiles_x * ((sd.oa + sd.na - 1) / sd.na);
+    return HEIFGPU_OK;
+}
+
 int heifgpu_render_batch_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
                                 const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
                                 const heifgpu_scale *scale, const heifgpu_surface *out, void *stream) {
@@ -674,48 +730,9 @@ int heifgpu_render_batch_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *im
     std::vector<ScaleDesc> descs(n);
     int bps = 0, max_tiles = 0;
     for (size_t i = 0; i < n; ++i) {
-        if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
-        DisplayMap dm = imgs[i]->img.display;
-        const heifgpu_scale &sc = scale[i];
-        if (!sc.out_width || !sc.out_height || sc.out_width > 65535 || sc.out_height > 65535)
-            return fail(HEIFGPU_E_INVALID, "rendered size outside 1..65535");
-        if (sc.width || sc.height) {
-            if (!sc.width || !sc.height || sc.x >= dm.out_width || sc.y >= dm.out_height ||
-                sc.width > dm.out_width - sc.x || sc.height > dm.out_height - sc.y)
-                return fail(HEIFGPU_E_INVALID, "window empty or outside the displayed picture");
-            display_window(dm, sc.x, sc.y, sc.width, sc.height);
-        }
-        if (dm.out_width > 65535 || dm.out_height > 65535)
-            return fail(HEIFGPU_E_UNSUPPORTED, "window side above 65535");  // (the 32-bit line sums of the kernel)
-        ScaleDesc &sd = descs[i];
-        sd = ScaleDesc{};
-        RenderDesc &d = sd.r;
-        if (int rc = render_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, out, dm, sc.out_width, sc.out_height,
-                                      bps, d))
+        if (int rc = scale_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, scale[i], 0, out, bps, descs[i]))
             return rc;
-        // the source's axes: a runs along its y, b along its x (kernels.hpp)
-        const int32_t cw = int32_t(dm.out_width), ch = int32_t(dm.out_height);
-        if (d.swap) {
-            sd.ca = cw, sd.oa = d.out_w, sd.ma = d.m[2], sd.ta = d.t[1];
-            sd.cb = ch, sd.ob = d.out_h, sd.mb = d.m[1], sd.tb = d.t[0];
-            // 64 pixels along the output's x (store_row); along its y as many as keep the footprint
-            // within a chunk of kScaleCols source columns, 16 at the least
-            sd.na = kScaleTile, sd.nb = kScaleTile;
-            while (sd.nb > 16 && int64_t(sd.nb) * sd.cb > int64_t(kScaleCols) * sd.ob) sd.nb /= 2;
-        } else {
-            sd.ca = ch, sd.oa = d.out_h, sd.ma = d.m[3], sd.ta = d.t[1];
-            sd.cb = cw, sd.ob = d.out_w, sd.mb = d.m[0], sd.tb = d.t[0];
-            // as many columns as fill a chunk of kScaleCols source columns, 64 at ratios from 4 up
-            sd.na = kScaleRowsA;
-            sd.nb = 64;
-            while (sd.nb < 256 && int64_t(2 * sd.nb) * sd.cb <= int64_t(kScaleCols) * sd.ob) sd.nb *= 2;
-        }
-        for (sd.nb_log2 = 4; (1 << sd.nb_log2) < sd.nb;) ++sd.nb_log2;
-        sd.den = 2 * uint64_t(cw) * uint64_t(ch);
-        sd.inv_den = 1.0 / double(sd.den);
-        d.tiles_x = (sd.ob + sd.nb - 1) / sd.nb;
-        d.tiles = d.tiles_x * ((sd.oa + sd.na - 1) / sd.na);
-        max_tiles = std::max(max_tiles, d.tiles);
+        max_tiles = std::max(max_tiles, descs[i].r.tiles);
     }
     if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -728,6 +745,64 @@ int heifgpu_render_batch_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *im
     std::memcpy(sl.host.p, descs.data(), bytes);
     HIP_TRY(hipMemcpyAsync(sl.sdev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(launch_render_scaled(sl.sdev.p, int(n), max_tiles, int(format), bps, s));  // the one launch
+    HIP_TRY(hipEventRecord(sl.done, s));
+    sl.pending = true;
+    return HEIFGPU_OK;
+}
+
+int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                                const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in,
+                                const heifgpu_tensor_format *fmt, const heifgpu_scale *scale, const uint32_t *flip,
+                                const heifgpu_tensor_surface *out, void *stream) {
+    // (the context is looked at last, as in heifgpu_render_batch_scaled)
+    if (!imgs || !in || !fmt || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (fmt->src > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "source format");
+    if (fmt->elem > HEIFGPU_ELEM_BF16) return fail(HEIFGPU_E_INVALID, "element type");
+    if (fmt->layout > HEIFGPU_LAYOUT_HWC) return fail(HEIFGPU_E_INVALID, "layout");
+    const int nch = (fmt->src & 1) ? 4 : 3;
+    for (int c = 0; c < nch; ++c)
+        if (!std::isfinite(fmt->a[c]) || !std::isfinite(fmt->b[c]))
+            return fail(HEIFGPU_E_INVALID, "scale or bias not finite");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    const int64_t esz = fmt->elem == HEIFGPU_ELEM_F32 ? 4 : 2;
+    std::vector<TensorDesc> descs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t fl = flip ? flip[i] : 0;
+        if (fl > 3) return fail(HEIFGPU_E_INVALID, "flip above 3");
+        TensorDesc &td = descs[i];
+        if (int rc = scale_desc_fill(i, imgs, in, alpha_imgs, alpha_in, fmt->src, scale[i], fl, nullptr, bps, td.s))
+            return rc;
+        const heifgpu_tensor_surface &o = out[i];
+        if (!o.data || (reinterpret_cast<uintptr_t>(o.data) & uintptr_t(esz - 1)))
+            return fail(HEIFGPU_E_INVALID, "tensor data null or not aligned to its element");
+        const int64_t row = int64_t(td.s.r.out_w) * esz * (fmt->layout == HEIFGPU_LAYOUT_HWC ? nch : 1);
+        if (o.stride_y < row || (o.stride_y & (esz - 1)))
+            return fail(HEIFGPU_E_INVALID, "stride_y below the row or not a multiple of the element size");
+        if (fmt->layout == HEIFGPU_LAYOUT_CHW && (o.stride_c & (esz - 1)))
+            return fail(HEIFGPU_E_INVALID, "stride_c not a multiple of the element size");
+        td.s.r.out = reinterpret_cast<uint64_t>(o.data);
+        td.stride_c = fmt->layout == HEIFGPU_LAYOUT_CHW ? o.stride_c : 0;
+        td.stride_y = o.stride_y;
+        td.elem = int32_t(fmt->elem);
+        td.layout = int32_t(fmt->layout);
+        for (int c = 0; c < 4; ++c) {
+            td.a[c] = c < nch ? fmt->a[c] : 0.f;
+            td.b[c] = c < nch ? fmt->b[c] : 0.f;
+        }
+        max_tiles = std::max(max_tiles, td.s.r.tiles);
+    }
+    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RenderRing::Slot *slot = nullptr;
+    if (int rc = render_ring_slot(ctx, &slot)) return rc;
+    RenderRing::Slot &sl = *slot;
+    const size_t bytes = n * sizeof(TensorDesc);
+    HIP_TRY(sl.host.reserve(bytes));
+    HIP_TRY(sl.tdev.alloc(n));
+    std::memcpy(sl.host.p, descs.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(sl.tdev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_render_tensor(sl.tdev.p, int(n), max_tiles, int(fmt->src), bps, s));  // the one launch
     HIP_TRY(hipEventRecord(sl.done, s));
     sl.pending = true;
     return HEIFGPU_OK;

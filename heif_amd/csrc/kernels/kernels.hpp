@@ -178,6 +178,19 @@ struct ScaleDesc {
     double inv_den;      // 1 / den (the quotient's estimate; corrected exactly)
 };
 
+// k_render_scaled's tensor epilogue (heifgpu_render_batch_tensor): the same descriptor
+// (s.r.out is the tensor's base, s.r.out_pitch is unused) and where every element goes:
+// out = round_to_elem(fadd(fmul(float(R), a[c]), b[c])), element (c, Y, X) at
+// out + c * stride_c + Y * stride_y + X * size (CHW) or out + Y * stride_y + (X * C + c) * size (HWC).
+enum : int { TENSOR_F32 = 0, TENSOR_F16 = 1, TENSOR_BF16 = 2 };
+enum : int { TENSOR_CHW = 0, TENSOR_HWC = 1 };
+struct TensorDesc {
+    ScaleDesc s;
+    int64_t stride_c, stride_y;  // bytes, multiples of the element size
+    int32_t elem, layout;
+    float a[4], b[4];
+};
+
 // parse modes (BatchArgs::parse_mode; heifgpu_batch_opts::parse_mode)
 // (4 was r05's row waves, HEIFGPU_PARSE_ROWS: removed in ABI 6, prepare answers HEIFGPU_E_UNSUPPORTED)
 enum : int { PARSE_AUTO = 0, PARSE_LANES = 1, PARSE_SOLO = 2, PARSE_SPREAD = 3 };
@@ -254,6 +267,8 @@ hipError_t launch_gather_tiles(const GatherArgs &g, hipStream_t s);
 hipError_t launch_render(const RenderDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
                          hipStream_t s);
 hipError_t launch_render_scaled(const ScaleDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                                hipStream_t s);
+hipError_t launch_render_tensor(const TensorDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
                                 hipStream_t s);
 hipError_t launch_parse(const BatchArgs &a, hipStream_t s);
 hipError_t launch_transform(const BatchArgs &a, hipStream_t s);

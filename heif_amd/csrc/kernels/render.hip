@@ -30,7 +30,11 @@
 //
 // k_render_scaled (heifgpu_render_batch_scaled), further down, writes the exact
 // area average of a window of the same picture onto another grid; it shares
-// convert()'s arithmetic and store_row.
+// convert()'s arithmetic and store_row.  With a TensorDesc the same kernel ends in
+// store_tensor instead (heifgpu_render_batch_tensor): the same integers, scaled
+// and biased per channel, as f32 / f16 / bf16, planar or interleaved.
+#include <type_traits>
+
 #include "kernels.hpp"
 
 namespace hg {
@@ -329,14 +333,118 @@ __device__ __forceinline__ void scale_columns(const ScaleDesc &s, int x0, int x1
     }
 }
 
-template <typename Pel, int FMT>
-__global__ void __launch_bounds__(256) k_render_scaled(const ScaleDesc *descs) {
+// ---- the tensor epilogue (heifgpu_render_batch_tensor) ------------------------
+// F = fadd_rn(fmul_rn(float(R), a[c]), b[c]) in binary32, then rounded to the
+// element type.  Two roundings: the pair must not become a fused multiply-add.
+// __fmul_rn / __fadd_rn would not keep it apart: they are a plain product and sum
+// in the header, compiled under -ffp-contract=fast, and the compiler fuses them.
+// The product and the sum are written out here under a pragma that takes
+// the contraction flag off both, so nothing later can fuse them.  f16 is the hardware's
+// round-to-nearest-even conversion with gradual underflow (the f16 denormal mode
+// is on by default), bf16 round-to-nearest-even on the bits (the inputs are finite).
+__device__ __forceinline__ uint32_t tensor_elem(uint32_t level, float a, float b, int elem) {
+#pragma clang fp contract(off)
+    const float m = (float)level * a;
+    const float f = m + b;
+    const uint32_t u = __float_as_uint(f);
+    if (elem == TENSOR_F32) return u;
+    if (elem == TENSOR_F16) return (uint32_t) __builtin_bit_cast(uint16_t, (_Float16)f);
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+template <int FMT>
+__device__ __forceinline__ uint32_t px_channel(Px p, int c) {
+    if (FMT >= RENDER_RGB16) return (((c & 2) ? p.hi : p.lo) >> (16 * (c & 1))) & 0xffffu;
+    return (p.lo >> (8 * c)) & 0xffu;
+}
+
+// v[c] for a c that differs between lanes (selects, not an indexed array: no scratch)
+__device__ __forceinline__ float pick4(const float (&v)[4], int c) {
+    return c == 0 ? v[0] : c == 1 ? v[1] : c == 2 ? v[2] : v[3];
+}
+
+// One wave stores pixels oxw .. oxw + 63 (oxw a multiple of 64) of output row oy; every
+// lane of the wave calls it.  px(i) reads pixel oxw + i of that row from the result
+// tile in LDS, for any i below the row's end (not only the lane's own), which is how
+// the interleaved layout gets whole dwords without an exchange between lanes:
+// - CHW: per channel 64 consecutive elements of one plane row.  f32 is a dword per
+//   lane; f16 / bf16 pack two pixels into a dword through the right neighbour, even
+//   lanes store (single elements where the plane row is not 4-byte aligned and for a
+//   ragged last pixel);
+// - HWC: the segment is 64 * C consecutive elements, written as consecutive dwords,
+//   lane l taking dwords l, 64 + l, ...: it converts the one or two elements of its
+//   dword, whichever pixels they belong to.  Lanes that read the same pixel read the
+//   same LDS word (a broadcast), neighbours read neighbouring pixels, so the tile's
+//   pitch (1 or 65 dwords per pixel) keeps the banks apart as in store_row's read.
+//   Single elements per pixel where the row is not 4-byte aligned, and for an odd last one.
+template <int FMT, typename Load>
+__device__ __forceinline__ void store_tensor(const TensorDesc &td, int oy, int oxw, int lane, Load px) {
+    constexpr int C = (FMT & 1) ? 4 : 3;
+    const RenderDesc &d = td.s.r;
+    const int elem = td.elem;
+    const int nv = min(64, d.out_w - oxw);  // the segment's pixels (at least 1)
+    uint8_t *row = reinterpret_cast<uint8_t *>(d.out) + (int64_t)oy * td.stride_y;
+    if (td.layout == TENSOR_CHW) {
+        const bool valid = lane < nv;
+        const Px p = valid ? px(lane) : Px{0, 0};
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const uint32_t e = tensor_elem(px_channel<FMT>(p, c), td.a[c], td.b[c], elem);
+            uint8_t *pl = row + (int64_t)c * td.stride_c;
+            if (elem == TENSOR_F32) {
+                if (valid) reinterpret_cast<uint32_t *>(pl)[oxw + lane] = e;
+            } else {
+                const uint32_t nxt = __shfl_down(e, 1);
+                if (!(reinterpret_cast<uintptr_t>(pl) & 3) && (lane | 1) < nv) {
+                    if (!(lane & 1)) reinterpret_cast<uint32_t *>(pl)[(oxw + lane) >> 1] = e | (nxt << 16);
+                } else if (valid) {
+                    reinterpret_cast<uint16_t *>(pl)[oxw + lane] = (uint16_t)e;
+                }
+            }
+        }
+        return;
+    }
+    const int ne = nv * C;  // the segment's elements
+    auto element = [&](int k) {  // element k of the segment
+        const int i = k / C, c = k - i * C;
+        return tensor_elem(px_channel<FMT>(px(i), c), pick4(td.a, c), pick4(td.b, c), elem);
+    };
+    if (elem == TENSOR_F32) {
+        uint32_t *seg = reinterpret_cast<uint32_t *>(row) + (size_t)oxw * C;
+#pragma unroll
+        for (int j = 0; j < C; ++j) {
+            const int k = j * 64 + lane;
+            if (k < ne) seg[k] = element(k);
+        }
+    } else if (!(reinterpret_cast<uintptr_t>(row) & 3)) {  // (64 pixels are a multiple of 4 bytes)
+        uint16_t *seg = reinterpret_cast<uint16_t *>(row) + (size_t)oxw * C;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {  // 32 * C dwords
+            const int k = 2 * (j * 64 + lane);
+            if (k + 1 < ne) reinterpret_cast<uint32_t *>(seg)[k >> 1] = element(k) | (element(k + 1) << 16);
+            else if (k < ne) seg[k] = (uint16_t)element(k);
+        }
+    } else if (lane < nv) {
+        uint16_t *o = reinterpret_cast<uint16_t *>(row) + (size_t)(oxw + lane) * C;
+        const Px p = px(lane);
+#pragma unroll
+        for (int c = 0; c < C; ++c) o[c] = (uint16_t)tensor_elem(px_channel<FMT>(p, c), td.a[c], td.b[c], elem);
+    }
+}
+
+__device__ __forceinline__ const ScaleDesc &scale_of(const ScaleDesc &s) { return s; }
+__device__ __forceinline__ const ScaleDesc &scale_of(const TensorDesc &t) { return t.s; }
+
+template <typename Pel, int FMT, typename Desc>
+__global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
+    constexpr bool TENSOR = std::is_same<Desc, TensorDesc>::value;  // (else ScaleDesc: the integer surfaces)
     constexpr bool WIDE = FMT >= RENDER_RGB16;
     constexpr int NCH = (FMT & 1) ? 4 : 3;
     constexpr int RES = kScaleTile * (kScaleTile + 1);  // dwords: 64 lines of pitch 65 (>= 8 lines of pitch 256)
     __shared__ uint32_t colsum[4 * kScaleCols];
     __shared__ uint32_t res[(WIDE ? 2 : 1) * RES];
-    const ScaleDesc s = descs[blockIdx.y];
+    const Desc dd = descs[blockIdx.y];
+    const ScaleDesc &s = scale_of(dd);
     const RenderDesc &d = s.r;
     if ((int)blockIdx.x >= d.tiles) return;  // (a smaller image of the batch: the whole workgroup leaves)
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -414,40 +522,65 @@ __global__ void __launch_bounds__(256) k_render_scaled(const ScaleDesc *descs) {
         for (int u = wave; u < (a1 - a0) * segs; u += 4) {
             const int al = u / segs, oxw = b0 + (u % segs) * 64;
             if (oxw >= d.out_w) continue;
-            const bool valid = oxw + lane < d.out_w;
-            Px p = none;
-            if (valid) {
-                p.lo = res[al * lp + (oxw - b0) + lane];
-                if (WIDE) p.hi = res[RES + al * lp + (oxw - b0) + lane];
+            const uint32_t *line = res + al * lp + (oxw - b0);
+            if constexpr (TENSOR) {
+                store_tensor<FMT>(dd, a0 + al, oxw, lane, [&](int i) {
+                    return Px{line[i], WIDE ? line[RES + i] : 0u};
+                });
+            } else {
+                const bool valid = oxw + lane < d.out_w;
+                Px p = none;
+                if (valid) {
+                    p.lo = line[lane];
+                    if (WIDE) p.hi = line[RES + lane];
+                }
+                store_row<FMT>(d, a0 + al, oxw, lane, p, valid);
             }
-            store_row<FMT>(d, a0 + al, oxw, lane, p, valid);
         }
     } else {
         const bool valid = a0 + lane < d.out_w;
         for (int oy = b0 + wave; oy < b1; oy += 4) {
-            Px p = none;
-            if (valid) {
-                p.lo = res[lane * lp + (oy - b0)];
-                if (WIDE) p.hi = res[RES + lane * lp + (oy - b0)];
+            const uint32_t *col = res + (oy - b0);
+            if constexpr (TENSOR) {
+                store_tensor<FMT>(dd, oy, a0, lane, [&](int i) {
+                    return Px{col[i * lp], WIDE ? col[RES + i * lp] : 0u};
+                });
+            } else {
+                Px p = none;
+                if (valid) {
+                    p.lo = col[lane * lp];
+                    if (WIDE) p.hi = col[RES + lane * lp];
+                }
+                store_row<FMT>(d, oy, a0, lane, p, valid);
             }
-            store_row<FMT>(d, oy, a0, lane, p, valid);
         }
     }
 }
 
-template <typename Pel>
-void launch_scaled_fmt(const ScaleDesc *descs, dim3 grid, int format, hipStream_t s) {
+// Desc = ScaleDesc: the integer surfaces; TensorDesc: the tensor epilogue (element type
+// and layout are uniform branches in store_tensor, so the heavy body is compiled once
+// per sample width and source format for each of the two)
+template <typename Pel, typename Desc>
+void launch_scaled_fmt(const Desc *descs, dim3 grid, int format, hipStream_t s) {
     switch (format) {
-    case RENDER_RGB8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB8>), grid, dim3(256), 0, s, descs); break;
-    case RENDER_RGBA8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA8>), grid, dim3(256), 0, s, descs); break;
-    case RENDER_RGB16: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB16>), grid, dim3(256), 0, s, descs); break;
-    default: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA16>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGB8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB8, Desc>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGBA8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA8, Desc>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGB16: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB16, Desc>), grid, dim3(256), 0, s, descs); break;
+    default: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA16, Desc>), grid, dim3(256), 0, s, descs); break;
     }
 }
 
 }  // namespace
 
 hipError_t launch_render_scaled(const ScaleDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                                hipStream_t s) {
+    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
+    if (bytes_per_sample == 1) launch_scaled_fmt<uint8_t>(descs, grid, format, s);
+    else launch_scaled_fmt<uint16_t>(descs, grid, format, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_render_tensor(const TensorDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
                                 hipStream_t s) {
     const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
     if (bytes_per_sample == 1) launch_scaled_fmt<uint8_t>(descs, grid, format, s);

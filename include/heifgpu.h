@@ -352,6 +352,59 @@ int heifgpu_render_batch_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *im
                                 uint32_t format, const heifgpu_scale *scale,
                                 const heifgpu_surface *out, void *stream);
 
+/* ---- tensor render: crop, flip, normalise to f32 / f16 / bf16 ---------------
+ * (added within ABI 6: new entry points only.)
+ * Let R be exactly what heifgpu_render_batch_scaled writes for an image, a
+ * heifgpu_scale and the pixel format `src` (one of HEIFGPU_PIX_*): integers,
+ * C = 3 or 4 channels, oh x ow.  The tensor render writes, for every channel c,
+ *     Rf         = R, columns reversed if flip & 1, rows reversed if flip & 2
+ *                  (the flip acts on the rendered picture)
+ *     F[Y][X][c] = fadd_rn(fmul_rn((float)Rf[Y][X][c], a[c]), b[c])
+ *                  (binary32, two roundings, never a fused multiply-add)
+ *     out        = F rounded to the element type: binary32 as is; binary16 and
+ *                  bfloat16 by round-to-nearest-even, gradual underflow for
+ *                  binary16, overflow to infinity
+ * so float32 arithmetic on the host (numpy) reproduces it bit for bit.  a[c] and
+ * b[c] are the caller's; the C used must be finite.  A value whose binary32
+ * intermediate (the product or the sum) is subnormal is outside the contract.
+ * A normaliser passes a = 1 / (maxv * std), b = -mean / std, maxv = 255 or
+ * (1 << B) - 1; with a 16-bit src the images of one call share a and b whatever
+ * their bit depths are, which is the caller's concern.
+ * HEIFGPU_LAYOUT_CHW puts element (c, Y, X) at data + c*stride_c + Y*stride_y +
+ * X*size, HEIFGPU_LAYOUT_HWC at data + Y*stride_y + (X*C + c)*size (size = 4 or
+ * 2 bytes; strides in bytes, so n images can be the slices of one (N, C, h, w)
+ * or (N, h, w, C) tensor).  Overlapping planes are the caller's business.
+ * flip[i] is 0..3 (flip NULL: none); it is folded into the image's display map
+ * behind the window, as one more 'imir'.
+ * Everything not named here is as in heifgpu_render_batch_scaled: alpha rules,
+ * mixed sizes, orientations and chroma formats, n <= 65535, the descriptor ring
+ * shared with it, one descriptor copy and ONE kernel launch whatever n, the
+ * sizes and the flips are (the same kernel, ending in another store).  All its
+ * checks apply and, like them, run before anything is launched and before ctx
+ * is looked at; HEIFGPU_E_INVALID besides for an unknown src, elem or layout, a
+ * flip above 3, a non-finite a or b among the C used, data NULL or not aligned
+ * to the element size, a stride_y below the row or not a multiple of the element
+ * size and, for CHW, a stride_c not a multiple of the element size.
+ * There is no full-size fast path: a full-size tensor is the identity window
+ * through this kernel, exact but slower than heifgpu_render_batch (which has
+ * no tensor store). */
+enum { HEIFGPU_ELEM_F32 = 0, HEIFGPU_ELEM_F16 = 1, HEIFGPU_ELEM_BF16 = 2 };
+enum { HEIFGPU_LAYOUT_CHW = 0, HEIFGPU_LAYOUT_HWC = 1 };
+typedef struct {
+    uint32_t src, elem, layout;       /* HEIFGPU_PIX_*, HEIFGPU_ELEM_*, HEIFGPU_LAYOUT_* */
+    float a[4], b[4];                 /* per channel; the first C are used */
+} heifgpu_tensor_format;
+typedef struct {
+    void *data;                       /* device, caller-owned */
+    int64_t stride_c, stride_y;       /* bytes; stride_c is unused for HWC */
+} heifgpu_tensor_surface;
+int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                const heifgpu_planes *in,
+                                const heifgpu_image *const *alpha_imgs,
+                                const heifgpu_planes *alpha_in,
+                                const heifgpu_tensor_format *fmt, const heifgpu_scale *scale,
+                                const uint32_t *flip, const heifgpu_tensor_surface *out, void *stream);
+
 /* ---- host test hooks (reference unit-test surface) -------------------- */
 size_t heifgpu_remove_emulation_prevention(const uint8_t *in, size_t n, uint8_t *out); /* rbsp_reader.rs:11-39 */
 int heifgpu_read_ue(const uint8_t *buf, size_t n, uint32_t *val);                      /* rbsp_reader.rs:87-99 */

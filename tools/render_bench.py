@@ -26,7 +26,21 @@ GB/s over algorithmic bytes: 1.5 read per source pixel of the window plus the
 output bytes.  The condition of 5.17: cover512 and cover224 no slower than
 `full` at the same rotation beyond the measured spread (max - min over runs).
 
-usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json] [--scaled]
+--tensor measures the tensor render (heifgpu_render_batch_tensor),
+same images, COVER to 224 x 224, rotation 0 and 3, half of the batch flipped,
+the variants alternated in one process in each of the --runs runs:
+  scaled       heifgpu_render_batch_scaled RGB8 (the integers, as before it)
+  scaled_torch `scaled`, then what a caller wrote before it: permute, float, / 255,
+               - mean, / std, half, and the flip of half the batch (to f16 NCHW)
+  f16_chw      heifgpu_render_batch_tensor, f16 CHW, the same flips: one launch
+  f32_chw      the same to f32 CHW
+  bf16_hwc     the same to bf16 HWC
+The condition of 5.19: f16_chw faster than scaled_torch by more than the larger
+spread (max - min over runs) of the two; f16_chw - scaled is reported.  Before
+timing, f16_chw is compared bit for bit with float32(R) * a + b of `scaled`'s
+integers computed by torch (a product, then a sum), at the size timed.
+
+usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json] [--scaled | --tensor]
 """
 import argparse
 import ctypes
@@ -163,6 +177,115 @@ def scaled_main(args):
         pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
 
 
+def tensor_main(args):
+    n = args.images
+    dev = torch.device("cuda", 0)
+    ctx = H.DecodeContext(0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    golden = (ROOT / "tests" / "golden" / "halfmoonbay.heic").read_bytes()
+    g = torch.Generator(device=dev).manual_seed(1)
+    ys = [torch.randint(0, 256, (HGT, W), generator=g, device=dev, dtype=torch.int32).to(torch.uint8) for _ in range(n)]
+    cs = [[torch.randint(0, 256, (HGT // 2, W // 2), generator=g, device=dev, dtype=torch.int32).to(torch.uint8)
+           for _ in range(n)] for _ in range(2)]
+    planes = (_lib.Planes * n)()
+    for i in range(n):
+        for c, t in enumerate((ys[i], cs[0][i], cs[1][i])):
+            planes[i].plane[c] = t.data_ptr()
+            planes[i].pitch[c] = t.stride(0) * t.element_size()
+    mean, std = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+    a = torch.tensor([1.0 / (255.0 * v) for v in std], dtype=torch.float64).float().to(dev)
+    b = torch.tensor([-m / v for m, v in zip(mean, std)], dtype=torch.float64).float().to(dev)
+    mean_t, std_t = torch.tensor(mean, device=dev).view(1, 3, 1, 1), torch.tensor(std, device=dev).view(1, 3, 1, 1)
+    flips = [i & 1 for i in range(n)]  # half of the batch mirrored
+    flip_idx = torch.tensor([i for i in range(n) if flips[i]], device=dev)
+    flip_arr = (ctypes.c_uint32 * n)(*flips)
+    bw = bh = 224
+    result = {"images": n, "width": W, "height": HGT, "box": [bh, bw], "reps": args.reps, "runs": args.runs,
+              "device": torch.cuda.get_device_name(0), "tensor": {}}
+    for rot in (0, 3):
+        img = H.HeifImage.parse(forced_rotation(golden, rot))
+        d = img.display
+        imgs = (ctypes.c_void_p * n)(*[img._h.value] * n)
+        sc = (_lib.Scale * n)()
+        for i in range(n):
+            _lib.check(_lib.lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_COVER, ctypes.byref(sc[i])))
+        ints = torch.empty((n, bh, bw, 3), dtype=torch.uint8, device=dev)
+        surf = (_lib.Surface * n)()
+        for i in range(n):
+            surf[i].pixels, surf[i].pitch = ints[i].data_ptr(), ints[i].stride(0)
+
+        def scaled():
+            _lib.check(_lib.lib.heifgpu_render_batch_scaled(ctx._h, imgs, n, planes, None, None, _lib.PIX_RGB8, sc, surf,
+                                                            stream))
+
+        keep = {}
+
+        def scaled_torch():
+            scaled()
+            x = ints.permute(0, 3, 1, 2).float().div(255).sub(mean_t).div(std_t).half()
+            x[flip_idx] = x[flip_idx].flip(-1)
+            keep["x"] = x
+
+        def tensor_variant(dtype, elem, layout):
+            chw = layout == _lib.LAYOUT_CHW
+            out = torch.empty((n, 3, bh, bw) if chw else (n, bh, bw, 3), dtype=dtype, device=dev)
+            fmt = _lib.TensorFormat(src=_lib.PIX_RGB8, elem=elem, layout=layout)
+            for c in range(3):
+                fmt.a[c], fmt.b[c] = float(a[c]), float(b[c])
+            ts = (_lib.TensorSurface * n)()
+            for i in range(n):
+                ts[i].data = out[i].data_ptr()
+                ts[i].stride_c = out[i].stride(0) * out.element_size() if chw else 0
+                ts[i].stride_y = out[i].stride(1 if chw else 0) * out.element_size()
+
+            def run():
+                _lib.check(_lib.lib.heifgpu_render_batch_tensor(ctx._h, imgs, n, planes, None, None, ctypes.byref(fmt), sc,
+                                                                flip_arr, ts, stream))
+            return run, out
+
+        f16_chw, out16 = tensor_variant(torch.float16, _lib.ELEM_F16, _lib.LAYOUT_CHW)
+        f32_chw, out32 = tensor_variant(torch.float32, _lib.ELEM_F32, _lib.LAYOUT_CHW)
+        bf16_hwc, outbf = tensor_variant(torch.bfloat16, _lib.ELEM_BF16, _lib.LAYOUT_HWC)
+        variants = (("scaled", scaled), ("scaled_torch", scaled_torch), ("f16_chw", f16_chw), ("f32_chw", f32_chw),
+                    ("bf16_hwc", bf16_hwc))
+        for _, fn in variants:  # warm-up
+            fn()
+        torch.cuda.synchronize()
+        # the results at the size timed: the definition over `scaled`'s integers, by torch (a product, then a sum)
+        want = ints.permute(0, 3, 1, 2).float() * a.view(1, 3, 1, 1) + b.view(1, 3, 1, 1)
+        want[flip_idx] = want[flip_idx].flip(-1)
+        assert torch.equal(out32, want), "f32_chw differs from float32(R) * a + b"
+        assert torch.equal(out16.view(torch.int16), want.half().view(torch.int16)), "f16_chw differs"
+        assert torch.equal(outbf.view(torch.int16), want.permute(0, 2, 3, 1).bfloat16().view(torch.int16)), "bf16_hwc differs"
+        route_diff = float((keep["x"].float() - out16.float()).abs().max())  # the float route rounds in another order
+        ms = {name: [] for name, _ in variants}
+        for _ in range(args.runs):
+            for name, fn in variants:
+                ms[name].append(timed(fn, args.reps))
+        r = {}
+        for name, _ in variants:
+            v = ms[name]
+            r[name] = {"ms_per_batch": round(statistics.median(v), 4), "ms_min": round(min(v), 4),
+                       "ms_max": round(max(v), 4), "ms_runs": [round(x, 4) for x in v],
+                       "spread_ms": round(max(v) - min(v), 4)}
+        pair = max(r["f16_chw"]["spread_ms"], r["scaled_torch"]["spread_ms"])
+        r["f16_chw"]["scaled_torch_minus_it_ms"] = round(r["scaled_torch"]["ms_per_batch"] - r["f16_chw"]["ms_per_batch"], 4)
+        r["f16_chw"]["faster_than_scaled_torch_beyond_spread"] = bool(
+            r["scaled_torch"]["ms_per_batch"] - r["f16_chw"]["ms_per_batch"] > pair)
+        for name in ("f16_chw", "f32_chw", "bf16_hwc"):
+            r[name]["minus_scaled_ms"] = round(r[name]["ms_per_batch"] - r["scaled"]["ms_per_batch"], 4)
+        r["f16_chw"]["max_abs_diff_vs_scaled_torch"] = round(route_diff, 6)
+        result["tensor"][f"rotation_{rot}"] = r
+        print(f"rotation {rot}: " + ", ".join(f"{name} {r[name]['ms_per_batch']:.3f} ms (spread {r[name]['spread_ms']:.3f})"
+                                              for name, _ in variants), flush=True)
+        del ints, out16, out32, outbf, want, keep
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=128)
@@ -170,9 +293,12 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default="")
     ap.add_argument("--scaled", action="store_true", help="measure heifgpu_render_batch_scaled (see above)")
+    ap.add_argument("--tensor", action="store_true", help="measure heifgpu_render_batch_tensor (see above)")
     args = ap.parse_args()
     if args.scaled:
         return scaled_main(args)
+    if args.tensor:
+        return tensor_main(args)
     n = args.images
     dev = torch.device("cuda", 0)
     ctx = H.DecodeContext(0)
