@@ -305,10 +305,26 @@ enum Cov : int {
     COV_CU_ENDS_IN_SB,                // a CU's last TB ending in a sub-block (not in U_TB)
     COV_TSKIP,                        // transform_skip_flag = 1
     COV_LAST_CTX5,                    // a last_sig_coeff prefix of 9 (32x32 luma: its fifth context)
-    COV_N
+    COV_N,
+    // the sub-block unit's paths (tests/lanes_sb_cases.py), on a `sb_paths` line of their own
+    COV_SB_SIG4 = COV_N,  // sub-blocks of 4x4 TBs through the sig_coeff_flag loop (nine context slots)
+    COV_SB_SIG,           // and of larger TBs (four slots)
+    COV_SB_BEYOND8,       // more than eight significant coefficients
+    COV_SB_RICE4,         // a remainder decoded with Rice parameter 4
+    COV_SB_ESCAPE,        // an escape level (abs - 1 >= 15)
+    COV_SB_EGK,           // a remainder with the EG(k + 1) suffix
+    COV_SB_HIDE,          // a hidden sign
+    COV_SB_NO_HIDE,       // sign hiding enabled, but first and last too close
+    COV_SB_CTXSET_INC,    // ctxSet raised by rc_prev_c1 == 0
+    COV_SB_INFER_DC,      // the DC inferred in a coded sub-block
+    COV_SB_LAST_POS0,     // a last sub-block with last_pos 0 (no sig_coeff_flag decoded)
+    COV_SB_GT2,           // coeff_abs_level_greater2_flag set
+    COV_SB_RUN_ANY4,      // unit runs of a wave with a 4x4 TB's lane among them
+    COV_SB_RUN_NO4,       // and without one
+    COV_ALL
 };
 #if defined(HG_HOST_EMU)
-long g_cov[COV_N];
+long g_cov[COV_ALL];
 #define HG_COV(i) (++g_cov[i])
 #else
 #define HG_COV(i) ((void)0)
@@ -1999,12 +2015,39 @@ HG_HD inline uint64_t spread16_nib(uint32_t m) {
     return x;
 }
 
-// the sub-block's record (SbRec): one 16-byte store (4 coefficient words); the
-// first escape of the record is the escape slot at L.nesc when it started
+// the vector engines' sub-block unit (the greater1 context selector,
+// the remainder phase's carried Rice parameter and in-place nibble update, the
+// record's nibble spread and escape slot); the scalar engines keep their code
+template <class EG>
+constexpr bool kSbVec = !EG::kSolo;
+
+// (vector engines) the same in 32-bit halves, eight positions each: the record
+// stores the nibbles as two dwords anyway, and a step is a shift-or and a mask
+// where the 64-bit ladder takes a 64-bit shift, two ORs and two masks
+HG_HD inline uint64_t spread16_nib_halves(uint32_t m) {
+    auto half = [](uint32_t x) {
+        x = (x | (x << 12)) & 0x000f000fu;
+        x = (x | (x << 6)) & 0x03030303u;
+        x = (x | (x << 3)) & 0x11111111u;
+        return x;
+    };
+    return (uint64_t)half(m & 0xffu) | ((uint64_t)half((m >> 8) & 0xffu) << 32);
+}
+
+// (nesc0, vector engines: L.nesc when the sub-block started; every nibble of 15
+// is an escape that the remainder loop counted into L.nesc, so the scalar
+// engines' count of those nibbles is L.nesc - nesc0)
 template <class EG, class L_, class P_>
-HG_HD inline void sb_store(L_ &L, const P_ &P, uint32_t sig, uint32_t signs, uint64_t nib, int xS, int yS, bool hide) {
-    const uint32_t nesc_sb = (uint32_t)__builtin_popcountll(nib & (nib >> 1) & (nib >> 2) & (nib >> 3) & 0x1111111111111111ull);
-    const uint32_t esc0 = P.coef_cap - 1 - (L.nesc - nesc_sb);  // row-relative index of its first escape
+HG_HD inline void sb_store(L_ &L, const P_ &P, uint32_t sig, uint32_t signs, uint64_t nib, int xS, int yS, bool hide,
+                           uint32_t nesc0) {
+    uint32_t esc0;  // row-relative index of its first escape
+    if constexpr (kSbVec<EG>) {
+        esc0 = P.coef_cap - 1 - nesc0;
+    } else {
+        const uint32_t nesc_sb =
+            (uint32_t)__builtin_popcountll(nib & (nib >> 1) & (nib >> 2) & (nib >> 3) & 0x1111111111111111ull);
+        esc0 = P.coef_cap - 1 - (L.nesc - nesc_sb);
+    }
     const uint32_t w0 = (sig & 0xffffu) | (signs & 0xffff0000u);
     const uint32_t w3 = (uint32_t)xS | ((uint32_t)yS << 3) | ((uint32_t)L.rc_scan << 6) | (hide ? 1u << 8 : 0u) |
                         (esc0 << 9);
@@ -2156,8 +2199,15 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
                 for (int nn = nstart; nn > 0; --nn) sig |= dec_slot((int)((seq >> (4 * nn)) & 15u)) << nn;
             }
             if (nstart >= 0) {
-                if (infer_dc && sig == 0) sig |= 1u;
-                else sig |= dec_slot((int)(seq & 15u));
+                HG_COV(l2 == 2 ? COV_SB_SIG4 : COV_SB_SIG);
+                if (infer_dc && sig == 0) {
+                    HG_COV(COV_SB_INFER_DC);
+                    sig |= 1u;
+                } else {
+                    sig |= dec_slot((int)(seq & 15u));
+                }
+            } else {
+                HG_COV(COV_SB_LAST_POS0);
             }
         }
         auto cw = [&](int i, uint32_t v) { ctx_st(L, G, cbase + i, v & 0xffu); };
@@ -2188,7 +2238,10 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     if (sig) {
         // greater1 / greater2 (9.3.4.2.6-7)
         int ctx_set = (i == 0 || cidx > 0) ? 0 : 2;
-        if ((L.fl & F_ANY_SB) && L.rc_prev_c1 == 0) ++ctx_set;
+        if ((L.fl & F_ANY_SB) && L.rc_prev_c1 == 0) {
+            HG_COV(COV_SB_CTXSET_INC);
+            ++ctx_set;
+        }
         L.fl |= F_ANY_SB;
         int c1 = 1;
         uint32_t g1 = 0, g2 = 0;
@@ -2220,23 +2273,30 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
             for (uint32_t &m = beyond8; m && num_g1 < 8;) {
                 const int nn = msb32(m);
                 m &= ~(1u << nn);
-                const int gs = (c1 < 3 ? c1 : 3) * 8;
+                // greater1Ctx (9.3.4.2.6) is 0 from the first flag set on and
+                // grows by one per flag before it, from 1.  The lanes in the loop
+                // step together, so the count is the wave's and only the test of
+                // g1 is per lane; c1 itself is put together after the loop
+                const int gs = g1 ? 0 : (num_g1 < 2 ? num_g1 + 1 : 3) * 8;
                 const uint32_t gm = 0x7fu << gs;  // (bit 7 of every byte of gc stays 0)
                 uint32_t t;
                 const int f = dec_t(L, G, (gc >> gs) & 0xffu, t);
                 gc = bfi32(gm, t << gs, gc);
                 ++num_g1;
                 g1 |= (uint32_t)f << nn;
-                if (c1 > 0) c1 = f ? 0 : c1 + 1;
             }
+            c1 = g1 ? 0 : 1 + num_g1;
             last_g1 = g1 ? msb32(g1) : -1;  // the first set in decoding order (positions decode downwards)
         }
         L.rc_prev_c1 = c1;
         for (int k = 0; k < 4; ++k) ctx_st(L, G, gbase + k, (gc >> (8 * k)) & 0xffu);
         if (last_g1 >= 0 && dec(L, G, CTX_GT2 + ctx_set + (cidx ? 4 : 0))) g2 = 1u << last_g1;
+        if (g2) HG_COV(COV_SB_GT2);
+        if (beyond8) HG_COV(COV_SB_BEYOND8);
         HG_SB_T(L, 2, tsb);
         const bool sign_hidden = !(lane_fl<EG>(L) & F_BYPASS) && (last_sig - first_sig > 3);
         const bool hide = (pic_flags<EG>(P) & SP_SIGN_HIDING) && sign_hidden;
+        if (pic_flags<EG>(P) & SP_SIGN_HIDING) HG_COV(hide ? COV_SB_HIDE : COV_SB_NO_HIDE);
         const int nsign = __builtin_popcount(sig) - (hide ? 1 : 0);
         uint32_t signs = byp_bits(L, G, nsign);
         signs = nsign ? signs << (32 - nsign) : 0u;  // first decoded sign in bit 31
@@ -2248,11 +2308,21 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         // coeff_abs_level_remaining where one is coded, so only those levels
         // are visited, one at a time (their Rice parameters chain); the r03
         // layout stored every coefficient with its own 4-byte store.
+        // (vector engines) the row's escape count before this sub-block: the
+        // record's first escape slot, without counting the nibbles of 15 afterwards
+        [[maybe_unused]] const uint32_t nesc0 = L.nesc;
+        uint64_t nib;
+        if constexpr (kSbVec<EG>) {
+            // greater1 alone: the position with a greater2 flag always has a
+            // remainder, and the remainder loop adds the flag with it
+            nib = spread16_nib_halves(g1);
+        } else {
 #if defined(HG_R05_BASE)
-        uint64_t nib = spread16_nib(g1) + spread16_nib(g2);
+            nib = spread16_nib(g1) + spread16_nib(g2);
 #else
-        uint64_t nib = spread16_nib<EG::kSolo>(g1) + (g2 ? 1ull << (4 * last_g1) : 0ull);  // (g2: at most the one bit)
+            nib = spread16_nib<EG::kSolo>(g1) + (g2 ? 1ull << (4 * last_g1) : 0ull);  // (g2: at most the one bit)
 #endif
+        }
         {
             // the levels with a coded remainder: greater1 set but not the one with a
             // greater2 flag, greater2 set, and every position past the first eight
@@ -2267,12 +2337,18 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
 #endif
             int last_abs = 0, last_rice = 0;
             bool first_rem = true;
+            // (vector engines) cRiceParam of the next remainder, carried: min(4, k + (abs > 3 << k))
+            // after every level (9.3.3.11), 0 for the first
+            [[maybe_unused]] int rice = 0;
             while (need) {
                 const int nn = msb32(need);
                 need ^= 1u << nn;
-                const int base = 1 + (int)((g1 >> nn) & 1) + (int)((g2 >> nn) & 1);
+                const int g1b = (int)((g1 >> nn) & 1);
+                const int base = 1 + g1b + (int)((g2 >> nn) & 1);
                 int k;
-                if (first_rem) {
+                if constexpr (kSbVec<EG>) {
+                    k = rice;
+                } else if (first_rem) {
                     k = 0;
                     first_rem = false;
                 } else {
@@ -2297,12 +2373,25 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
                     } else {
                         rem = (int)((4u << k) + (((1u << ones) - 1u) << (k + 1)) + byp_bits(L, G, ones + k + 1));
                     }
+                    HG_COV(COV_SB_EGK);
                 }
+                if (k == 4) HG_COV(COV_SB_RICE4);
                 last_abs = base + rem;
                 last_rice = k;
                 const int am1 = base - 1 + rem;  // abs - 1
-                nib = (nib & ~(0xfull << (4 * nn))) | ((uint64_t)(am1 < 15 ? am1 : 15) << (4 * nn));
+                if constexpr (kSbVec<EG>) {
+                    const int inc = last_abs > (3 << k) ? 1 : 0;
+                    rice = k + inc < 4 ? k + inc : 4;
+                    // The nibble holds the greater1 flag g1b (0 or 1) and has to
+                    // become min(abs - 1, 15), which is at least g1b: abs - 1 =
+                    // g1b + greater2 + rem.  So the difference is added in place,
+                    // with no carry into the next nibble and nothing to clear first
+                    nib += (uint64_t)(uint32_t)((am1 < 15 ? am1 : 15) - g1b) << (4 * nn);
+                } else {
+                    nib = (nib & ~(0xfull << (4 * nn))) | ((uint64_t)(am1 < 15 ? am1 : 15) << (4 * nn));
+                }
                 if (HG_UNLIKELY(am1 >= 15)) {  // escape: the whole level, in descending scan order from the row's end
+                    HG_COV(COV_SB_ESCAPE);
                     if (L.ncoef + L.nesc + 4 < P.coef_cap) {
                         Coef HG_GAS *e = P.coef_base + L.coef_row + P.coef_cap - 1 - L.nesc;
                         if (pic_flags<EG>(P) & PF_COHERENT) store_word_agent((uint32_t *)e, (uint32_t)last_abs);
@@ -2315,7 +2404,7 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
             }
         }
         HG_SB_T(L, 3, tsb);
-        sb_store<EG>(L, P, sig, signs, nib, xS, yS, hide);
+        sb_store<EG>(L, P, sig, signs, nib, xS, yS, hide, nesc0);
     }
     if (--L.rc_i < 0) {
         // (the TU at the CU's bottom right corner, its last TB)
@@ -2787,6 +2876,11 @@ void emu_parse_lanes(const BatchArgs &a) {
                 ++kruns;
                 ++kr[kind];
                 ku[kind] += cnt;
+                if (kind == U_SB) {
+                    bool any4 = false;
+                    for (int l = 0; l < 64; ++l) any4 |= mine[l] && lanes[l].tb_log2 == 2;
+                    HG_COV(any4 ? COV_SB_RUN_ANY4 : COV_SB_RUN_NO4);
+                }
                 for (int l = 0; l < 64; ++l) {
                     Lane &L = lanes[l];
                     E.lane = l;
@@ -2817,6 +2911,8 @@ void emu_parse_lanes(const BatchArgs &a) {
             for (int k = U_CTU; k <= U_TBD; ++k) printf(" %ld", ku[k]);
             printf("\n  paths");  // (Cov, counted since the last wave)
             for (int k = 0; k < COV_N; ++k) printf(" %ld", g_cov[k]), g_cov[k] = 0;
+            printf("\n  sb_paths");
+            for (int k = COV_N; k < COV_ALL; ++k) printf(" %ld", g_cov[k]), g_cov[k] = 0;
             printf("\n");
         }
     }
