@@ -200,6 +200,8 @@ constexpr int kSoloMaxWaves = 16;
 // first); returns the pictures per wave it dealt for (BatchArgs::parse_group).
 // ppw_force = 0: the adaptive choice.
 int lanes_parse_order(const PicDesc *pics, int n, int lane_rows, int ppw_force, std::vector<uint32_t> &order);
+// the adaptive choice itself: pictures per k_parse_lanes wave for a batch (launch_parse without a parse_order)
+int lanes_pics_per_wave(int lane_rows, int n_pics);
 // k_intra_stream (reconstruction behind the spread parse, k_transform folded in) for this batch
 // (same box, spread, one-decode latency: 4 images 28.3 vs 33.7 ms streamed; 8
 // images 44.4 vs 40.5, the reconstruction no longer keeps up with the parse)
@@ -215,7 +217,7 @@ bool intra_stream_for(int parse_mode, int n_pics, bool has_assembly, const Strea
 // (pics: the batch's pictures; one with dependent slice segments starting inside a
 // CTB row (PicDesc.flags, PD_NMID_SHIFT) makes it a lanes parse: only that engine takes them)
 int parse_mode_for(int requested, int n_pics, const PicDesc *pics = nullptr);
-// the lanes parse's body for a batch (parse_lanes.hip, EngT): lean when every
+// the lanes parse's body for a batch (parse_engine.hpp, EngT): lean when every
 // picture is 4:2:0 without PCM, transform_skip, cu_transquant_bypass, slice
 // segments inside it or wrapping rows; HEIFGPU_LANES_VARIANT=general|auto
 enum : int { LANES_GENERAL = 0, LANES_LEAN = 1 };
@@ -271,6 +273,9 @@ hipError_t launch_render_scaled(const ScaleDesc *descs, int n_images, int max_ti
 hipError_t launch_render_tensor(const TensorDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
                                 hipStream_t s);
 hipError_t launch_parse(const BatchArgs &a, hipStream_t s);
+// (launch_parse's: the kernels of parse_solo.hip and parse_lean.hip)
+hipError_t launch_parse_solo(const BatchArgs &a, hipStream_t s);
+hipError_t launch_parse_lean(const BatchArgs &a, int waves, size_t lds_bytes, hipStream_t s);
 hipError_t launch_transform(const BatchArgs &a, hipStream_t s);
 hipError_t launch_intra(const BatchArgs &a, hipStream_t s);
 hipError_t launch_deblock(const BatchArgs &a, hipStream_t s);

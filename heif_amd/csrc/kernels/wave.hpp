@@ -110,17 +110,12 @@ constexpr int kWave = 64;
 // before the handed-off bytes are read.  Producer: an agent release (buffer_wbl2
 // sc1; s_waitcnt vmcnt(0)), then the explicit wait the guide prescribes (the
 // compiler may drop its own after the write-back), then the relaxed flag store.
-#if defined(HG_HANDOFF_RELAXED)  // A/B only: the r04 forms (vmcnt(0) + sc1 flag; no acquire)
-#define HG_ACQ_AGENT() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup")
-#define HG_REL_AGENT() __builtin_amdgcn_s_waitcnt(0x0f70)
-#else
 #define HG_ACQ_AGENT() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
 #define HG_REL_AGENT()                                  \
     do {                                                \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  \
     } while (0)
-#endif
 // Orders one wave's own LDS traffic across lanes (write by lane i, read by
 // lane j).  A wave's LDS instructions execute in order, so wavefront scope is
 // enough; workgroup scope would also drain the wave's outstanding global

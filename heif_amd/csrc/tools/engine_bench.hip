@@ -3,7 +3,7 @@
 // One substream per wave, one wave per SIMD: the latency of one decision bin
 // on the dependency chain, which bounds the solo / spread parse of one image
 // (its WPP critical path is ~130 k bins).  Variants:
-//   0  branch-free VALU decision (parse_lanes.hip dec_s) on wave-uniform
+//   0  branch-free VALU decision (parse_engine.hpp dec_s) on wave-uniform
 //      values held in VGPRs, state rows by v_readlane, contexts in a VGPR by
 //      v_readlane / v_writelane
 //   1  the same decision in scalar registers (values made uniform with

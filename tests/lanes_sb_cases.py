@@ -7,7 +7,7 @@ synthetic encoder draws the syntax at random (levels with a long tail: 10 % of t
 up to 200 or 3000, so Rice parameters reach 4 and levels escape), so a case is a
 parameter set that makes the path it is named for frequent, or that excludes the
 other paths.  The emulation counts the paths of the unit (the `sb_paths` line of
-HEIFGPU_LANES_STATS, the COV_SB_ entries of enum Cov in kernels/parse_lanes.hip, next
+HEIFGPU_LANES_STATS, the COV_SB_ entries of enum Cov in kernels/parse_state.hpp, next
 to the `paths` line of the TB sizes); NEEDS names the counters a case has to reach and
 ZERO the ones it must not, which the CPU test asserts.
 

@@ -8,7 +8,7 @@ CUs are NxN with four PBs, a third of the PBs take an MPM, 30 % of the
 cu_qp_delta_abs values are drawn over the whole range, 30 % of the last
 positions over the whole TB), so a case is a parameter set that makes the path
 it is named for frequent.  The emulation counts those paths (the `paths` line
-of HEIFGPU_LANES_STATS, enum Cov of kernels/parse_lanes.hip), and NEEDS names
+of HEIFGPU_LANES_STATS, enum Cov of kernels/parse_state.hpp), and NEEDS names
 the ones each case's first picture has to reach, which the CPU test asserts.
 
 Run as a program with a device (`python tests/lanes_units_cases.py`, which

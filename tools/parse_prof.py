@@ -24,7 +24,7 @@ import heif_amd as H  # noqa: E402
 from heif_amd import _lib  # noqa: E402
 from heif_amd.synthetic import permuted_heic  # noqa: E402
 
-# slots of heifgpu_debug_counters (parse_lanes.hip g_prof_lanes), summed over waves
+# slots of heifgpu_debug_counters (parse_state.hpp g_prof_lanes), summed over waves
 LANES = ["cycles", "passes", "ctu", "tree", "tb", "sb", "ctu_end", "units"]
 BINS_PER_IMAGE = 15358022  # context + bypass + terminate bins of one halfmoonbay image (oracle count)
 

@@ -27,7 +27,7 @@ from heif_amd import _lib  # noqa: E402
 from heif_amd.synthetic import permutation, permuted_heic  # noqa: E402
 
 
-# parse_lanes.hip kWaveRec / kWaveRecCap: the records of each wave's own breakdown
+# parse_state.hpp kWaveRec / kWaveRecCap: the records of each wave's own breakdown
 WAVE_REC, WAVE_REC_CAP = 4096, 4096
 KINDS = ["ctu", "cqt", "cu", "tt", "tb", "sb", "ctu_end"]
 
