@@ -1119,6 +1119,7 @@ int heifgpu_batch_prepare_ex(heifgpu_ctx *ctx, const heifgpu_image *const *imgs,
     a.lanes_lean = mode == PARSE_LANES
                        ? lanes_variant_for(hb.seqs.data(), hb.pics.data(), int(hb.pics.size()), a.wpp_ring)
                        : LANES_GENERAL;
+    a.flags_from_recs = mode == PARSE_LANES ? 1 : 0;  // (never streaming: launch_transform paints)
     a.has_assembly = hb.has_assembly ? 1 : 0;
     a.total_rows = int(hb.rows);
     a.bytes_per_sample = hb.bps;

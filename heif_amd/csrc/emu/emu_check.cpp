@@ -8,6 +8,7 @@
 //   sentinel the planes start with
 //   emu_check file.heic 0 [more.heic ...]: host only; the files as one batch
 //   (its picture count, parse mode and lanes variant: prepare's choices)
+//   HEIFGPU_EMU_DUMP_MAPS=path: the pictures' QpY and flag maps after stage 4, to that file
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -67,6 +68,7 @@ int main(int argc, char **argv) {
     std::vector<Coef> coefs(hb.coef_n);
     std::vector<uint32_t> rc(2 * hb.rows), status(hb.pics.size());
     std::vector<uint8_t> recon(hb.recon_bytes), maps(hb.map_bytes);
+    if (getenv("HEIFGPU_EMU_DUMP_MAPS")) std::fill(maps.begin(), maps.end(), uint8_t(0xa5));  // (a byte nobody wrote shows)
     std::vector<int16_t> resid(hb.resid_elems);
     std::vector<SaoParams> sao(hb.sao_n);
     const int W = int(im.out_width), H = int(im.out_height), bps = hb.bps;
@@ -135,6 +137,7 @@ int main(int argc, char **argv) {
     a.lanes_lean = mode == PARSE_LANES
                        ? lanes_variant_for(hb.seqs.data(), hb.pics.data(), int(hb.pics.size()), a.wpp_ring)
                        : LANES_GENERAL;
+    a.flags_from_recs = mode == PARSE_LANES ? 1 : 0;
     a.has_assembly = hb.has_assembly ? 1 : 0;
     a.total_rows = int(hb.rows);
     a.bytes_per_sample = bps;
@@ -189,6 +192,18 @@ int main(int argc, char **argv) {
         }
     }
     if (stages >= 4) emu_deblock(a);
+    if (const char *path = getenv("HEIFGPU_EMU_DUMP_MAPS")) {
+        // every picture's QpY and edge / no-filter maps (w4 * h4 bytes each) as the deblocking
+        // read them, in picture order: the same bytes whichever parse mode wrote them
+        FILE *f = fopen(path, "wb");
+        if (!f) return 2;
+        for (const PicDesc &pd : hb.pics) {
+            const SeqParams &sp = hb.seqs[pd.seq];
+            const size_t n = size_t((sp.width + 3) >> 2) * size_t((sp.height + 3) >> 2);
+            fwrite(maps.data() + pd.map_off, 1, 2 * n, f);
+        }
+        fclose(f);
+    }
     if (stages >= 5) {
         emu_sao_out(a);
     } else {

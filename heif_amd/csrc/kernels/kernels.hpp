@@ -67,6 +67,8 @@ struct BatchArgs {
     int intra_split;           // k_intra: luma and chroma on separate waves (set by launch_intra)
     // (added last: every other kernel's argument offsets, and so its code, stay as they were)
     int lanes_lean;            // lanes parse: the lean tool set's body (lanes_variant_for; LANES_*)
+    int flags_from_recs;       // the edge / no-filter map is painted from the luma TuRecs after the parse (k_paint_flags:
+                               // the lanes parse leaves it out); 0: the parse wrote it (solo / spread)
 };
 
 // k_ycbcr_rgb (color.hip): one decoded image → interleaved RGB8, rotated

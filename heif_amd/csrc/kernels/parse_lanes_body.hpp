@@ -165,7 +165,8 @@ __device__ __forceinline__ void parse_lanes_body(const BatchArgs &a) {
         for (int k = 0; k < 8; ++k) atomicAdd((unsigned long long *)&g_prof_lanes[k], (unsigned long long)pf[k]);
 #if defined(HG_PARSE_PROF_SB)
     // the sub-block unit's phases (slots 8..13: header, sig loop, greater1/2,
-    // signs + remainders + record, sig bins, -), the wave's time: one lane per run
+    // signs + remainders + record, sig bins, -; `make prof-tb`: the tree / TB units' six,
+    // HG_TB_T of parse_state.hpp), the wave's time: one lane per run
     if (live) {
         for (int k = 0; k < 6; ++k) atomicAdd((unsigned long long *)&g_prof_lanes[8 + k], (unsigned long long)L.psb[k]);
         if (blockIdx.x < (unsigned)kWaveRecCap)  // and per wave (records 3 and 4 of the wave's breakdown)

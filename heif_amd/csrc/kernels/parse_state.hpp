@@ -217,21 +217,39 @@ struct Lane {
     uint32_t reinit;  // F_REINIT: RBSP byte (absolute) where the engine restarts after PCM samples
 #if defined(HG_PARSE_PROF_SB)
     // solo tuning build: s_memtime cycles of unit_sb's phases (header, sig loop,
-    // greater1/2, signs + levels + coefficient stores) and sig bins / coefficients
+    // greater1/2, signs + levels + coefficient stores) and sig bins / coefficients;
+    // lanes kernels of the prof-tb build: the tree / TB units' phases (HG_TB_T below)
     uint64_t psb[6];
 #endif
 };
 #if defined(HG_PARSE_PROF_SB) && !defined(HG_HOST_EMU)
 // (the lowest active lane accumulates: in the lanes kernel the lanes running
 // the unit share one timeline, so the psb sums over lanes are the wave's time)
-#define HG_SB_T(L, i, t0)                                                            \
+#define HG_PHASE_T(L, i, t0)                                                         \
     do {                                                                             \
         const uint64_t t_ = __builtin_amdgcn_s_memtime();                            \
         if ((int)__lane_id() == __builtin_ctzll(__ballot(1))) (L).psb[i] += t_ - (t0); \
         (t0) = t_;                                                                   \
     } while (0)
+#endif
+// `make prof-tb` (HG_PARSE_PROF_TB on top of the prof-sb build) times the tree and
+// TB units' phases into the same six slots instead of the sub-block unit's: 0 the
+// TB unit up to the last position, 1 the last-position prefix bins, 2 suffixes and
+// scan set-up, 3 the transform-tree unit up to its map rows, 4 the flag-map rows,
+// 5 the QpY rows of a finished CU (tools/wave_times.py names them)
+#if defined(HG_PARSE_PROF_SB) && !defined(HG_HOST_EMU) && !defined(HG_PARSE_PROF_TB)
+#define HG_SB_T(L, i, t0) HG_PHASE_T(L, i, t0)
+#elif defined(HG_PARSE_PROF_TB) && !defined(HG_HOST_EMU)
+#define HG_SB_T(L, i, t0) ((void)(t0))
 #else
 #define HG_SB_T(L, i, t0) ((void)0)
+#endif
+#if defined(HG_PARSE_PROF_TB) && !defined(HG_HOST_EMU)
+#define HG_TB_T0(t0) uint64_t t0 = __builtin_amdgcn_s_memtime()
+#define HG_TB_T(L, i, t0) HG_PHASE_T(L, i, t0)
+#else
+#define HG_TB_T0(t0) ((void)0)
+#define HG_TB_T(L, i, t0) ((void)0)
 #endif
 
 // Emulation only (HEIFGPU_LANES_STATS prints them per wave): how often the parse
@@ -266,6 +284,15 @@ enum Cov : int {
     COV_SB_GT2,           // coeff_abs_level_greater2_flag set
     COV_SB_RUN_ANY4,      // unit runs of a wave with a 4x4 TB's lane among them
     COV_SB_RUN_NO4,       // and without one
+    COV_SB_END,
+    // the residual header's last-position prefixes (tests/lanes_tbhdr_cases.py), on a `tb_paths` line
+    COV_LAST_00 = COV_SB_END,  // both prefixes 0 (one bin each)
+    COV_LAST_0M,               // x prefix 0, y prefix cMax (no terminating bin)
+    COV_LAST_M0,               // x prefix cMax, y prefix 0
+    COV_LAST_MM,               // both cMax
+    COV_LAST_SUFFIX_X_ONLY,    // a suffix on the x axis alone
+    COV_LAST_SUFFIX_Y_ONLY,    // and on the y axis alone
+    COV_LAST_SWAP,             // vertical scan: the two positions swapped
     COV_ALL
 };
 #if defined(HG_HOST_EMU)

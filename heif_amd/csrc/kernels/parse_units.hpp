@@ -562,10 +562,27 @@ HG_HD inline void unit_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     L.st = U_TT;
 }
 
+// The scalar engines write the edge / no-filter map's rows as the tree's leaves
+// are parsed.  The vector engines leave them to k_paint_flags (transform.hip),
+// which paints the map from the luma TB records after the parse
+// (BatchArgs::flags_from_recs): the per-lane row loop held every lane of the unit
+// run for its largest TB in nearly every pass.  A PCM CU's block
+// stays with pcm_cu in every engine: its record cannot tell the CU's own bypass flag.
+// (HG_FLAGS_IN_PARSE: written by every engine too, for same-box pairs; harmless
+// beside the painting, which writes the same bytes later.)
+#if defined(HG_FLAGS_IN_PARSE)
+template <class EG>
+constexpr bool kFlagsInParse = true;
+#else
+template <class EG>
+constexpr bool kFlagsInParse = EG::kSolo;
+#endif
+
 // U_TT: transform_tree descent (7.3.8.8) from the current node to a leaf,
 // then transform_unit (7.3.8.10) up to its first TB
 template <class EG>
 HG_HD inline void unit_tt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
+    HG_TB_T0(ttt);
     const bool nxn = (L.fl & F_NXN) != 0;
     const int max_depth = P.maxDepthIntra + (nxn ? 1 : 0);
     for (;;) {
@@ -638,7 +655,8 @@ HG_HD inline void unit_tt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         L.cu_qp_delta_val = v;
         update_qpy(L, P);
     }
-    {  // edge / no-filter flags of every 4x4 luma block of the TB (MF_*)
+    HG_TB_T(L, 3, ttt);
+    if constexpr (kFlagsInParse<EG>) {  // edge / no-filter flags of every 4x4 luma block of the TB (MF_*)
         const int nb = 1 << (L.tl - 2), gx0 = L.tx >> 2, gy0 = L.ty >> 2;
         const int wx = gx0 + nb <= P.w4 ? nb : P.w4 - gx0, hy = gy0 + nb <= P.h4 ? nb : P.h4 - gy0;
         const uint64_t nf = (lane_fl<EG>(L) & F_BYPASS) ? MF_NOFILT : 0;
@@ -649,6 +667,7 @@ HG_HD inline void unit_tt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
             store_bytes(row, wx, (rep * h) | (uint64_t)MF_EDGE_V);
         }
     }
+    HG_TB_T(L, 4, ttt);
     const int blk = L.td == 0 ? 0 : (((L.tx >> L.tl) & 1) | (((L.ty >> L.tl) & 1) << 1));
     // luma, then Cb and Cr (two each with 4:2:2: upper, lower)
     L.tb_n = (HG_PIC_CHROMA(P) != 0 && (!chroma4 || blk == 3)) ? (HG_PIC_CHROMA(P) == 2 ? 5 : 3) : 1;
@@ -722,6 +741,7 @@ HG_HD inline void tb_done(Lane &L, LaneLds &ld, LanePic &P) {
 // coding-quadtree node in z-order (skipping children outside the picture) or
 // the CTU end
 HG_HD inline void cu_done(Lane &L, LaneLds &ld, LanePic &P) {
+    HG_TB_T0(tcu);
     {
         const int n = 1 << L.ql, nd = n >> 3;
         const int dy = (L.qy - L.ctby) >> 3, dx = (L.qx - L.ctbx) >> 3;
@@ -737,6 +757,7 @@ HG_HD inline void cu_done(Lane &L, LaneLds &ld, LanePic &P) {
         }
         L.qp_prev_last = L.qpy_cur;
     }
+    HG_TB_T(L, 5, tcu);
     // next coding-quadtree node in z-order, skipping children outside the picture
     while (L.qd > 0) {
         const int s = 1 << L.ql;
@@ -763,6 +784,7 @@ HG_HD inline void cu_done(Lane &L, LaneLds &ld, LanePic &P) {
 // (transform_skip_flag, last position) is parsed
 template <class EG>
 HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
+    HG_TB_T0(ttb);
     const int t = L.tb_t;
     const bool chroma4 = (HG_PIC_CHROMA(P) == 1 || HG_PIC_CHROMA(P) == 2) && L.tl == 2;
     // component and (4:2:2) upper / lower half of TB t: luma, Cb (, Cb lower), Cr (, Cr lower)
@@ -819,13 +841,17 @@ HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     const int off = cidx == 0 ? 3 * (l2 - 2) + ((l2 - 1) >> 2) : 15;
     const int shift = cidx == 0 ? (l2 + 1) >> 2 : l2 - 2;
     int px = 0, py = 0;
+    HG_TB_T(L, 0, ttb);
     // (a register word of the prefix's up to five contexts, read and stored once,
     // measured no faster than these per-bin LDS bytes: DESIGN 5.18)
     while (px < cmax && dec(L, G, CTX_LAST_X + off + (px >> shift))) ++px;
     while (py < cmax && dec(L, G, CTX_LAST_Y + off + (py >> shift))) ++py;
+    HG_TB_T(L, 1, ttb);
     int lx = px, ly = py;
     if (px > 3 || py > 3) HG_COV(COV_LAST_SUFFIX);
     if (px > 8 || py > 8) HG_COV(COV_LAST_CTX5);
+    if ((px == 0 || px == cmax) && (py == 0 || py == cmax)) HG_COV(COV_LAST_00 + (px ? 2 : 0) + (py ? 1 : 0));
+    if ((px > 3) != (py > 3)) HG_COV(px > 3 ? COV_LAST_SUFFIX_X_ONLY : COV_LAST_SUFFIX_Y_ONLY);
     if (px > 3) {
         const int k = (px >> 1) - 1;
         lx = (1 << k) * (2 + (px & 1)) + (int)byp_bits(L, G, k);
@@ -840,6 +866,7 @@ HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         else if (L.tb_mode >= 22 && L.tb_mode <= 30) scan = 1;
     }
     if (scan == 2) {
+        HG_COV(COV_LAST_SWAP);
         const int tt = lx;
         lx = ly;
         ly = tt;
@@ -858,6 +885,7 @@ HG_HD inline void unit_tb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     L.fl &= ~F_ANY_SB;
     L.rc_i = L.rc_last_sub;
     L.st = U_SB;
+    HG_TB_T(L, 2, ttb);
 }
 
 // bit n of a 16-bit mask to bit 4n (a nibble per scan position).  Scalar
@@ -1096,7 +1124,7 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
             cw(off + 1, c0 >> 16);
             cw(off + 2, c0 >> 24);
         }
-#if defined(HG_PARSE_PROF_SB) && !defined(HG_HOST_EMU)
+#if defined(HG_PARSE_PROF_SB) && !defined(HG_PARSE_PROF_TB) && !defined(HG_HOST_EMU)
         L.psb[4] += (uint64_t)(nstart + 1);
 #endif
         HG_SB_T(L, 1, tsb);

@@ -243,11 +243,61 @@ __global__ void __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_e
 #endif
 }
 
+// The edge / no-filter map (MF_*, one byte per 4x4 luma block) of the pictures the
+// lanes parse decoded, from their luma TB records: the lanes parse leaves the map's
+// rows out of its serial chain, where a 32x32 TB held every lane of the
+// unit run for eight stores.  The luma TBs tile the picture, so every byte is written:
+// MF_EDGE_V down the TB's first column, MF_EDGE_H along its first row, MF_NOFILT
+// everywhere under cu_transquant_bypass.  A PCM CU's record (one luma TB of the CU's
+// size, TU_BYPASS set whatever the CU's own flag) is skipped: pcm_cu painted it.
+// One workgroup per CTB row of a picture like k_transform, a record per lane.
+__global__ void __launch_bounds__(kWaves * 64) k_paint_flags(BatchArgs a) {
+    const int pic = a.pic0 + blockIdx.y, row = blockIdx.x;
+    const PicDesc pd = a.pics[pic];
+    if (pd.flags & PD_ASSEMBLY) return;  // k_assemble copies its children's maps
+    const SeqParams sp = a.seqs[pd.seq];
+    const int hctb = (sp.height + (1 << sp.log2_ctb) - 1) >> sp.log2_ctb;
+    if (row >= hctb) return;
+    const int w4 = (sp.width + 3) >> 2, h4 = (sp.height + 3) >> 2;
+    uint8_t *flg = a.maps + pd.map_off + (size_t)w4 * h4;
+    const uint32_t ntu = min(a.row_counts[2 * (pd.row_off + row)], pd.tu_cap_row);
+    const TuRec *tus = a.tus + pd.tu_off + (uint64_t)row * pd.tu_cap_row;
+    const int wave = (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    for (uint32_t t0 = 64u * wave; t0 < ntu; t0 += 64u * kWaves) {
+        for (int vl = lane; vl < 64; vl += kWave) {
+            const uint32_t t = t0 + (uint32_t)vl;
+            if (t >= ntu) continue;
+            const TuRec tu = tus[t];
+            if ((tu.flags & (TU_CIDX_MASK | TU_PCM)) || tu.log2 < 2 || tu.log2 > 5) continue;
+            const int nb = 1 << (tu.log2 - 2), gx0 = tu.x >> 2, gy0 = tu.y >> 2;
+            if (gx0 >= w4 || gy0 >= h4) continue;
+            const int wx = gx0 + nb <= w4 ? nb : w4 - gx0, hy = gy0 + nb <= h4 ? nb : h4 - gy0;
+            const uint8_t nf = (tu.flags & TU_BYPASS) ? MF_NOFILT : 0;
+            for (int y = 0; y < hy; ++y) {
+                uint8_t *r = flg + (size_t)(gy0 + y) * w4 + gx0;
+                const uint8_t h = (uint8_t)((y == 0 ? MF_EDGE_H : 0) | nf);
+                const uint64_t v = (0x0101010101010101ull * h) | (uint64_t)MF_EDGE_V;
+                if (wx == 8) {
+                    __builtin_memcpy(r, &v, 8);
+                } else if (wx == 4) {
+                    __builtin_memcpy(r, &v, 4);
+                } else {
+                    for (int x = 0; x < wx; ++x) r[x] = (uint8_t)(v >> (8 * x));
+                }
+            }
+        }
+    }
+}
+
 #if defined(HG_HOST_EMU)
-void emu_transform(const BatchArgs &a) { emu_launch(k_transform, a.max_rows, a.n_pics, kWaves, a); }
+void emu_transform(const BatchArgs &a) {
+    emu_launch(k_transform, a.max_rows, a.n_pics, kWaves, a);
+    if (a.flags_from_recs) emu_launch(k_paint_flags, a.max_rows, a.n_pics, kWaves, a);
+}
 #else
 hipError_t launch_transform(const BatchArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_transform, dim3(a.max_rows, a.n_pics), dim3(kWaves * 64), 0, s, a);
+    if (a.flags_from_recs) hipLaunchKernelGGL(k_paint_flags, dim3(a.max_rows, a.n_pics), dim3(kWaves * 64), 0, s, a);
     return hipGetLastError();
 }
 #endif
