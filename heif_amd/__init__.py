@@ -95,6 +95,32 @@ class HeifImage:
         _lib.check(lib.heifgpu_image_get_display(self._h, ctypes.byref(d)))
         return d
 
+    def source_rect(self, window=None):
+        """(x, y, w, h) of the decoded planes that a render of `window` reads
+        (heifgpu_window_source_rect): window = (x, y, w, h) in displayed
+        coordinates, the tuples render_scaled(windows=) takes; None or
+        (0, 0, 0, 0) is the whole displayed picture.  ValueError for a window
+        that is empty or not inside the displayed picture."""
+        w = _lib.Rect(*(int(v) for v in window)) if window is not None else _lib.Rect()
+        src = _lib.Rect()
+        try:
+            _lib.check(lib.heifgpu_window_source_rect(self._h, ctypes.byref(w), ctypes.byref(src)))
+        except HeifGpuError as e:
+            raise ValueError(str(e)) from None
+        return src.as_tuple()
+
+    def tiles_for(self, rect=None):
+        """(col0, row0, cols, rows): the grid tiles a source rectangle of the
+        decoded planes selects (heifgpu_image_tiles_for_rect); None = all of
+        them.  ValueError for a rectangle that is empty or outside the image."""
+        r = _lib.Rect(*(int(v) for v in rect)) if rect is not None else _lib.Rect()
+        v = [ctypes.c_uint32() for _ in range(4)]
+        try:
+            _lib.check(lib.heifgpu_image_tiles_for_rect(self._h, ctypes.byref(r), *[ctypes.byref(x) for x in v]))
+        except HeifGpuError as e:
+            raise ValueError(str(e)) from None
+        return tuple(x.value for x in v)
+
     def tile_params(self, tile: int) -> dict:
         """Parsed SPS/PPS/slice-header fields of grid tile `tile` (row-major)."""
         tp = _lib.TileParams()
@@ -126,6 +152,27 @@ class DecodedImage:
     cr: Optional["object"]
     info: _lib.ImageInfo
     image: Optional["HeifImage"] = None  # the parsed image (its display map; DecodeContext.render)
+    # window decode: the (x, y, w, h) of the planes the last decode_async wrote for certain
+    # (DeviceBatch.rects); None after a full decode.  The renders refuse to read outside it.
+    valid: Optional[tuple] = None
+
+
+def _inside(need, valid) -> bool:
+    return (need[0] >= valid[0] and need[1] >= valid[1] and need[0] + need[2] <= valid[0] + valid[2]
+            and need[1] + need[3] <= valid[1] + valid[3])
+
+
+def _check_valid(what: str, i: int, out: "DecodedImage", alpha, window) -> None:
+    """ValueError if rendering `window` of out (None: the whole displayed picture)
+    would read samples a window decode did not write, of out or of its alpha image."""
+    parts = [(n, o) for n, o in (("image", out), ("alpha image", alpha)) if o is not None and o.valid is not None]
+    if not parts:
+        return
+    need = out.image.source_rect(window)
+    for name, o in parts:
+        if not _inside(need, o.valid):
+            raise ValueError(f"{what}: {name} {i} was decoded for the rectangle {o.valid} of its planes, "
+                             f"this call reads {need}")
 
 
 class DecodeContext:
@@ -207,7 +254,7 @@ class DecodeContext:
 
     def prepare(self, images: Sequence[HeifImage], tile_stride: int = 1, tile_offset: int = 0,
                 reuse: Optional["DeviceBatch"] = None, wait: bool = True, parse: str = "auto",
-                pics_per_wave: int = 0, pipeline_sets: int = 0) -> "DeviceBatch":
+                pics_per_wave: int = 0, pipeline_sets: int = 0, windows=None, rects=None) -> "DeviceBatch":
         """Device batch of `images` (heifgpu_batch_prepare_ex).  tile_stride /
         tile_offset select the grid tiles k % tile_stride == tile_offset (the
         single-image tile split across GPUs); `reuse` reloads an existing batch
@@ -217,18 +264,48 @@ class DecodeContext:
         adaptive), "solo" (one substream per wave, a picture's rows in one
         workgroup) or "spread" (one substream per wave, one workgroup per row:
         small-batch latency).  pipeline_sets: parse-output sets of a new batch
-        (0 = default 3; 1-3, include/heifgpu.h)."""
-        arr = (ctypes.c_void_p * len(images))(*[im._h.value for im in images])
+        (0 = default 3; 1-3, include/heifgpu.h).
+        Window decode (heifgpu_batch_prepare_rects): windows[i] = (x, y, w, h)
+        in displayed coordinates, the tuples render_scaled(windows=) takes, or
+        None for the whole image; only the grid tiles (and independent
+        sub-pictures) that a render of that window reads are uploaded and
+        decoded.  rects[i] = (x, y, w, h) gives the rectangle in decoded-plane
+        coordinates instead and wins over windows[i]: an alpha image is
+        prepared with its colour image's HeifImage.source_rect(window).  The
+        rectangles end up in DeviceBatch.rects and, at decode_async, in
+        DecodedImage.valid."""
+        n = len(images)
+        for name, v in (("windows", windows), ("rects", rects)):
+            if v is not None and len(v) != n:
+                raise ValueError(f"{name} must have one entry per image")
+        chosen = [None] * n
+        for i, im in enumerate(images):
+            if rects is not None and rects[i] is not None:
+                chosen[i] = tuple(int(v) for v in rects[i])
+            elif windows is not None and windows[i] is not None:
+                chosen[i] = im.source_rect(windows[i])
+            if chosen[i] is not None and chosen[i][2] == 0 and chosen[i][3] == 0:
+                chosen[i] = None  # the "everything" form
+        src = None
+        if any(r is not None for r in chosen):
+            src = (_lib.Rect * n)(*[_lib.Rect(*r) if r is not None else _lib.Rect() for r in chosen])
+        arr = (ctypes.c_void_p * n)(*[im._h.value for im in images])
         opts = _lib.BatchOpts(tile_stride, tile_offset, _lib.PARSE_MODES[parse], pics_per_wave, pipeline_sets)
+        if src is None and not hasattr(lib, "heifgpu_batch_prepare_rects"):  # an earlier build of this ABI
+            def load(handle):
+                return lib.heifgpu_batch_prepare_ex(self._h, arr, n, ctypes.byref(opts), handle)
+        else:
+            def load(handle):
+                return lib.heifgpu_batch_prepare_rects(self._h, arr, n, ctypes.byref(opts), src, handle)
         if reuse is not None:
-            _lib.check(lib.heifgpu_batch_prepare_ex(self._h, arr, len(images), ctypes.byref(opts),
-                                                    ctypes.byref(reuse._h)))
+            _lib.check(load(ctypes.byref(reuse._h)))
             reuse.images = list(images)
             batch = reuse
         else:
             b = ctypes.c_void_p()
-            _lib.check(lib.heifgpu_batch_prepare_ex(self._h, arr, len(images), ctypes.byref(opts), ctypes.byref(b)))
+            _lib.check(load(ctypes.byref(b)))
             batch = DeviceBatch(self, b, list(images))
+        batch.rects = chosen
         if wait:
             self._torch.cuda.synchronize(self.device)
         return batch
@@ -270,6 +347,8 @@ class DecodeContext:
         (heifgpu_ycbcr_to_rgb), as a torch tensor on the device."""
         torch = self._torch
         inf = img.info
+        if img.valid is not None and not _inside((0, 0, inf.width, inf.height), img.valid):
+            raise ValueError(f"to_rgb reads the whole image, which was decoded for the rectangle {img.valid} only")
         rot = inf.rotation & 3
         ow, oh = (inf.height, inf.width) if rot & 1 else (inf.width, inf.height)
         rgb = torch.empty((oh, ow, 3), dtype=torch.uint8, device=torch.device("cuda", self.device))
@@ -298,6 +377,8 @@ class DecodeContext:
             raise ValueError("render needs images that carry their HeifImage (alloc_outputs)")
         if alphas is not None and len(alphas) != n:
             raise ValueError("alphas must have one entry per image")
+        for i, o in enumerate(outs):
+            _check_valid("render", i, o, alphas[i] if alphas is not None else None, None)
         dev = torch.device("cuda", self.device)
         res, surf = [], (_lib.Surface * max(n, 1))()
         for i, o in enumerate(outs):
@@ -363,6 +444,10 @@ class DecodeContext:
             else:
                 d = o.image.display
                 _lib.check(lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_MODES[mode], ctypes.byref(scales[i])))
+        for i, o in enumerate(outs):
+            sc = scales[i]
+            _check_valid("render_scaled", i, o, alphas[i] if alphas is not None else None,
+                         (sc.x, sc.y, sc.width, sc.height))
         dev = torch.device("cuda", self.device)
         dt = torch.int16 if wide else torch.uint8
         if windows is not None or mode != "contain":
@@ -446,6 +531,10 @@ class DecodeContext:
             else:
                 d = o.image.display
                 _lib.check(lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_MODES[mode], ctypes.byref(scales[i])))
+        for i, o in enumerate(outs):
+            sc = scales[i]
+            _check_valid("render_tensor", i, o, alphas[i] if alphas is not None else None,
+                         (sc.x, sc.y, sc.width, sc.height))
         dev = torch.device("cuda", self.device)
         chw = layout == "chw"
 
@@ -501,6 +590,9 @@ class DeviceBatch:
 
     def __init__(self, ctx: DecodeContext, handle: ctypes.c_void_p, images: List[HeifImage]):
         self.ctx, self._h, self.images = ctx, handle, images
+        # window decode: per image the (x, y, w, h) of its planes this load decodes for
+        # certain, None where it decodes everything (DecodeContext.prepare sets it)
+        self.rects: List[Optional[tuple]] = [None] * len(images)
 
     def decode_async(self, outs: Sequence[DecodedImage], stream: Optional[int] = None):
         torch = self.ctx._torch
@@ -508,6 +600,15 @@ class DeviceBatch:
             stream = torch.cuda.current_stream(self.ctx.device).cuda_stream
         planes = DecodeContext.planes_of(outs)
         _lib.check(lib.heifgpu_batch_decode(self.ctx._h, self._h, planes, ctypes.c_void_p(stream)))
+        for o, r in zip(outs, self.rects):
+            o.valid = r
+
+    @property
+    def pictures(self) -> int:
+        """The pictures this load decodes (heifgpu_batch_picture_count)."""
+        v = ctypes.c_uint32()
+        _lib.check(lib.heifgpu_batch_picture_count(self._h, ctypes.byref(v)))
+        return v.value
 
     def status(self, stream: Optional[int] = None) -> List[int]:
         torch = self.ctx._torch
@@ -586,19 +687,48 @@ class HeicDecoder:
         """decode() then YCbCr -> RGB8 with the irot rotation (libheif's default output)."""
         return cls.context(device).to_rgb(cls.decode(data, device, item_id))
 
+    @staticmethod
+    def _fit_window(img: HeifImage, size, mode: str):
+        """The window of the displayed picture that render_scaled / render_tensor
+        read for (size, mode); None: the whole picture."""
+        if size is None:
+            return None
+        if mode not in _lib.FIT_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(_lib.FIT_MODES)}")
+        sc = _lib.Scale()
+        d = img.display
+        _lib.check(lib.heifgpu_scale_fit(ctypes.byref(d), int(size[1]), int(size[0]), _lib.FIT_MODES[mode],
+                                         ctypes.byref(sc)))
+        return (sc.x, sc.y, sc.width, sc.height) if sc.width or sc.height else None
+
+    @classmethod
+    def _decode_pair(cls, data: bytes, device: int, size, mode: str, tiles: str, with_alpha: bool):
+        """The primary image and (with_alpha, when the file has one) its alpha
+        image, decoded whole (tiles="all") or for the window that (size, mode)
+        reads (tiles="window")."""
+        if tiles not in ("all", "window"):
+            raise ValueError(f"tiles {tiles!r}: 'all' or 'window'")
+        ctx = cls.context(device)
+        img = HeifImage.parse(data)
+        rect = img.source_rect(cls._fit_window(img, size, mode)) if tiles == "window" else None
+        out = cls._decode_image(ctx, img, rect)
+        aid = img.display.alpha_item_id
+        alpha = cls._decode_image(ctx, HeifImage.parse(data, aid), rect) if aid and with_alpha else None
+        return out, alpha
+
     @classmethod
     def decode_display(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, size=None,
-                       mode: str = "contain"):
+                       mode: str = "contain", tiles: str = "all"):
         """The picture a viewer shows: decodes the primary image and, when it
         has one (display.alpha_item_id), its alpha plane, then renders
         (DecodeContext.render) with clap / irot / imir applied.  fmt None picks
         RGBA when there is alpha and 16 bits when the bit depth is above 8.
         size = (h, w) renders it into that box instead (DecodeContext.render_scaled
-        with `mode`); None is the full size."""
+        with `mode`); None is the full size.  tiles="window" decodes only the
+        grid tiles the rendered window reads (of the alpha image too): the same
+        pixels, bit for bit, for less work when `mode` or a clap crops."""
         ctx = cls.context(device)
-        out = cls.decode(data, device)
-        aid = out.image.display.alpha_item_id
-        alpha = cls.decode(data, device, aid) if aid else None
+        out, alpha = cls._decode_pair(data, device, size, mode, tiles, True)
         if fmt is None:
             fmt = ("rgba" if alpha is not None else "rgb") + ("16" if out.info.bit_depth > 8 else "8")
         alphas = [alpha] if alpha is not None else None
@@ -607,25 +737,36 @@ class HeicDecoder:
         return ctx.render([out], fmt, alphas)[0]
 
     @classmethod
-    def decode_tensor(cls, data: bytes, size, mode: str = "cover", device: int = 0, flip: int = 0, **kw):
+    def decode_tensor(cls, data: bytes, size, mode: str = "cover", device: int = 0, flip: int = 0,
+                      tiles: str = "all", **kw):
         """decode_display(size=) as a normalised float tensor: decodes the
         primary image (and its alpha plane when `src` is an RGBA format and the
         file has one), then DecodeContext.render_tensor of that one picture:
         (C, h, w), or (h, w, C) for layout="hwc".  dtype, layout, mean, std, src
-        and scale_bias go through to render_tensor."""
+        and scale_bias go through to render_tensor; tiles as in decode_display."""
         ctx = cls.context(device)
-        out = cls.decode(data, device)
-        aid = out.image.display.alpha_item_id
         rgba = kw.get("src", "rgb8").startswith("rgba")
-        alphas = [cls.decode(data, device, aid)] if aid and rgba else None
+        out, alpha = cls._decode_pair(data, device, size, mode, tiles, rgba)
+        alphas = [alpha] if alpha is not None else None
         return ctx.render_tensor([out], size, mode, flips=[flip], alphas=alphas, **kw)[0]
 
     @classmethod
-    def decode(cls, data: bytes, device: int = 0, item_id: int = 0) -> DecodedImage:
+    def decode(cls, data: bytes, device: int = 0, item_id: int = 0, window=None, rect=None) -> DecodedImage:
+        """Decodes one image item.  window = (x, y, w, h) in displayed
+        coordinates decodes only the grid tiles a render of that window reads
+        (DecodedImage.valid then names the rectangle of the planes that was
+        written); rect gives it in decoded-plane coordinates instead (an alpha
+        image takes its colour image's HeifImage.source_rect(window))."""
         ctx = cls.context(device)
         img = HeifImage.parse(data, item_id)
+        if rect is None and window is not None:
+            rect = img.source_rect(window)
+        return cls._decode_image(ctx, img, rect)
+
+    @staticmethod
+    def _decode_image(ctx: DecodeContext, img: HeifImage, rect) -> DecodedImage:
         outs = ctx.alloc_outputs([img])
-        batch = ctx.prepare([img])
+        batch = ctx.prepare([img], rects=[rect])
         try:
             batch.decode_async(outs)
             st = batch.status()

@@ -144,6 +144,14 @@ class Scale(ctypes.Structure):
                 ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
 
 
+class Rect(ctypes.Structure):
+    """heifgpu_rect: a rectangle of samples (width == height == 0: everything)."""
+    _fields_ = [("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
+
+    def as_tuple(self):
+        return (self.x, self.y, self.width, self.height)
+
+
 class TensorFormat(ctypes.Structure):
     """heifgpu_tensor_format: the integer format the picture is rendered in, the
     element type and layout it is written as, and out = R * a[c] + b[c]."""
@@ -184,7 +192,8 @@ EXPORTS = (
     "heifgpu_image_parse_many", "heifgpu_batch_parse_geometry", "heifgpu_ipc_export", "heifgpu_ipc_open",
     "heifgpu_ipc_close", "heifgpu_batch_status_previous", "heifgpu_abi_version", "heifgpu_batch_lanes_variant",
     "heifgpu_image_get_display", "heifgpu_render_batch", "heifgpu_scale_fit", "heifgpu_render_batch_scaled",
-    "heifgpu_render_batch_tensor",
+    "heifgpu_render_batch_tensor", "heifgpu_window_source_rect", "heifgpu_image_tiles_for_rect",
+    "heifgpu_batch_prepare_rects", "heifgpu_batch_count_pictures", "heifgpu_batch_picture_count",
 )
 
 
@@ -263,9 +272,16 @@ def _load() -> ctypes.CDLL:
                                               VP]),
         "heifgpu_render_batch_tensor": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), P(TensorFormat), P(Scale),
                                               P(U32), P(TensorSurface), VP]),
+        "heifgpu_window_source_rect": (I32, [VP, P(Rect), P(Rect)]),
+        "heifgpu_image_tiles_for_rect": (I32, [VP, P(Rect), P(U32), P(U32), P(U32), P(U32)]),
+        "heifgpu_batch_prepare_rects": (I32, [VP, P(VP), SZ, P(BatchOpts), P(Rect), P(VP)]),
+        "heifgpu_batch_count_pictures": (I32, [P(VP), SZ, P(BatchOpts), P(Rect), P(U32)]),
+        "heifgpu_batch_picture_count": (I32, [VP, P(U32)]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
-    optional = {"heifgpu_batch_lanes_variant"}
+    # (and no window decode: DecodeContext.prepare without windows then goes through prepare_ex)
+    optional = {"heifgpu_batch_lanes_variant", "heifgpu_window_source_rect", "heifgpu_image_tiles_for_rect",
+                "heifgpu_batch_prepare_rects", "heifgpu_batch_count_pictures", "heifgpu_batch_picture_count"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue

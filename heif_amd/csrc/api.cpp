@@ -32,6 +32,7 @@ static_assert(sizeof(heifgpu_planes) == 40, "heifgpu_planes: 3 pointers + 3 int3
 static_assert(sizeof(heifgpu_batch_opts) == 20, "heifgpu_batch_opts: 5 x uint32");
 static_assert(sizeof(heifgpu_display_info) == 44, "heifgpu_display_info: 11 x 32 bits");
 static_assert(sizeof(heifgpu_surface) == 16, "heifgpu_surface: pointer + int32 (+ padding)");
+static_assert(sizeof(heifgpu_rect) == 16, "heifgpu_rect: 4 x uint32");
 static_assert(HEIFGPU_PIX_RGB8 == RENDER_RGB8 && HEIFGPU_PIX_RGBA8 == RENDER_RGBA8 && HEIFGPU_PIX_RGB16 == RENDER_RGB16 &&
                   HEIFGPU_PIX_RGBA16 == RENDER_RGBA16,
               "pixel formats");
@@ -890,8 +891,83 @@ int heifgpu_stage_times(heifgpu_ctx *ctx, float ms[6]) {
     return HEIFGPU_OK;
 }
 
+// ---- window decode: geometry (host only) and the per-image source rectangles ----
+static Rect rect_of(const heifgpu_rect &r) { return Rect{r.x, r.y, r.width, r.height}; }
+
+int heifgpu_window_source_rect(const heifgpu_image *img, const heifgpu_rect *window, heifgpu_rect *src) {
+    if (!img || !src) return fail(HEIFGPU_E_INVALID, "null argument");
+    Rect out;
+    if (!window_source_rect(img->img, window ? rect_of(*window) : Rect{}, out))
+        return fail(HEIFGPU_E_INVALID, "window empty or outside the displayed picture");
+    *src = heifgpu_rect{out.x, out.y, out.w, out.h};
+    return HEIFGPU_OK;
+}
+
+int heifgpu_image_tiles_for_rect(const heifgpu_image *img, const heifgpu_rect *src, uint32_t *col0, uint32_t *row0,
+                                 uint32_t *cols, uint32_t *rows) {
+    if (!img) return fail(HEIFGPU_E_INVALID, "null argument");
+    const Rect r = src ? rect_of(*src) : Rect{};
+    if (!rect_inside(r, img->img.out_width, img->img.out_height))
+        return fail(HEIFGPU_E_INVALID, "source rectangle empty or outside the image");
+    uint32_t v[4];
+    tiles_for_rect(img->img, r, v[0], v[1], v[2], v[3]);
+    if (col0) *col0 = v[0];
+    if (row0) *row0 = v[1];
+    if (cols) *cols = v[2];
+    if (rows) *rows = v[3];
+    return HEIFGPU_OK;
+}
+
+// the checks of the arguments that heifgpu_batch_prepare_rects and heifgpu_batch_count_pictures share
+static int prepare_args(const heifgpu_image *const *imgs, size_t n, const heifgpu_batch_opts *opts,
+                        const heifgpu_rect *src, uint32_t &stride, uint32_t &offset,
+                        std::vector<const ParsedImage *> &parsed, std::vector<Rect> &rects) {
+    stride = opts && opts->tile_stride ? opts->tile_stride : 1u;
+    offset = opts ? opts->tile_offset : 0u;
+    if (offset >= stride) return fail(HEIFGPU_E_INVALID, "tile_offset must be below tile_stride");
+    for (size_t i = 0; i < n; ++i) {
+        if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
+        parsed.push_back(&imgs[i]->img);
+        if (!src) continue;
+        rects.push_back(rect_of(src[i]));
+        if (!rect_inside(rects.back(), imgs[i]->img.out_width, imgs[i]->img.out_height))
+            return fail(HEIFGPU_E_INVALID, "source rectangle of image " + std::to_string(i) + " empty or outside the image");
+    }
+    return HEIFGPU_OK;
+}
+
+int heifgpu_batch_count_pictures(const heifgpu_image *const *imgs, size_t n, const heifgpu_batch_opts *opts,
+                                 const heifgpu_rect *src, uint32_t *pictures) {
+    if (!imgs || !pictures || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    uint32_t stride, offset;
+    std::vector<const ParsedImage *> parsed;
+    std::vector<Rect> rects;
+    if (int rc = prepare_args(imgs, n, opts, src, stride, offset, parsed, rects)) return rc;
+    try {
+        *pictures = uint32_t(build_batch(parsed.data(), n, stride, offset, /*defer_bits=*/true,
+                                         src ? rects.data() : nullptr).pics.size());
+    } catch (const UnsupportedError &e) {
+        return fail(HEIFGPU_E_UNSUPPORTED, e.what());
+    } catch (const std::exception &e) {
+        return fail(HEIFGPU_E_PARSE, e.what());
+    }
+    return HEIFGPU_OK;
+}
+
+int heifgpu_batch_picture_count(const heifgpu_batch *b, uint32_t *pictures) {
+    if (!b || !pictures) return fail(HEIFGPU_E_INVALID, "null argument");
+    if (!b->loaded) return fail(HEIFGPU_E_INVALID, "batch not loaded (its last prepare failed)");
+    *pictures = uint32_t(b->n_pics);
+    return HEIFGPU_OK;
+}
+
 int heifgpu_batch_prepare_ex(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
                              const heifgpu_batch_opts *opts, heifgpu_batch **inout) {
+    return heifgpu_batch_prepare_rects(ctx, imgs, n, opts, nullptr, inout);
+}
+
+int heifgpu_batch_prepare_rects(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                const heifgpu_batch_opts *opts, const heifgpu_rect *src, heifgpu_batch **inout) {
     if (!ctx || !imgs || !inout || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
     const uint32_t stride = opts && opts->tile_stride ? opts->tile_stride : 1u;
     const uint32_t offset = opts ? opts->tile_offset : 0u;
@@ -902,19 +978,23 @@ int heifgpu_batch_prepare_ex(heifgpu_ctx *ctx, const heifgpu_image *const *imgs,
         return fail(HEIFGPU_E_UNSUPPORTED, "HEIFGPU_PARSE_ROWS was removed in ABI 6 (DESIGN.md 5.9)");
     const int ppw_req = opts ? int(std::min<uint32_t>(opts->pics_per_wave, 64u)) : 0;
     if (*inout && (*inout)->device != ctx->device) return fail(HEIFGPU_E_INVALID, "batch belongs to another device");
-    HIP_TRY(hipSetDevice(ctx->device));
+    // the rectangles are checked here: nothing has been uploaded or launched, a reloaded batch is untouched
     std::vector<const ParsedImage *> parsed;
+    std::vector<Rect> rects;
+    {
+        uint32_t s_, o_;
+        if (int rc = prepare_args(imgs, n, opts, src, s_, o_, parsed, rects)) return rc;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
     std::vector<heifgpu_image_info> infos;
     for (size_t i = 0; i < n; ++i) {
-        if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
-        parsed.push_back(&imgs[i]->img);
         heifgpu_image_info info;
         heifgpu_image_get_info(imgs[i], &info);
         infos.push_back(info);
     }
     HostBatch hb;
     try {
-        hb = build_batch(parsed.data(), n, stride, offset, /*defer_bits=*/true);
+        hb = build_batch(parsed.data(), n, stride, offset, /*defer_bits=*/true, src ? rects.data() : nullptr);
     } catch (const UnsupportedError &e) {
         return fail(HEIFGPU_E_UNSUPPORTED, e.what());
     } catch (const std::exception &e) {

@@ -8,6 +8,10 @@
 //   sentinel the planes start with
 //   emu_check file.heic 0 [more.heic ...]: host only; the files as one batch
 //   (its picture count, parse mode and lanes variant: prepare's choices)
+//   rect=x,y,w,h anywhere after the file, in either form: the window decode
+//    of the first file for that rectangle of its decoded planes;
+//   the pictures build_batch selected must match the oracle, must cover the
+//   rectangle, and every other sample must keep the sentinel
 //   HEIFGPU_EMU_DUMP_MAPS=path: the pictures' QpY and flag maps after stage 4, to that file
 #include <cstdio>
 #include <cstdlib>
@@ -27,6 +31,20 @@ using namespace hg;
 int main(int argc, char **argv) {
     if (argc < 2) return 2;
     setvbuf(stdout, nullptr, _IONBF, 0);  // every line out before a sanitizer abort
+    Rect want;  // rect=: taken out of argv, the positional forms stay as they are
+    bool have_rect = false;
+    {
+        int k = 1;
+        for (int j = 1; j < argc; ++j) {
+            if (j > 1 && !strncmp(argv[j], "rect=", 5)) {
+                if (sscanf(argv[j] + 5, "%u,%u,%u,%u", &want.x, &want.y, &want.w, &want.h) != 4) return 2;
+                have_rect = true;
+            } else {
+                argv[k++] = argv[j];
+            }
+        }
+        argc = k;
+    }
     int stages = argc > 2 ? atoi(argv[2]) : 5;
     const bool host_only = stages <= 0;
     const uint32_t tstride = !host_only && argc > 4 ? uint32_t(atoi(argv[3])) : 1u,
@@ -59,7 +77,9 @@ int main(int argc, char **argv) {
             more[k] = parse_heic(more_data[k].data(), more_data[k].size());
             ims.push_back(&more[k]);
         }
-        hb = build_batch(ims.data(), ims.size(), tstride, toff);
+        std::vector<Rect> rects(ims.size());
+        rects[0] = want;
+        hb = build_batch(ims.data(), ims.size(), tstride, toff, false, have_rect ? rects.data() : nullptr);
     } catch (const std::exception &e) {
         printf("host rejected: %s\n", e.what());
         return 3;
@@ -154,6 +174,7 @@ int main(int argc, char **argv) {
     std::fill(status.begin(), status.end(), 0x5au);
     std::fill(xprog.begin(), xprog.end(), 0x7777u);
     std::fill(xntu.begin(), xntu.end(), 0x3333u);
+    printf("pictures: %zu\n", hb.pics.size());
     emu_rbsp(a);
     emu_parse(a);
     uint32_t st = 0;
@@ -234,6 +255,23 @@ int main(int argc, char **argv) {
         return 1;
     }
     long bad_total = 0;
+    // rect=: the luma samples the selected pictures show (a child shows through its assembly)
+    std::vector<uint8_t> shown;
+    if (have_rect) {
+        shown.assign(size_t(W) * H, 0);
+        for (const PicDesc &pd : hb.pics) {
+            if (pd.flags & PD_CHILD) continue;
+            const SeqParams &sp = hb.seqs[pd.seq];
+            for (int y = std::max(pd.out_y, 0); y < std::min(pd.out_y + sp.out_h, H); ++y)
+                for (int x = std::max(pd.out_x, 0); x < std::min(pd.out_x + sp.out_w, W); ++x) shown[size_t(y) * W + x] = 1;
+        }
+        long uncovered = 0;
+        for (uint32_t y = want.y; y < want.y + want.h; ++y)
+            for (uint32_t x = want.x; x < want.x + want.w; ++x) uncovered += !shown[size_t(y) * W + x];
+        printf("rect %u,%u %ux%u: %ld samples not covered by the selected pictures\n", want.x, want.y, want.w, want.h,
+               uncovered);
+        bad_total += uncovered;
+    }
     const char *names[3] = {"Y", "Cb", "Cr"};
     for (int c = 0; c < 3; ++c) {
         const uint8_t *g = c == 0 ? oy.data() : (c == 1 ? ocb.data() : ocr.data());
@@ -245,9 +283,9 @@ int main(int argc, char **argv) {
             for (int x = 0; x < pw; ++x) {
                 int gv = bps == 1 ? g[size_t(y) * pw + x] : reinterpret_cast<const uint16_t *>(g)[size_t(y) * pw + x];
                 const uint32_t tile = uint32_t((y << sy) / int(im.tile_height)) * im.cols + uint32_t((x << sx) / int(im.tile_width));
-                const int want = tile % tstride == toff ? int(ref.plane[c][size_t(y) * pw + x])
-                                                        : (bps == 1 ? kSentinel : kSentinel * 0x101);
-                if (gv != want) {
+                const bool sel = have_rect ? shown[size_t(y << sy) * W + (x << sx)] != 0 : tile % tstride == toff;
+                const int exp = sel ? int(ref.plane[c][size_t(y) * pw + x]) : (bps == 1 ? kSentinel : kSentinel * 0x101);
+                if (gv != exp) {
                     if (!bad) fx = x, fy = y;
                     ++bad;
                 }

@@ -75,10 +75,63 @@ void fill_scaling(const ParamSet &ps, uint8_t *blk) {
     }
 }
 
+// [x, x + w) x [y, y + h) meets r (neither empty; r not "everything")
+bool meets(const Rect &r, int64_t x, int64_t y, int64_t w, int64_t h) {
+    return w > 0 && h > 0 && x < int64_t(r.x) + r.w && int64_t(r.x) < x + w && y < int64_t(r.y) + r.h &&
+           int64_t(r.y) < y + h;
+}
+
 }  // namespace
 
+bool rect_inside(const Rect &r, uint32_t W, uint32_t H) {
+    if (r.everything()) return true;
+    return r.w && r.h && r.x < W && r.y < H && r.w <= W - r.x && r.h <= H - r.y;
+}
+
+bool window_source_rect(const ParsedImage &im, const Rect &window, Rect &src) {
+    const DisplayMap &d = im.display;
+    Rect w = window;
+    if (w.everything()) w = Rect{0, 0, d.out_width, d.out_height};
+    if (!rect_inside(w, d.out_width, d.out_height) || w.everything()) return false;
+    // the map is a signed permutation: the box of two opposite corners is the box of the window
+    const int64_t ox[2] = {int64_t(w.x), int64_t(w.x) + w.w - 1}, oy[2] = {int64_t(w.y), int64_t(w.y) + w.h - 1};
+    int64_t x0 = 0, x1 = 0, y0 = 0, y1 = 0;
+    for (int c = 0; c < 2; ++c) {
+        const int64_t x = d.m[0] * ox[c] + d.m[1] * oy[c] + d.t[0], y = d.m[2] * ox[c] + d.m[3] * oy[c] + d.t[1];
+        x0 = c ? std::min(x0, x) : x;
+        x1 = c ? std::max(x1, x) : x;
+        y0 = c ? std::min(y0, y) : y;
+        y1 = c ? std::max(y1, y) : y;
+    }
+    const int64_t W = im.out_width, H = im.out_height;
+    if (x0 < 0 || y0 < 0 || x1 >= W || y1 >= H) return false;  // (parse_heic keeps the map inside)
+    const int cf = im.params.empty() ? 0 : im.params[0].sps.chroma_array_type();
+    const int64_t mx = cf ? (int64_t(1) << chroma_sx(cf)) - 1 : 0, my = cf ? (int64_t(1) << chroma_sy(cf)) - 1 : 0;
+    x0 &= ~mx;
+    y0 &= ~my;
+    x1 = std::min(x1 | mx, W - 1);
+    y1 = std::min(y1 | my, H - 1);
+    src = Rect{uint32_t(x0), uint32_t(y0), uint32_t(x1 - x0 + 1), uint32_t(y1 - y0 + 1)};
+    return true;
+}
+
+void tiles_for_rect(const ParsedImage &im, const Rect &src, uint32_t &col0, uint32_t &row0, uint32_t &cols,
+                    uint32_t &rows) {
+    if (src.everything() || !im.tile_width || !im.tile_height) {
+        col0 = row0 = 0;
+        cols = im.cols;
+        rows = im.rows;
+        return;
+    }
+    // (a tile's visible part is its cell clipped to the image, and src lies inside the image)
+    col0 = std::min(src.x / im.tile_width, im.cols - 1);
+    row0 = std::min(src.y / im.tile_height, im.rows - 1);
+    cols = std::min((src.x + src.w - 1) / im.tile_width, im.cols - 1) - col0 + 1;
+    rows = std::min((src.y + src.h - 1) / im.tile_height, im.rows - 1) - row0 + 1;
+}
+
 HostBatch build_batch(const ParsedImage *const *imgs, size_t n, uint32_t tile_stride, uint32_t tile_offset,
-                      bool defer_bits) {
+                      bool defer_bits, const Rect *rects) {
     if (tile_stride == 0) tile_stride = 1;
     if (tile_offset >= tile_stride) throw HeifError("tile_offset must be below tile_stride");
     HostBatch hb;
@@ -160,8 +213,15 @@ HostBatch build_batch(const ParsedImage *const *imgs, size_t n, uint32_t tile_st
         } else if (hb.bps != bps || hb.chroma != s0.chroma_array_type()) {
             throw UnsupportedError("a batch must share bit depth and chroma format");
         }
+        // window decode: the image's rectangle (nullptr: every picture is taken)
+        const Rect *want = rects && !rects[i].everything() ? &rects[i] : nullptr;
+        if (want && !rect_inside(*want, im.out_width, im.out_height))
+            throw HeifError("source rectangle empty or outside the image");
         for (size_t t = tile_offset; t < im.tiles.size(); t += tile_stride) {
             const TileJob &tj = im.tiles[t];
+            if (want && !meets(*want, int64_t(t % im.cols) * im.tile_width, int64_t(t / im.cols) * im.tile_height,
+                               im.tile_width, im.tile_height))
+                continue;  // (nothing of it in hb.pieces: it is not uploaded either)
             const ParamSet &ps = im.params[size_t(tj.param)];
             // A coded picture decodes as one or more independent sub-pictures
             // (heic_image.cpp accepts only layouts where nothing crosses their
@@ -249,6 +309,11 @@ HostBatch build_batch(const ParsedImage *const *imgs, size_t n, uint32_t tile_st
                     vis_dx = vx0 - ps.sps.conf_win_left;
                     vis_dy = vy0 - ps.sps.conf_win_top;
                     if (su.subset_end) base.flags |= SP_SUBSET_END;
+                    // window decode: an independent sub-picture nobody reads (an assembly is
+                    // taken whole; the substreams were counted above, in subs_of)
+                    if (want && !assemble && !meets(*want, int64_t(grid_x) + vis_dx, int64_t(grid_y) + vis_dy,
+                                                    base.out_w, base.out_h))
+                        continue;
                 }
                 const uint32_t seq = seq_of(ps, base);
                 const SeqParams &sq = hb.seqs[seq];

@@ -33,10 +33,34 @@ struct HostBatch {
     bool has_assembly = false;        // some picture is a PD_ASSEMBLY (BatchArgs::has_assembly)
 };
 
+// A rectangle of samples; w == 0 && h == 0 stands for "everything".
+struct Rect {
+    uint32_t x = 0, y = 0, w = 0, h = 0;
+    bool everything() const { return w == 0 && h == 0; }
+};
+
+// Window decode, exact integers, host only.
+// rect_inside: r is "everything", or a non-empty rectangle inside W x H.
+bool rect_inside(const Rect &r, uint32_t W, uint32_t H);
+// The decoded samples of `im` that a render of `window` (displayed coordinates;
+// "everything": the whole displayed picture) reads: the bounding box of the display
+// map over the window's opposite corners, grown to the chroma sample grid (the
+// render replicates chroma, so a luma sample reads its chroma sample's whole cell)
+// and clipped to the image.  False if the window is not inside the displayed picture.
+bool window_source_rect(const ParsedImage &im, const Rect &window, Rect &src);
+// The grid tiles whose visible part meets src (rect_inside the image): columns
+// [col0, col0 + cols), rows [row0, row0 + rows).
+void tiles_for_rect(const ParsedImage &im, const Rect &src, uint32_t &col0, uint32_t &row0, uint32_t &cols,
+                    uint32_t &rows);
+
 // Throws HeifError / UnsupportedError.  Only grid tiles k (row-major) with
 // k % tile_stride == tile_offset become pictures (the single-image tile split
-// across GPUs); the default takes every tile.
+// across GPUs); the default takes every tile.  rects (nullptr:
+// everything) holds one rectangle per image in decoded-plane coordinates, each
+// rect_inside its image: a picture (a grid tile; inside a coded picture each
+// independent sub-picture; an assembly with all its children) is taken only if
+// its visible rectangle in the output planes meets the image's rectangle.
 HostBatch build_batch(const ParsedImage *const *imgs, size_t n, uint32_t tile_stride = 1, uint32_t tile_offset = 0,
-                      bool defer_bits = false);
+                      bool defer_bits = false, const Rect *rects = nullptr);
 
 }  // namespace hg

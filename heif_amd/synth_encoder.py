@@ -225,7 +225,8 @@ def _assemble(items: List[Tuple[int, bytes, bytes]], primary: int, props: List[b
               assoc: List[Tuple[int, List[int]]], iref: bytes, idat: bytes,
               layout: Optional[BoxLayout] = None) -> bytes:
     """items: (item_id, item_type, data); data of 'grid' items lives in idat
-    (construction_method 1), everything else in mdat."""
+    (construction_method 1; `idat` holds the grid items' data back to back in
+    item order), everything else in mdat."""
     L = layout or BoxLayout()
     ftyp = _box(b"ftyp", b"heic" + struct.pack(">I", 0) + b"mif1heic")
     hdlr = _fbox(b"hdlr", 0, 0, struct.pack(">I", 0) + b"pict" + bytes(12) + b"\0")
@@ -259,11 +260,13 @@ def _assemble(items: List[Tuple[int, bytes, bytes]], primary: int, props: List[b
         os_, ls_, bs_ = L.offset_size, L.length_size, L.base_offset_size
         ent = struct.pack(">BBH", (os_ << 4) | ls_, bs_ << 4, len(items))
         off = mdat_start
+        ioff = 0
         body = b""
         for iid, typ, data in items:
             if typ == b"grid":
-                ent += struct.pack(">HHH", iid, 1, 0) + _be(0, bs_) + struct.pack(">H", 1) + _be(0, os_) + \
+                ent += struct.pack(">HHH", iid, 1, 0) + _be(0, bs_) + struct.pack(">H", 1) + _be(ioff, os_) + \
                     _be(len(data), ls_)
+                ioff += len(data)
             else:
                 n = max(1, min(L.extents, len(data)))
                 cuts = [len(data) * k // n for k in range(n + 1)]
@@ -290,9 +293,17 @@ def _len_prefixed(nal: bytes) -> bytes:
 
 
 def grid_heic(out_w: int, out_h: int, p: SynthParams, seed: int = 0, pictures: Optional[List[bytes]] = None,
-              layout: Optional[BoxLayout] = None) -> bytes:
+              layout: Optional[BoxLayout] = None, transforms: Tuple[bytes, ...] = (), colr: Optional[bytes] = None,
+              aux: Tuple["AuxImage", ...] = ()) -> bytes:
     """A grid HEIC of ceil(out_w/W) x ceil(out_h/H) synthetic tiles of p's
-    size, tile k drawn with seed (seed << 16) + k."""
+    size, tile k drawn with seed (seed << 16) + k.  `colr` (nclx_box) and then
+    `transforms` (clap_box / irot_box / imir_box, applied in the order given) are
+    appended to the grid item's property association, as in display_heic.  Every
+    `aux` entry (an AuxImage) becomes a grid item of its own over the same
+    out_w x out_h, cut into tiles of ITS params' size (tile k drawn with seed
+    (a.seed << 16) + k), with auxC and an 'auxl' reference to the primary grid
+    ('prem' from the primary when premultiplied).  With the defaults the file is
+    byte for byte what it was before these arguments existed."""
     cols = -(-out_w // (p.width - p.conf_right))
     rows = -(-out_h // (p.height - p.conf_bottom))
     n = rows * cols
@@ -306,10 +317,34 @@ def grid_heic(out_w: int, out_h: int, p: SynthParams, seed: int = 0, pictures: O
     items = [(grid_id, b"grid", struct.pack(">BBBBHH", 0, 0, rows - 1, cols - 1, out_w, out_h))]
     for k in range(n):
         items.append((k + 2, b"hvc1", items_data[k]))
-    assoc = [(grid_id, [3])] + [(k + 2, [1, 2]) for k in range(n)]
-    iref = _fbox(b"iref", 0, 0, _box(b"dimg", struct.pack(">HH", grid_id, n) +
-                                     b"".join(struct.pack(">H", k + 2) for k in range(n))))
-    return _assemble(items, grid_id, props, assoc, iref, items[0][2], layout)
+    grid_idx = [3]
+    for box in ([colr] if colr else []) + list(transforms):
+        props.append(box)
+        grid_idx.append(len(props))
+    assoc = [(grid_id, grid_idx)] + [(k + 2, [1, 2]) for k in range(n)]
+    refs = _box(b"dimg", struct.pack(">HH", grid_id, n) + b"".join(struct.pack(">H", k + 2) for k in range(n)))
+    idat = items[0][2]
+    next_id = n + 2
+    for a in aux:
+        q = a.params
+        qw, qh = q.width - q.conf_right, q.height - q.conf_bottom
+        acols, arows = -(-out_w // qw), -(-out_h // qh)
+        an = acols * arows
+        aid, next_id = next_id, next_id + 1 + an
+        props += [hvcc(q, *parameter_sets(q)), _ispe(qw, qh), auxc_box(a.urn)]
+        tile_idx = [len(props) - 2, len(props) - 1]
+        items.append((aid, b"grid", struct.pack(">BBBBHH", 0, 0, arows - 1, acols - 1, out_w, out_h)))
+        idat += items[-1][2]
+        assoc.append((aid, [3, len(props)]))
+        for k in range(an):
+            items.append((aid + 1 + k, b"hvc1", picture_item(q, (a.seed << 16) + k)))
+            assoc.append((aid + 1 + k, tile_idx))
+        refs += _box(b"dimg", struct.pack(">HH", aid, an) + b"".join(struct.pack(">H", aid + 1 + k) for k in range(an)))
+        refs += _box(b"auxl", struct.pack(">HHH", aid, 1, grid_id))
+        if a.premultiplied:
+            refs += _box(b"prem", struct.pack(">HHH", grid_id, 1, aid))
+    iref = _fbox(b"iref", 0, 0, refs)
+    return _assemble(items, grid_id, props, assoc, iref, idat, layout)
 
 
 def single_heic(p: SynthParams, seed: int = 0, layout: Optional[BoxLayout] = None,

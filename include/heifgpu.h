@@ -405,6 +405,67 @@ int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *im
                                 const heifgpu_tensor_format *fmt, const heifgpu_scale *scale,
                                 const uint32_t *flip, const heifgpu_tensor_surface *out, void *stream);
 
+/* ---- window decode: decode only the pictures a window reads ----------------
+ * (added within ABI 6: new entry points only; heifgpu_batch_opts keeps its layout.)
+ * A render of a window of the displayed picture (heifgpu_scale's x, y, width,
+ * height) reads a rectangle of the decoded planes, the SOURCE RECTANGLE:
+ *   - the window is taken by heifgpu_scale's rules (0, 0 sizes: the whole
+ *     displayed picture; otherwise non-empty and inside out_width x out_height,
+ *     else HEIFGPU_E_INVALID);
+ *   - its two opposite corners go through the display map (m, t of
+ *     heifgpu_display_info); their bounding box is the box of the whole window,
+ *     m being a signed permutation;
+ *   - the box is grown to the chroma sample grid (x0 down and x1 up to multiples
+ *     of SubWidthC, y likewise with SubHeightC; 4:0:0 and 4:4:4 grow nothing),
+ *     because the render replicates chroma: a luma sample reads the chroma sample
+ *     of its cell;
+ *   - and clipped to width x height (heifgpu_image_info).
+ * That is exactly the set of decoded samples heifgpu_render_batch (whole
+ * picture), heifgpu_render_batch_scaled and heifgpu_render_batch_tensor read for
+ * that window (a flip reads the same samples).
+ * SELECTION, one rule at every level: a picture of the batch is decoded iff its
+ * visible rectangle in the output planes (its placement clipped to the image)
+ * intersects the source rectangle.  "Picture" is a grid tile and, inside a coded
+ * picture, each independent sub-picture the decode splits it into: an HEVC tile
+ * or a row band of a slice with no loop filter across the boundaries.  Pictures
+ * filtered across their boundaries (the children of an assembly) are taken all
+ * or none: if any sample of the coded picture is needed it is decoded whole.  A
+ * skipped picture costs no upload, no parse and no reconstruction.
+ * heifgpu_batch_prepare_rects is heifgpu_batch_prepare_ex with one rectangle per
+ * image, src[i], in DECODED-PLANE coordinates (not displayed ones): what
+ * heifgpu_window_source_rect returns.  An alpha or other auxiliary image is
+ * given its colour image's source rectangle (the render addresses it through
+ * the colour image's map) and selects by its own tile grid.  src == NULL, or
+ * src[i] with width == 0 && height == 0, decodes everything as
+ * heifgpu_batch_prepare_ex does (which is this call with src == NULL).  A
+ * rectangle that is empty otherwise or not inside width x height is
+ * HEIFGPU_E_INVALID, reported before anything is uploaded or launched; a batch
+ * being reloaded then keeps its contents and stays decodable.  The selection
+ * combines with tile_stride / tile_offset: a grid tile must pass both.  After a
+ * decode every sample of src[i] has been written; samples outside it may or may
+ * not have been (whole pictures are written), nothing outside the caller's
+ * planes is touched.  Status words, heifgpu_batch_status_previous, the parse
+ * mode chosen by picture count, heifgpu_batch_parse_geometry and
+ * heifgpu_batch_lanes_variant all speak of the pictures selected. */
+typedef struct { uint32_t x, y, width, height; } heifgpu_rect;  /* width == 0 && height == 0: everything */
+/* host only: the source rectangle of `window` (NULL: the whole displayed picture) */
+int heifgpu_window_source_rect(const heifgpu_image *img, const heifgpu_rect *window, heifgpu_rect *src);
+/* host only: the grid tiles a source rectangle selects (src NULL: everything):
+ * columns [col0, col0 + cols), rows [row0, row0 + rows); cols * rows tiles.  Any
+ * of the four pointers may be NULL.  1 x 1 for a single coded item. */
+int heifgpu_image_tiles_for_rect(const heifgpu_image *img, const heifgpu_rect *src,
+                                 uint32_t *col0, uint32_t *row0, uint32_t *cols, uint32_t *rows);
+int heifgpu_batch_prepare_rects(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                const heifgpu_batch_opts *opts, const heifgpu_rect *src,
+                                heifgpu_batch **inout);
+/* host only, no device: the number of pictures heifgpu_batch_prepare_rects would
+ * make of these arguments (sub-pictures and assemblies counted as the decode
+ * counts them), so a loader can size a batch of crops before it prepares it. */
+int heifgpu_batch_count_pictures(const heifgpu_image *const *imgs, size_t n, const heifgpu_batch_opts *opts,
+                                 const heifgpu_rect *src, uint32_t *pictures);
+/* the pictures of a prepared batch */
+int heifgpu_batch_picture_count(const heifgpu_batch *batch, uint32_t *pictures);
+
 /* ---- host test hooks (reference unit-test surface) -------------------- */
 size_t heifgpu_remove_emulation_prevention(const uint8_t *in, size_t n, uint8_t *out); /* rbsp_reader.rs:11-39 */
 int heifgpu_read_ue(const uint8_t *buf, size_t n, uint32_t *val);                      /* rbsp_reader.rs:87-99 */
