@@ -214,6 +214,9 @@ struct ParseSet {
     DevBuf<TuRec> tus;
     DevBuf<Coef> coefs;
     DevBuf<uint32_t> row_counts, status;
+    // lanes parse: a word per CU and the words of every CTB row (BatchArgs::cus); k_paint_flags
+    // paints the QpY map from them.  As large as the QpY maps padded to whole CTBs.
+    DevBuf<uint32_t> cus, cu_counts;
     DevBuf<uint8_t> maps;
     DevBuf<SaoParams> sao;
     DevBuf<int16_t> resid;  // k_transform -> k_intra
@@ -1064,7 +1067,9 @@ int heifgpu_batch_prepare_rects(heifgpu_ctx *ctx, const heifgpu_image *const *im
                                      hb.sao_n > b->set[0].sao.cap || 2 * size_t(hb.rows) > b->set[0].row_counts.cap ||
                                      hb.pics.size() > b->set[0].status.cap || hb.pics.size() > G.sticky.cap ||
                                      (cross_rows && (xprog_words(hb) > b->set[0].xprog.cap || hb.rows * CTX_PAD > b->xctx.cap)) ||
-                                     (mode == PARSE_SPREAD && xntu_words(hb) > b->set[0].xntu.cap));
+                                     (mode == PARSE_SPREAD && xntu_words(hb) > b->set[0].xntu.cap) ||
+                                     (mode == PARSE_LANES && (cu_list_off(hb.sao_n, hb.max_log2ctb) > b->set[0].cus.cap ||
+                                                              size_t(hb.rows) > b->set[0].cu_counts.cap)));
     if (grows) {  // reallocation: every decode of the old contents fully drained
         for (int k = 0; k < b->n_sets; ++k)
             if (b->set[k].pending) HIP_TRY(hipEventSynchronize(b->set[k].recon_done));
@@ -1092,6 +1097,10 @@ int heifgpu_batch_prepare_rects(heifgpu_ctx *ctx, const heifgpu_image *const *im
         HIP_TRY(ps.tus.alloc(hb.tu_n));
         HIP_TRY(ps.coefs.alloc(hb.coef_n));
         HIP_TRY(ps.row_counts.alloc(size_t(2) * hb.rows));
+        if (mode == PARSE_LANES) {
+            HIP_TRY(ps.cus.alloc(cu_list_off(hb.sao_n, hb.max_log2ctb)));
+            HIP_TRY(ps.cu_counts.alloc(hb.rows));
+        }
         HIP_TRY(ps.maps.alloc(hb.map_bytes));
         HIP_TRY(ps.sao.alloc(hb.sao_n));
         HIP_TRY(ps.status.alloc(hb.pics.size()));
@@ -1252,6 +1261,8 @@ int heifgpu_batch_decode(heifgpu_ctx *ctx, heifgpu_batch *b, const heifgpu_plane
     a.tus = ps.tus.p;
     a.coefs = ps.coefs.p;
     a.row_counts = ps.row_counts.p;
+    a.cus = a.parse_mode == PARSE_LANES ? ps.cus.p : nullptr;
+    a.cu_counts = a.parse_mode == PARSE_LANES ? ps.cu_counts.p : nullptr;
     a.maps = ps.maps.p;
     a.sao = ps.sao.p;
     a.status = ps.status.p;
@@ -1277,6 +1288,7 @@ int heifgpu_batch_decode(heifgpu_ctx *ctx, heifgpu_batch *b, const heifgpu_plane
         HIP_TRY(hipStreamSynchronize(ctx->recon));
         HIP_TRY(hipMemsetAsync(ps.status.p, 0, size_t(b->n_pics) * sizeof(uint32_t), s));
         HIP_TRY(hipMemsetAsync(ps.row_counts.p, 0, size_t(2) * uint32_t(b->args.total_rows) * sizeof(uint32_t), s));
+        if (a.cu_counts) HIP_TRY(hipMemsetAsync(a.cu_counts, 0, uint32_t(b->args.total_rows) * sizeof(uint32_t), s));
         HIP_TRY(launch_rbsp(a, s));
         hipError_t (*fns[5])(const BatchArgs &, hipStream_t) = {launch_parse, launch_transform, launch_intra,
                                                                 launch_deblock, launch_sao_out};

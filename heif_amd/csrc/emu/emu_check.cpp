@@ -87,6 +87,9 @@ int main(int argc, char **argv) {
     std::vector<TuRec> tus(hb.tu_n);
     std::vector<Coef> coefs(hb.coef_n);
     std::vector<uint32_t> rc(2 * hb.rows), status(hb.pics.size());
+    // the lanes parse's CU lists, exactly as large as the library allocates them (the
+    // sanitizer build reports a word stored past them); stale words of an earlier decode
+    std::vector<uint32_t> cus(cu_list_off(hb.sao_n, hb.max_log2ctb), 0xa5a5a5a5u), cu_counts(hb.rows);
     std::vector<uint8_t> recon(hb.recon_bytes), maps(hb.map_bytes);
     if (getenv("HEIFGPU_EMU_DUMP_MAPS")) std::fill(maps.begin(), maps.end(), uint8_t(0xa5));  // (a byte nobody wrote shows)
     std::vector<int16_t> resid(hb.resid_elems);
@@ -132,6 +135,8 @@ int main(int argc, char **argv) {
     a.tus = tus.data();
     a.coefs = coefs.data();
     a.row_counts = rc.data();
+    a.cus = cus.data();
+    a.cu_counts = cu_counts.data();
     a.recon = recon.data();
     a.resid = resid.data();
     a.maps = maps.data();
@@ -171,6 +176,7 @@ int main(int argc, char **argv) {
     // k_rbsp zeroes the decode's status words, row counts, progress words and TU
     // counts: start them as garbage, as a reused parse-output set holds them
     std::fill(rc.begin(), rc.end(), 0xa5a5a5a5u);
+    std::fill(cu_counts.begin(), cu_counts.end(), 0xa5a5a5a5u);
     std::fill(status.begin(), status.end(), 0x5au);
     std::fill(xprog.begin(), xprog.end(), 0x7777u);
     std::fill(xntu.begin(), xntu.end(), 0x3333u);

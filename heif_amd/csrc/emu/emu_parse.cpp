@@ -117,7 +117,9 @@ void emu_parse_lanes(const BatchArgs &a) {
             printf("\n  sb_paths");
             for (int k = COV_N; k < COV_SB_END; ++k) printf(" %ld", g_cov[k]), g_cov[k] = 0;
             printf("\n  tb_paths");
-            for (int k = COV_SB_END; k < COV_ALL; ++k) printf(" %ld", g_cov[k]), g_cov[k] = 0;
+            for (int k = COV_SB_END; k < COV_TB_END; ++k) printf(" %ld", g_cov[k]), g_cov[k] = 0;
+            printf("\n  cu_paths");
+            for (int k = COV_TB_END; k < COV_ALL; ++k) printf(" %ld", g_cov[k]), g_cov[k] = 0;
             printf("\n");
         }
     }

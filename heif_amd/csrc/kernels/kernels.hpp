@@ -67,9 +67,26 @@ struct BatchArgs {
     int intra_split;           // k_intra: luma and chroma on separate waves (set by launch_intra)
     // (added last: every other kernel's argument offsets, and so its code, stay as they were)
     int lanes_lean;            // lanes parse: the lean tool set's body (lanes_variant_for; LANES_*)
-    int flags_from_recs;       // the edge / no-filter map is painted from the luma TuRecs after the parse (k_paint_flags:
-                               // the lanes parse leaves it out); 0: the parse wrote it (solo / spread)
+    // the lanes parse's CU lists: a word per CU (cu_word), CTB row r of a picture at word
+    // cu_list_off(sao_off, max_log2ctb) + r * cu_cap_row(wctb, log2_ctb), and the words of every row
+    // (indexed like row_counts / 2; k_rbsp and the decode's memset clear them with the row counts)
+    uint32_t *cus;
+    uint32_t *cu_counts;
+    int flags_from_recs;       // the edge / no-filter map is painted from the luma TuRecs and the QpY map from the
+                               // CU lists after the parse (k_paint_flags: the lanes parse leaves both out); 0: the
+                               // parse wrote them (solo / spread)
 };
+
+// CU list geometry.  CUs are at least 8x8 and disjoint, so a CTB row holds at most
+// wctb * (ctb / 8)^2 of them; a picture's lists start at its first CTB's index (PicDesc::sao_off,
+// every picture's CTBs counted) times the batch's largest (ctb / 8)^2, which leaves each picture
+// at least its own rows' room.  The arena is as large as the QpY maps padded to whole CTBs.
+constexpr uint32_t cu_cap_row(int wctb, int log2ctb) { return (uint32_t)wctb << (2 * (log2ctb - 3)); }
+constexpr uint64_t cu_list_off(uint64_t sao_off, int max_log2ctb) { return sao_off << (2 * (max_log2ctb - 3)); }
+// a CU's word: x >> 3 (bits 0-15), its 8x8 row inside the CTB row (16-19), log2 size (20-23), QpY (24-31)
+constexpr uint32_t cu_word(int x, int y_in_row, int log2, int qpy) {
+    return (uint32_t)(x >> 3) | ((uint32_t)(y_in_row >> 3) << 16) | ((uint32_t)log2 << 20) | ((uint32_t)qpy << 24);
+}
 
 // k_ycbcr_rgb (color.hip): one decoded image → interleaved RGB8, rotated
 struct ColorArgs {

@@ -9,6 +9,7 @@
 #include "tables.hpp"
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -100,6 +101,9 @@ struct alignas(16) LaneLds {
     uint8_t dL[8], dA[8];        // CtDepth (8x8 units)
     int8_t qL[8], qA[8];         // QpY (8x8 units)
 };
+// (the vector engines update a CU's or PB's segment of these lines as a masked 64-bit word)
+static_assert(offsetof(LaneLds, ipmL) % 8 == 0 && offsetof(LaneLds, ipmA) % 8 == 0, "64-bit line updates");
+static_assert(offsetof(LaneLds, dL) % 8 == 0 && offsetof(LaneLds, dA) % 8 == 0, "64-bit line updates");
 
 // picture constants and output pointers (LDS, one per picture of the wave)
 struct LanePic {
@@ -112,6 +116,10 @@ struct LanePic {
     // global memory, said so in the type: a generic pointer loaded from LDS
     // would make every store through it a flat store, and flat stores count in
     // lgkmcnt, so each later LDS read of the wave would wait for them
+    // (gqpy: the scalar engines' QpY map, whose rows they write.  The vector engines keep
+    // the picture's CU list in the slot instead, lane_cus: they append a word per CU and
+    // k_paint_flags paints the rows from the words.  One slot, one type: the struct, and
+    // with it the scalar engines' code, stay what they were)
     int8_t HG_GAS *gqpy;
     uint8_t HG_GAS *gflags;
     uint8_t HG_GAS *gdepth;
@@ -119,6 +127,7 @@ struct LanePic {
     TuRec HG_GAS *tu_base;
     Coef HG_GAS *coef_base;
 };
+HG_HD inline uint32_t HG_GAS *lane_cus(const LanePic &P) { return (uint32_t HG_GAS *)P.gqpy; }
 
 // syntax units (Lane.st)
 enum Unit : int {
@@ -208,6 +217,7 @@ struct Lane {
     int rc_scan, rc_last_sub, rc_last_pos, rc_i, rc_prev_c1;
     uint64_t rc_csbf;  // coded_sub_block_flag, bit yS * 8 + xS
     uint32_t ntu, ncoef;
+    uint32_t ncu;               // vector engines: CU words of the row (the picture's CU list, cu_done)
     uint32_t nesc;              // escape levels of the row (stored down from the end of its coefficient space)
     uint32_t tu_row, coef_row;  // TuRec / Coef index of the current row's outputs
     // solo mode on the GPU: the context states, byte i of the LDS layout at
@@ -235,11 +245,19 @@ struct Lane {
 // `make prof-tb` (HG_PARSE_PROF_TB on top of the prof-sb build) times the tree and
 // TB units' phases into the same six slots instead of the sub-block unit's: 0 the
 // TB unit up to the last position, 1 the last-position prefix bins, 2 suffixes and
-// scan set-up, 3 the transform-tree unit up to its map rows, 4 the flag-map rows,
-// 5 the QpY rows of a finished CU (tools/wave_times.py names them)
-#if defined(HG_PARSE_PROF_SB) && !defined(HG_HOST_EMU) && !defined(HG_PARSE_PROF_TB)
+// scan set-up, 3 the transform-tree unit (its map rows included: nothing in the
+// vector engines since r13), 4 the QpY lines of a finished CU (LDS), 5 its QpY map
+// rows or CU word (global) (tools/wave_times.py names them)
+// `make prof-cu` (HG_PARSE_PROF_CU on top of the prof-sb build) times the coding
+// quadtree and CU units there instead: 0 the quadtree unit, 1 the CU unit up to its
+// CtDepth lines, 2 the CtDepth lines, 3 the prev_intra and mode bins, 4 the luma
+// mode derivations with the IntraPredModeY lines, 5 the chroma mode
+#if defined(HG_PARSE_PROF_TB) && defined(HG_PARSE_PROF_CU)
+#error "prof-tb and prof-cu share the six phase slots: one of them per build"
+#endif
+#if defined(HG_PARSE_PROF_SB) && !defined(HG_HOST_EMU) && !defined(HG_PARSE_PROF_TB) && !defined(HG_PARSE_PROF_CU)
 #define HG_SB_T(L, i, t0) HG_PHASE_T(L, i, t0)
-#elif defined(HG_PARSE_PROF_TB) && !defined(HG_HOST_EMU)
+#elif (defined(HG_PARSE_PROF_TB) || defined(HG_PARSE_PROF_CU)) && !defined(HG_HOST_EMU)
 #define HG_SB_T(L, i, t0) ((void)(t0))
 #else
 #define HG_SB_T(L, i, t0) ((void)0)
@@ -250,6 +268,13 @@ struct Lane {
 #else
 #define HG_TB_T0(t0) ((void)0)
 #define HG_TB_T(L, i, t0) ((void)0)
+#endif
+#if defined(HG_PARSE_PROF_CU) && !defined(HG_HOST_EMU)
+#define HG_CU_T0(t0) uint64_t t0 = __builtin_amdgcn_s_memtime()
+#define HG_CU_T(L, i, t0) HG_PHASE_T(L, i, t0)
+#else
+#define HG_CU_T0(t0) ((void)0)
+#define HG_CU_T(L, i, t0) ((void)0)
 #endif
 
 // Emulation only (HEIFGPU_LANES_STATS prints them per wave): how often the parse
@@ -293,7 +318,10 @@ enum Cov : int {
     COV_LAST_SUFFIX_X_ONLY,    // a suffix on the x axis alone
     COV_LAST_SUFFIX_Y_ONLY,    // and on the y axis alone
     COV_LAST_SWAP,             // vertical scan: the two positions swapped
-    COV_ALL
+    COV_TB_END,
+    // the end of a CU (tests/lanes_culist_cases.py), on a `cu_paths` line
+    COV_CU_DONE = COV_TB_END,  // + log2 - 3: CUs of 8, 16, 32 and 64 samples that reached cu_done
+    COV_ALL = COV_CU_DONE + 4
 };
 #if defined(HG_HOST_EMU)
 long g_cov[COV_ALL];

@@ -48,7 +48,7 @@ HG_HD inline void derive_qp_pred(Lane &L, const LaneLds &ld, const LanePic &P) {
     L.qp_pred = (qa + qb + 1) >> 1;
 }
 
-// 8.4.2 luma intra prediction mode of the PB at (xPb, yPb)
+// 8.4.2 luma intra prediction mode of the PB at (xPb, yPb), its neighbours read from the lines
 HG_HD inline int derive_luma_mode(const Lane &L, const LaneLds &ld, int xPb, int yPb, int prev, int mpm_idx,
                                   int rem) {
     const int ca = xPb <= 0 ? 1 : ld.ipmL[(yPb - L.ctby) >> 2];
@@ -81,6 +81,74 @@ HG_HD inline int derive_luma_mode(const Lane &L, const LaneLds &ld, int xPb, int
     if (m >= l1) ++m;
     if (m >= l2) ++m;
     return m;
+}
+// the same from candIntraPredModeA / B themselves (the vector engines keep a CU's neighbours in
+// registers).  A copy, not the function above calling this one: its code in the scalar kernels changes otherwise
+HG_HD inline int luma_mode(int ca, int cb, int prev, int mpm_idx, int rem) {
+    int l0, l1, l2;
+    if (ca == cb) {
+        if (ca < 2) {
+            l0 = 0;
+            l1 = 1;
+            l2 = 26;
+        } else {
+            l0 = ca;
+            l1 = 2 + ((ca + 29) % 32);
+            l2 = 2 + ((ca - 2 + 1) % 32);
+        }
+    } else {
+        l0 = ca;
+        l1 = cb;
+        if (ca != 0 && cb != 0) l2 = 0;
+        else if (ca != 1 && cb != 1) l2 = 1;
+        else l2 = 26;
+    }
+    if (prev) return mpm_idx == 0 ? l0 : (mpm_idx == 1 ? l1 : l2);
+    int t;
+    if (l0 > l1) { t = l0; l0 = l1; l1 = t; }
+    if (l0 > l2) { t = l0; l0 = l2; l2 = t; }
+    if (l1 > l2) { t = l1; l1 = l2; l2 = t; }
+    int m = rem;
+    if (m >= l0) ++m;
+    if (m >= l1) ++m;
+    if (m >= l2) ++m;
+    return m;
+}
+
+// The vector engines update a CU's or PB's segment of the CtDepth and IntraPredModeY lines
+// (an aligned run of 1, 2, 4, 8 or 16 bytes) as a masked 64-bit word, not byte by byte: a
+// byte loop's trip count differs by lane, and every lane of the unit run waits for the
+// longest (the QpY lines stay byte loops, cu_done).  HG_LINE_BYTES (tuning
+// builds) keeps the byte loops of the lines named in its bits: 1 CtDepth, 2 IntraPredModeY.
+#if !defined(HG_LINE_BYTES)
+#define HG_LINE_BYTES 0
+#endif
+template <class EG>
+constexpr bool kLineWords(int which) { return !EG::kSolo && !(HG_LINE_BYTES & which); }
+HG_HD inline uint64_t line_ld(const void *line) {
+    uint64_t w;
+    __builtin_memcpy(&w, line, 8);
+    return w;
+}
+HG_HD inline void line_st(void *line, uint64_t w) { __builtin_memcpy(line, &w, 8); }
+// bytes [b0, b0 + nb) of an 8-byte line := v; nb = 1, 2, 4 or 8
+// (~0 >> (64 - 8 nb): no shift by 64 when the run fills the word)
+HG_HD inline void line8_fill(void *line, int b0, int nb, int v) {
+    const uint64_t m = (~0ull >> (64 - 8 * nb)) << (8 * b0);
+    line_st(line, (line_ld(line) & ~m) | ((0x0101010101010101ull * (uint8_t)v) & m));
+}
+// bytes [b0, b0 + nb / 2) of a 16-byte line := lo, [b0 + nb / 2, b0 + nb) := hi; nb = 2, 4, 8 or 16;
+// w: the word holding byte b0 as it is now (a 16-byte run fills both words)
+HG_HD inline void line16_fill(uint8_t *line, uint64_t w, int b0, int nb, int lo, int hi) {
+    const uint64_t rl = 0x0101010101010101ull * (uint8_t)lo, rh = 0x0101010101010101ull * (uint8_t)hi;
+    if (nb == 16) {
+        line_st(line, rl);
+        line_st(line + 8, rh);
+        return;
+    }
+    const int h = 4 * nb, sh = 8 * (b0 & 7);  // bits of a half (at most 32), of the run's offset
+    const uint64_t hm = (1ull << h) - 1, m = ~0ull >> (64 - 8 * nb);
+    line_st(line + (b0 & 8), (w & ~(m << sh)) | (((rl & hm) | ((rh & hm) << h)) << sh));
 }
 
 // 6.5.3-6.5.5 scans.  Packed 4-bit 2x2 / 4x4 scans (entry x | (y << 2)) are
@@ -375,6 +443,7 @@ HG_HD inline void unit_ctu(Lane &L, LaneLds &ld, LanePic &P, const Env &E, const
 // U_CQT: split_cu_flag descent (7.3.8.4) from the current node to a CU
 template <class EG>
 HG_HD inline void unit_cqt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
+    HG_CU_T0(tcq);
     for (;;) {
         const int n = 1 << L.ql;
         bool split;
@@ -401,9 +470,11 @@ HG_HD inline void unit_cqt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         --L.ql;  // child 0 (always inside the picture)
         ++L.qd;
     }
+    HG_CU_T(L, 0, tcq);
     L.st = U_CU;
 }
 
+template <class EG>
 HG_HD inline void cu_done(Lane &L, LaneLds &ld, LanePic &P);
 template <class EG>
 HG_HD inline void tu_emit(Lane &L, const LanePic &P);
@@ -422,9 +493,14 @@ HG_HD inline void pcm_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     const int n = 1 << L.ql;
     {
         const int nb = n >> 2, by = (L.qy - L.ctby) >> 2, bx = (L.qx - L.ctbx) >> 2;
-        for (int k = 0; k < nb; ++k) {
-            ld.ipmL[by + k] = 1;
-            ld.ipmA[bx + k] = 1;
+        if constexpr (kLineWords<EG>(2)) {
+            line16_fill(ld.ipmL, line_ld(ld.ipmL + (by & 8)), by, nb, 1, 1);
+            line16_fill(ld.ipmA, line_ld(ld.ipmA + (bx & 8)), bx, nb, 1, 1);
+        } else {
+            for (int k = 0; k < nb; ++k) {
+                ld.ipmL[by + k] = 1;
+                ld.ipmA[bx + k] = 1;
+            }
         }
     }
     // bits consumed so far: 8 * end - budget - k (absolute RBSP bit position)
@@ -477,12 +553,13 @@ HG_HD inline void pcm_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     } else {
         engine_init(L, G, next, P.bits_end);
     }
-    cu_done(L, ld, P);
+    cu_done<EG>(L, ld, P);
 }
 
 // U_CU: coding_unit (7.3.8.5) up to its transform_tree
 template <class EG>
 HG_HD inline void unit_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
+    HG_CU_T0(tcu);
     if (L.fl & F_QG_NEW) {
         derive_qp_pred(L, ld, P);
         L.fl &= ~F_QG_NEW;
@@ -493,14 +570,21 @@ HG_HD inline void unit_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
     if (L.ql == P.minCb && !dec(L, G, CTX_PART_MODE)) L.fl |= F_NXN;
     const bool nxn = (L.fl & F_NXN) != 0;
     const bool pcm = !nxn && (pic_flags<EG>(P) & SP_PCM) && L.ql >= P.pcmMin && L.ql <= P.pcmMax && term(L, G);
+    HG_CU_T(L, 1, tcu);
     {  // CtDepth of the CU
         const int nd = 1 << (L.ql - 3);
         const int dy = (L.qy - L.ctby) >> 3, dx = (L.qx - L.ctbx) >> 3;
-        for (int k = 0; k < nd; ++k) {
-            ld.dL[dy + k] = (uint8_t)L.qd;
-            ld.dA[dx + k] = (uint8_t)L.qd;
+        if constexpr (kLineWords<EG>(1)) {
+            line8_fill(ld.dL, dy, nd, L.qd);
+            line8_fill(ld.dA, dx, nd, L.qd);
+        } else {
+            for (int k = 0; k < nd; ++k) {
+                ld.dL[dy + k] = (uint8_t)L.qd;
+                ld.dA[dx + k] = (uint8_t)L.qd;
+            }
         }
     }
+    HG_CU_T(L, 2, tcu);
     if constexpr (!EG::kLean) {
         if (pcm) {
             pcm_cu(L, ld, P, G);
@@ -520,6 +604,20 @@ HG_HD inline void unit_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         for (int i = 0; i < np; ++i) prev |= dec(L, G, CTX_PREV_INTRA) << i;
     }
     int modes = 0;
+    // vector engines: the CU's words of the two lines, read once.  PB i + 1's neighbours inside
+    // the CU are PB i's modes (in `modes`), so no PB waits for an LDS round trip of the one
+    // before; the lines are written back once, after the last PB
+    const int nbc = 1 << (L.ql - 2), byc = (L.qy - L.ctby) >> 2, bxc = (L.qx - L.ctbx) >> 2;
+    uint64_t wl = 0, wa = 0;
+    int nl1 = 1, na1 = 1;  // the lower PBs' left and the right PBs' above neighbour (NxN)
+    if constexpr (kLineWords<EG>(2)) {
+        wl = line_ld(ld.ipmL + (byc & 8));
+        wa = line_ld(ld.ipmA + (bxc & 8));
+        if (nxn) {  // (a 64x64 NxN CU's second halves lie in the lines' second words)
+            nl1 = nbc == 16 ? ld.ipmL[8] : (int)(wl >> (8 * ((byc & 7) + (nbc >> 1)))) & 0xff;
+            na1 = nbc == 16 ? ld.ipmA[8] : (int)(wa >> (8 * ((bxc & 7) + (nbc >> 1)))) & 0xff;
+        }
+    }
     for (int i = 0; i < np; ++i) {
         const int p = (prev >> i) & 1;
         int mpm = 0, rem = 0;
@@ -530,14 +628,33 @@ HG_HD inline void unit_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
             mpm = rem = byp_luma_mode(L, G, p);
         }
         if (nxn) HG_COV(p ? COV_NXN_MPM + mpm : COV_NXN_REM);
-        const int xPb = L.qx + (i & 1) * pb, yPb = L.qy + (i >> 1) * pb;
-        const int m = derive_luma_mode(L, ld, xPb, yPb, p, mpm, rem);
-        modes |= m << (8 * i);
-        const int nb = pb >> 2, by = (yPb - L.ctby) >> 2, bx = (xPb - L.ctbx) >> 2;
-        for (int k = 0; k < nb; ++k) {
-            ld.ipmL[by + k] = (uint8_t)m;
-            ld.ipmA[bx + k] = (uint8_t)m;
+        HG_CU_T(L, 3, tcu);
+        if constexpr (kLineWords<EG>(2)) {
+            // left: PB i - 1 (right column), else the line (DC at the picture's edge);
+            // above: PB i - 2 (lower row), else the line (DC above the CTB)
+            const int ca = (i & 1) ? (modes >> (8 * (i - 1))) & 0xff
+                                   : (L.qx <= 0 ? 1 : (i ? nl1 : (int)(wl >> (8 * (byc & 7))) & 0xff));
+            const int cb = (i & 2) ? (modes >> (8 * (i - 2))) & 0xff
+                                   : (L.qy - 1 < L.ctby ? 1 : (i ? na1 : (int)(wa >> (8 * (bxc & 7))) & 0xff));
+            modes |= luma_mode(ca, cb, p, mpm, rem) << (8 * i);
+        } else {
+            const int xPb = L.qx + (i & 1) * pb, yPb = L.qy + (i >> 1) * pb;
+            const int m = derive_luma_mode(L, ld, xPb, yPb, p, mpm, rem);
+            modes |= m << (8 * i);
+            const int nb = pb >> 2, by = (yPb - L.ctby) >> 2, bx = (xPb - L.ctbx) >> 2;
+            for (int k = 0; k < nb; ++k) {
+                ld.ipmL[by + k] = (uint8_t)m;
+                ld.ipmA[bx + k] = (uint8_t)m;
+            }
         }
+        HG_CU_T(L, 4, tcu);
+    }
+    if constexpr (kLineWords<EG>(2)) {
+        // last written per row: the right PBs (1, 3); per column: the lower PBs (2, 3)
+        const int m0 = modes & 0xff;
+        line16_fill(ld.ipmL, wl, byc, nbc, nxn ? (modes >> 8) & 0xff : m0, nxn ? (modes >> 24) & 0xff : m0);
+        line16_fill(ld.ipmA, wa, bxc, nbc, nxn ? (modes >> 16) & 0xff : m0, nxn ? (modes >> 24) & 0xff : m0);
+        HG_CU_T(L, 4, tcu);
     }
     L.cu_modes = modes;
     if (HG_PIC_CHROMA(P)) {  // intra_chroma_pred_mode: per PB with 4:4:4, else per CU; 8.4.3
@@ -558,6 +675,7 @@ HG_HD inline void unit_cu(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         }
         L.cu_chroma = nc == 1 ? (int)((uint32_t)cms * 0x01010101u) : cms;  // byte k: PB k
     }
+    HG_CU_T(L, 5, tcu);
     L.tx = L.qx, L.ty = L.qy, L.tl = L.ql, L.td = 0, L.tcbf = 0;
     L.st = U_TT;
 }
@@ -577,6 +695,25 @@ constexpr bool kFlagsInParse = true;
 template <class EG>
 constexpr bool kFlagsInParse = EG::kSolo;
 #endif
+// The QpY map likewise: the scalar engines write a finished CU's rows in cu_done.
+// The vector engines append one word per CU (cu_word, kernels.hpp) to the CTB row's
+// CU list instead, and k_paint_flags paints the rows from the words after the parse:
+// the row loop ran up to 16 stores on every lane of nearly every completion step
+// (DESIGN 5.24).  (HG_QPY_IN_PARSE: every engine writes the rows too, for same-box pairs.)
+#if defined(HG_QPY_IN_PARSE)
+template <class EG>
+constexpr bool kQpyInParse = true;
+#else
+template <class EG>
+constexpr bool kQpyInParse = EG::kSolo;
+#endif
+// the QpY map itself (the vector engines' slot of its pointer holds their CU list,
+// lane_cus: the map lies before the flag map)
+template <class EG>
+HG_HD inline int8_t HG_GAS *qpy_map(const LanePic &P) {
+    if constexpr (EG::kSolo) return P.gqpy;
+    else return (int8_t HG_GAS *)(P.gflags - (size_t)P.w4 * P.h4);
+}
 
 // U_TT: transform_tree descent (7.3.8.8) from the current node to a leaf,
 // then transform_unit (7.3.8.10) up to its first TB
@@ -655,7 +792,6 @@ HG_HD inline void unit_tt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
         L.cu_qp_delta_val = v;
         update_qpy(L, P);
     }
-    HG_TB_T(L, 3, ttt);
     if constexpr (kFlagsInParse<EG>) {  // edge / no-filter flags of every 4x4 luma block of the TB (MF_*)
         const int nb = 1 << (L.tl - 2), gx0 = L.tx >> 2, gy0 = L.ty >> 2;
         const int wx = gx0 + nb <= P.w4 ? nb : P.w4 - gx0, hy = gy0 + nb <= P.h4 ? nb : P.h4 - gy0;
@@ -667,7 +803,7 @@ HG_HD inline void unit_tt(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
             store_bytes(row, wx, (rep * h) | (uint64_t)MF_EDGE_V);
         }
     }
-    HG_TB_T(L, 4, ttt);
+    HG_TB_T(L, 3, ttt);
     const int blk = L.td == 0 ? 0 : (((L.tx >> L.tl) & 1) | (((L.ty >> L.tl) & 1) << 1));
     // luma, then Cb and Cr (two each with 4:2:2: upper, lower)
     L.tb_n = (HG_PIC_CHROMA(P) != 0 && (!chroma4 || blk == 3)) ? (HG_PIC_CHROMA(P) == 2 ? 5 : 3) : 1;
@@ -706,6 +842,7 @@ HG_HD inline void tu_emit(Lane &L, const LanePic &P) {
     }
 }
 
+template <class EG>
 HG_HD inline void cu_done(Lane &L, LaneLds &ld, LanePic &P);
 
 // After a TB: its record, then the next TB of the TU, the next transform-tree
@@ -734,26 +871,41 @@ HG_HD inline void tb_done(Lane &L, LaneLds &ld, LanePic &P) {
         ++L.tl;
         --L.td;
     }
-    cu_done(L, ld, P);
+    cu_done<EG>(L, ld, P);
 }
 
-// end of a CU: QpY for qPY_A/B and the 4x4 map (deblocking), then the next
-// coding-quadtree node in z-order (skipping children outside the picture) or
-// the CTU end
+// end of a CU: QpY for qPY_A/B and the 4x4 map (deblocking: the scalar engines
+// write its rows, the vector engines one word for the CU in the CTB row's CU
+// list, kQpyInParse), then the next coding-quadtree node in z-order (skipping
+// children outside the picture) or the CTU end
+template <class EG>
 HG_HD inline void cu_done(Lane &L, LaneLds &ld, LanePic &P) {
     HG_TB_T0(tcu);
+    HG_COV(COV_CU_DONE + L.ql - 3);
     {
         const int n = 1 << L.ql, nd = n >> 3;
         const int dy = (L.qy - L.ctby) >> 3, dx = (L.qx - L.ctbx) >> 3;
+        // (byte loops in every engine: as words beside the other two lines they lost)
         for (int k = 0; k < nd; ++k) {
             ld.qL[dy + k] = (int8_t)L.qpy_cur;
             ld.qA[dx + k] = (int8_t)L.qpy_cur;
         }
-        const int nb = n >> 2, gx0 = L.qx >> 2, gy0 = L.qy >> 2;
-        const int wx = gx0 + nb <= P.w4 ? nb : P.w4 - gx0, hy = gy0 + nb <= P.h4 ? nb : P.h4 - gy0;
-        for (int y = 0; y < hy; ++y) {
-            int8_t *row = P.gqpy + (size_t)(gy0 + y) * P.w4 + gx0;
-            store_bytes(reinterpret_cast<uint8_t *>(row), wx, 0x0101010101010101ull * (uint8_t)L.qpy_cur);
+        HG_TB_T(L, 4, tcu);
+        if constexpr (!EG::kSolo) {
+            // geometric capacity (CUs are at least 8x8 and disjoint): a stream cannot exceed it
+            if (HG_LIKELY(L.ncu < cu_cap_row(P.wctb, P.log2ctb)))
+                lane_cus(P)[(uint32_t)L.row * cu_cap_row(P.wctb, P.log2ctb) + L.ncu++] =
+                    cu_word(L.qx, L.qy - L.ctby, L.ql, L.qpy_cur);
+            else
+                L.status |= ST_CAPACITY;
+        }
+        if constexpr (kQpyInParse<EG>) {
+            const int nb = n >> 2, gx0 = L.qx >> 2, gy0 = L.qy >> 2;
+            const int wx = gx0 + nb <= P.w4 ? nb : P.w4 - gx0, hy = gy0 + nb <= P.h4 ? nb : P.h4 - gy0;
+            for (int y = 0; y < hy; ++y) {
+                int8_t *row = qpy_map<EG>(P) + (size_t)(gy0 + y) * P.w4 + gx0;
+                store_bytes(reinterpret_cast<uint8_t *>(row), wx, 0x0101010101010101ull * (uint8_t)L.qpy_cur);
+            }
         }
         L.qp_prev_last = L.qpy_cur;
     }
@@ -1124,7 +1276,7 @@ HG_HD inline void unit_sb(Lane &L, LaneLds &ld, LanePic &P, const EG &G) {
             cw(off + 1, c0 >> 16);
             cw(off + 2, c0 >> 24);
         }
-#if defined(HG_PARSE_PROF_SB) && !defined(HG_PARSE_PROF_TB) && !defined(HG_HOST_EMU)
+#if defined(HG_PARSE_PROF_SB) && !defined(HG_PARSE_PROF_TB) && !defined(HG_PARSE_PROF_CU) && !defined(HG_HOST_EMU)
         L.psb[4] += (uint64_t)(nstart + 1);
 #endif
         HG_SB_T(L, 1, tsb);
@@ -1378,11 +1530,13 @@ HG_HD inline void unit_ctu_end(Lane &L, LaneLds &ld, LanePic &P, const Env &E, c
     uint32_t *rc = E.a->row_counts + 2 * (size_t)(P.row_off + L.row);
     rc[0] = L.ntu;
     rc[1] = L.ncoef;
+    if constexpr (!EG::kSolo) E.a->cu_counts[P.row_off + L.row] = L.ncu;
     const int step = (L.fl & F_WPP) ? P.R : 1;  // one substream (no WPP): walk on to the next row
     if (!(L.fl & F_STOP) && L.row + step < P.hctb) {
         L.row += step;
         L.c = 0;
         row_outputs(L, P);
+        if constexpr (!EG::kSolo) L.ncu = 0;  // (not in row_outputs: the scalar engines' code would change)
         L.st = U_CTU;
         return;
     }
@@ -1477,7 +1631,9 @@ HG_HD inline bool pic_init(LanePic &P, const BatchArgs &a, int pic, int lane0, i
     P.tu_cap = pd.tu_cap_row;
     P.coef_cap = pd.coef_cap_row;
     P.pic = (uint32_t)pic;
-    P.gqpy = (int8_t HG_GAS *)(a.maps + pd.map_off);
+    // (Mid: the vector engines; their slot of the QpY map's pointer holds the picture's CU list)
+    if constexpr (Mid) P.gqpy = (int8_t HG_GAS *)(a.cus + cu_list_off(pd.sao_off, a.max_log2ctb));
+    else P.gqpy = (int8_t HG_GAS *)(a.maps + pd.map_off);
     P.gflags = (uint8_t HG_GAS *)(a.maps + pd.map_off + (size_t)P.w4 * P.h4);
     P.gdepth = (uint8_t HG_GAS *)(a.maps + pd.map_off + 2 * (size_t)P.w4 * P.h4);
     P.gsao = (SaoParams HG_GAS *)(a.sao + pd.sao_off);
@@ -1506,6 +1662,7 @@ HG_HD inline bool lane_init(Lane &L, LanePic &P, LaneLds &ld, const BatchArgs &a
                             int cap) {
     if (!pic_init<Mid>(P, a, pic, lane0, cap) || row >= P.R) return false;
     lane_start(L, P, ld, row);
+    if constexpr (Mid) L.ncu = 0;  // the vector engines' CU words of the row
     return true;
 }
 

@@ -29,7 +29,7 @@ namespace hg {
 // This decode's per-picture words that start at zero, cleared here instead of
 // by memsets on the parse stream (each of those waited ~5 ms for a slot behind
 // the previous decode's k_transform, on the parse's critical path): the
-// status word, the picture's row counts, its spread-parse progress words and,
+// status word, the picture's row counts (TUs, coefficients, CU words), its spread-parse progress words and,
 // for k_intra_stream, its TU counts and done word.
 __device__ inline void zero_outputs(const BatchArgs &a, int pic, int lane, int nl) {
     const PicDesc &pd = a.pics[pic];
@@ -39,6 +39,8 @@ __device__ inline void zero_outputs(const BatchArgs &a, int pic, int lane, int n
     const SeqParams &sp = a.seqs[pd.seq];
     const int hctb = (sp.height + (1 << sp.log2_ctb) - 1) >> sp.log2_ctb;
     for (int i = lane; i < 2 * hctb; i += nl) a.row_counts[2 * (size_t)pd.row_off + i] = 0;
+    if (a.cu_counts)  // lanes parse: the rows' CU words
+        for (int i = lane; i < hctb; i += nl) a.cu_counts[pd.row_off + i] = 0;
     if (a.xprog)  // spread parse: one progress word per row
         for (int i = lane; i < hctb; i += nl) a.xprog[pd.row_off + i] = 0;
     if (a.intra_stream && a.xntu) {

@@ -251,6 +251,10 @@ __global__ void __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_e
 // everywhere under cu_transquant_bypass.  A PCM CU's record (one luma TB of the CU's
 // size, TU_BYPASS set whatever the CU's own flag) is skipped: pcm_cu painted it.
 // One workgroup per CTB row of a picture like k_transform, a record per lane.
+// The QpY map (one byte per 4x4 luma block, before the flag map) in the same launch,
+// from the row's CU words (cu_word; cu_done of the vector engines appends one per CU,
+// PCM CUs included): a CU per lane writes its final QpY over its (n / 4)^2 blocks,
+// clipped at the picture's edges.  The CUs tile the picture, so every byte is written.
 __global__ void __launch_bounds__(kWaves * 64) k_paint_flags(BatchArgs a) {
     const int pic = a.pic0 + blockIdx.y, row = blockIdx.x;
     const PicDesc pd = a.pics[pic];
@@ -284,6 +288,35 @@ __global__ void __launch_bounds__(kWaves * 64) k_paint_flags(BatchArgs a) {
                 } else {
                     for (int x = 0; x < wx; ++x) r[x] = (uint8_t)(v >> (8 * x));
                 }
+            }
+        }
+    }
+    uint8_t *qmap = a.maps + pd.map_off;
+    const int wctb = (sp.width + (1 << sp.log2_ctb) - 1) >> sp.log2_ctb;
+    const uint32_t cap = cu_cap_row(wctb, sp.log2_ctb);
+    const uint32_t ncu = min(a.cu_counts[pd.row_off + row], cap);
+    const uint32_t *cus = a.cus + cu_list_off(pd.sao_off, a.max_log2ctb) + (uint64_t)row * cap;
+    for (uint32_t t0 = 64u * wave; t0 < ncu; t0 += 64u * kWaves) {
+        for (int vl = lane; vl < 64; vl += kWave) {
+            const uint32_t t = t0 + (uint32_t)vl;
+            if (t >= ncu) continue;
+            const uint32_t w = cus[t];
+            const int log2 = (int)((w >> 20) & 15u);
+            if (log2 < 3 || log2 > 6) continue;
+            const int nb = 1 << (log2 - 2), gx0 = (int)(w & 0xffffu) << 1;
+            const int gy0 = (row << (sp.log2_ctb - 2)) + ((int)((w >> 16) & 15u) << 1);
+            if (gx0 >= w4 || gy0 >= h4) continue;
+            const int wx = gx0 + nb <= w4 ? nb : w4 - gx0, hy = gy0 + nb <= h4 ? nb : h4 - gy0;
+            const uint64_t v = 0x0101010101010101ull * (uint64_t)(w >> 24);
+            for (int y = 0; y < hy; ++y) {
+                uint8_t *r = qmap + (size_t)(gy0 + y) * w4 + gx0;
+                int x = 0;
+                for (; x + 8 <= wx; x += 8) __builtin_memcpy(r + x, &v, 8);
+                if (x + 4 <= wx) {
+                    __builtin_memcpy(r + x, &v, 4);
+                    x += 4;
+                }
+                for (; x < wx; ++x) r[x] = (uint8_t)v;
             }
         }
     }

@@ -46,6 +46,7 @@ def main():
     lib = _lib.lib
     sb = "profsb" in str(_lib.LIB_PATH)  # `make prof-sb`: 16 counter slots, the sub-block phases per wave
     tb = "profsb_tb" in str(_lib.LIB_PATH)  # `make prof-tb`: the tree / TB units' phases in those slots
+    cu = "profsb_cu" in str(_lib.LIB_PATH)  # `make prof-cu`: the quadtree / CU units' phases there
     o = 16 if sb else 8
     m = o + 3 * (WAVE_REC + 5 * WAVE_REC_CAP)
     buf = (ctypes.c_uint64 * m)()
@@ -89,8 +90,11 @@ def main():
         r["kind_passes"] = dict(zip(KINDS, kc))
         r["kind_passes"]["tbd"] = b[6] >> 48
         r["lane_units"] = 4 * (b[8] >> 48)
-        if tb:  # TB unit head, prefix bins, suffixes + scan, TT unit, flag rows, QpY rows
-            r["tb_phases"] = dict(zip(["tb_head", "last_prefix", "last_rest", "tt_syntax", "flag_rows", "qpy_rows"],
+        if tb:  # TB unit head, prefix bins, suffixes + scan, TT unit, a finished CU's QpY lines, its map rows / CU word
+            r["tb_phases"] = dict(zip(["tb_head", "last_prefix", "last_rest", "tt_unit", "qpy_lines", "qpy_rows"],
+                                      b[9:15]))
+        elif cu:  # quadtree unit; CU unit: head, CtDepth lines, prev_intra + mode bins, mode derivation + lines, chroma
+            r["cu_phases"] = dict(zip(["cqt", "cu_head", "depth_lines", "mode_bins", "derive_ipm_lines", "chroma_mode"],
                                       b[9:15]))
         elif sb:  # header, sig loop, greater1/2, signs + remainders + record (cycles, one lane per run), sig bins
             r["sb_phases"] = dict(zip(["head", "sig", "g1g2", "rest", "sig_bins"], b[9:14]))
@@ -153,15 +157,21 @@ def breakdown(r):
             "lanes_per_pass": round(r["lane_units"] / max(r["passes"], 1), 2),
             **({"sb_phase_cycles_per_run": {k: round(v / max(kp["sb"], 1)) for k, v in r["sb_phases"].items()}}
                if "sb_phases" in r else {}),
-            # per pass that ran the unit: the TB unit's three, the TT unit's two, the QpY rows per
-            # TB-completion pass (tb_rest: tu_emit and the tree walks, what the "tb" group has left)
+            # per pass that ran the unit: the TB unit's three, the TT unit, a finished CU's QpY lines and
+            # rows per TB-completion pass (tb_rest: tu_emit and the tree walks, what the "tb" group has left)
             **({"tb_phase_cycles_per_run": {
                 **{k: round(r["tb_phases"][k] / max(kp["tb"], 1)) for k in ("tb_head", "last_prefix", "last_rest")},
-                **{k: round(r["tb_phases"][k] / max(kp["tt"], 1)) for k in ("tt_syntax", "flag_rows")},
-                "qpy_rows": round(r["tb_phases"]["qpy_rows"] / max(kp["tbd"], 1)),
+                "tt_unit": round(r["tb_phases"]["tt_unit"] / max(kp["tt"], 1)),
+                **{k: round(r["tb_phases"][k] / max(kp["tbd"], 1)) for k in ("qpy_lines", "qpy_rows")},
                 "tb_rest": round((c["tb"] - sum(r["tb_phases"][k] for k in ("tb_head", "last_prefix", "last_rest",
-                                                                             "qpy_rows"))) / max(kp["tbd"], 1))}}
-               if "tb_phases" in r else {})}
+                                                                             "qpy_lines", "qpy_rows"))) / max(kp["tbd"], 1))}}
+               if "tb_phases" in r else {}),
+            # per pass that ran the unit: the quadtree unit's one, the CU unit's five
+            **({"cu_phase_cycles_per_run": {
+                "cqt": round(r["cu_phases"]["cqt"] / max(kp["cqt"], 1)),
+                **{k: round(r["cu_phases"][k] / max(kp["cu"], 1))
+                   for k in ("cu_head", "depth_lines", "mode_bins", "derive_ipm_lines", "chroma_mode")}}}
+               if "cu_phases" in r else {})}
 
 
 if __name__ == "__main__":
