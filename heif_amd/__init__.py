@@ -24,7 +24,7 @@ from ._lib import HeifGpuError, UnsupportedError, lib
 
 __all__ = [
     "HeicDecoder", "HeifImage", "DecodeContext", "DeviceBatch", "DecodedImage", "RbspReader",
-    "HeifGpuError", "UnsupportedError", "ipc_export", "ipc_open", "ipc_close", "chroma_dims",
+    "HeifGpuError", "UnsupportedError", "ipc_export", "ipc_open", "ipc_close", "chroma_dims", "ColorDescription",
 ]
 
 
@@ -95,6 +95,47 @@ class HeifImage:
         _lib.check(lib.heifgpu_image_get_display(self._h, ctypes.byref(d)))
         return d
 
+    @property
+    def color(self) -> "ColorDescription":
+        """The image's colour space (heifgpu_image_get_color): what defines it
+        ("icc", "nclx" or "none", which is taken as sRGB), the nclx primaries and
+        transfer codes, and the source colourants (3 x 3: row c is X Y Z of
+        primary c, D50), None when a transform of this source is refused."""
+        ci = _lib.ColorInfo()
+        _lib.check(lib.heifgpu_image_get_color(self._h, ctypes.byref(ci)))
+        col = None
+        if ci.status == _lib.HEIFGPU_OK:
+            col = tuple(tuple(ci.colorants[3 * c + k] for k in range(3)) for c in range(3))
+        return ColorDescription(_lib.COLOR_KINDS[ci.kind], ci.primaries, ci.transfer, col, ci.icc_size, bool(ci.has_nclx),
+                                ci.status)
+
+    @property
+    def icc_profile(self) -> Optional[bytes]:
+        """The bytes of the item's ICC profile (heifgpu_image_get_icc), None without one."""
+        n = ctypes.c_size_t()
+        _lib.check(lib.heifgpu_image_get_icc(self._h, None, 0, ctypes.byref(n)))
+        if not n.value:
+            return None
+        buf = (ctypes.c_uint8 * n.value)()
+        _lib.check(lib.heifgpu_image_get_icc(self._h, buf, n.value, ctypes.byref(n)))
+        return bytes(buf)
+
+    def color_transform(self, colorspace: str, bits: int = 8) -> _lib.ColorTransform:
+        """The transform of this image's colour space to "srgb" or "display-p3" at
+        the depth a render computes at (heifgpu_color_transform_make): 8 for the
+        8-bit formats, the image's bit depth for the 16-bit ones.  UnsupportedError
+        for a source outside the supported set (LUT profiles, PQ / HLG, ...),
+        HeifGpuError for a malformed profile.  Cached per (colorspace, bits)."""
+        if colorspace not in _lib.COLORSPACES:
+            raise ValueError(f"colorspace {colorspace!r}: one of {sorted(_lib.COLORSPACES)}")
+        cache = self.__dict__.setdefault("_xf", {})
+        key = (colorspace, int(bits))
+        if key not in cache:
+            t = _lib.ColorTransform()
+            _lib.check(lib.heifgpu_color_transform_make(self._h, _lib.COLORSPACES[colorspace], int(bits), ctypes.byref(t)))
+            cache[key] = t
+        return cache[key]
+
     def source_rect(self, window=None):
         """(x, y, w, h) of the decoded planes that a render of `window` reads
         (heifgpu_window_source_rect): window = (x, y, w, h) in displayed
@@ -134,6 +175,17 @@ class HeifImage:
         if h is not None and h.value and lib is not None:  # lib is None during interpreter teardown
             lib.heifgpu_image_free(h)
             self._h = None
+
+
+@dataclass
+class ColorDescription:
+    kind: str                   # "icc", "nclx" or "none"
+    primaries: int              # of the nclx colr; 2 (unspecified) without one
+    transfer: int
+    colorants: Optional[tuple]  # ((Xr, Yr, Zr), (Xg, Yg, Zg), (Xb, Yb, Zb)), D50
+    icc_size: int = 0
+    has_nclx: bool = False
+    status: int = 0             # HEIFGPU_OK, or the code a transform of this source answers
 
 
 def chroma_dims(info):
@@ -361,14 +413,20 @@ class DecodeContext:
 
 
     def render(self, outs: Sequence[DecodedImage], fmt: str = "rgb8",
-               alphas: Optional[Sequence[Optional[DecodedImage]]] = None, stream: Optional[int] = None):
+               alphas: Optional[Sequence[Optional[DecodedImage]]] = None, stream: Optional[int] = None,
+               colorspace: Optional[str] = None):
         """Display-ready pixels of a batch of decoded images with ONE
         heifgpu_render_batch call (one kernel launch): a list of (H', W', C)
         device tensors, C = 3 or 4, uint8 for "rgb8" / "rgba8" and int16 (like
         the 16-bit planes) for "rgb16" / "rgba16", with every image's clap /
         irot / imir applied.  alphas[i] is the decoded alpha image of outs[i]
         (None = opaque).  The images come from alloc_outputs (they carry their
-        parsed HeifImage)."""
+        parsed HeifImage).  colorspace None leaves every picture in its own colour
+        space (the colr matrix and range applied, nothing else); "srgb" or
+        "display-p3" converts every RGB triple from the image's ICC profile or
+        nclx description to that space in the same launch (heifgpu_render_batch_color;
+        alpha untouched); a source the library cannot transform raises
+        UnsupportedError before anything is launched."""
         torch = self._torch
         n = len(outs)
         f = _lib.PIX_FORMATS[fmt]
@@ -388,11 +446,29 @@ class DecodeContext:
             surf[i].pitch = t.stride(0) * t.element_size()
             res.append(t)
         imgs, aimgs, aplanes = self._render_args(outs, alphas)
+        xf, keep = self._transforms(outs, colorspace, wide)
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(lib.heifgpu_render_batch(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f, surf,
-                                            ctypes.c_void_p(stream)))
+        if xf is None:
+            _lib.check(lib.heifgpu_render_batch(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f, surf,
+                                                ctypes.c_void_p(stream)))
+        else:
+            _lib.check(lib.heifgpu_render_batch_color(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f,
+                                                      xf, surf, ctypes.c_void_p(stream)))
         return res
+
+    @staticmethod
+    def _transforms(outs, colorspace, wide):
+        """(one transform pointer per image, the transforms they point to) for a
+        colour-managed render call; (None, None) for colorspace None.  Raises
+        before anything is launched (UnsupportedError, HeifGpuError)."""
+        if colorspace is None:
+            return None, None
+        if colorspace not in _lib.COLORSPACES:
+            raise ValueError(f"colorspace {colorspace!r}: None or one of {sorted(_lib.COLORSPACES)}")
+        keep = [o.image.color_transform(colorspace, int(o.info.bit_depth) if wide else 8) for o in outs]
+        arr = (ctypes.c_void_p * max(len(outs), 1))(*[ctypes.addressof(t) for t in keep])
+        return arr, keep
 
     @staticmethod
     def _render_args(outs, alphas):
@@ -411,7 +487,7 @@ class DecodeContext:
 
     def render_scaled(self, outs: Sequence[DecodedImage], size, mode: str = "cover", fmt: str = "rgb8",
                       alphas: Optional[Sequence[Optional[DecodedImage]]] = None, windows=None,
-                      stream: Optional[int] = None):
+                      stream: Optional[int] = None, colorspace: Optional[str] = None):
         """render() onto a smaller grid: the exact area average of a window of
         every displayed picture, with ONE heifgpu_render_batch_scaled call (one
         kernel launch).  size = (h, w) is the box; mode "cover" (a centred
@@ -421,8 +497,10 @@ class DecodeContext:
         coordinates replaces the mode's window; the output is then `size`
         exactly.  Returns ONE (N, h, w, C) device tensor when every output has
         the same size (cover, stretch, windows), whose slices are the surfaces,
-        and a list of (h_i, w_i, C) tensors for "contain".  Dtypes, fmt and
-        alphas as in render()."""
+        and a list of (h_i, w_i, C) tensors for "contain".  Dtypes, fmt,
+        alphas and colorspace as in render(): with a colorspace the result is
+        the transform of what render_scaled() writes without one (the rounded
+        averages are transformed, not the source pixels)."""
         torch = self._torch
         n = len(outs)
         f = _lib.PIX_FORMATS[fmt]
@@ -465,14 +543,19 @@ class DecodeContext:
         imgs, aimgs, aplanes = self._render_args(outs, alphas)
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(lib.heifgpu_render_batch_scaled(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f,
-                                                   scales, surf, ctypes.c_void_p(stream)))
+        xf, keep = self._transforms(outs, colorspace, wide)
+        if xf is None:
+            _lib.check(lib.heifgpu_render_batch_scaled(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f,
+                                                       scales, surf, ctypes.c_void_p(stream)))
+        else:
+            _lib.check(lib.heifgpu_render_batch_scaled_color(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs,
+                                                             aplanes, f, scales, xf, surf, ctypes.c_void_p(stream)))
         return whole if whole is not None else res
 
     def render_tensor(self, outs: Sequence[DecodedImage], size, mode: str = "cover", dtype=None, layout: str = "chw",
                       mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), src: str = "rgb8", windows=None,
                       flips=None, alphas: Optional[Sequence[Optional[DecodedImage]]] = None, scale_bias=None,
-                      stream: Optional[int] = None):
+                      stream: Optional[int] = None, colorspace: Optional[str] = None):
         """render_scaled() as a loader wants it: crop, flip and normalise into
         float elements with ONE heifgpu_render_batch_tensor call (one kernel
         launch).  With R the integers render_scaled(fmt=src) gives, flipped
@@ -485,8 +568,9 @@ class DecodeContext:
         (pictures of different bit depths B then have no common a, b: ValueError).
         layout "chw" returns ONE (N, C, h, w) tensor, "hwc" ONE (N, h, w, C)
         tensor, for cover, stretch and windows; "contain" returns a list of
-        (C, h_i, w_i) or (h_i, w_i, C) tensors.  size, mode, windows and alphas
-        as in render_scaled()."""
+        (C, h_i, w_i) or (h_i, w_i, C) tensors.  size, mode, windows, alphas
+        and colorspace as in render_scaled(): R is then what
+        render_scaled(colorspace=) gives."""
         torch = self._torch
         n = len(outs)
         f = _lib.PIX_FORMATS[src]
@@ -559,8 +643,14 @@ class DecodeContext:
         imgs, aimgs, aplanes = self._render_args(outs, alphas)
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(lib.heifgpu_render_batch_tensor(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes,
-                                                   ctypes.byref(tf), scales, fl, surf, ctypes.c_void_p(stream)))
+        xf, keep = self._transforms(outs, colorspace, wide)
+        if xf is None:
+            _lib.check(lib.heifgpu_render_batch_tensor(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes,
+                                                       ctypes.byref(tf), scales, fl, surf, ctypes.c_void_p(stream)))
+        else:
+            _lib.check(lib.heifgpu_render_batch_tensor_color(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs,
+                                                             aplanes, ctypes.byref(tf), scales, fl, xf, surf,
+                                                             ctypes.c_void_p(stream)))
         return whole if whole is not None else res
 
 
@@ -718,7 +808,7 @@ class HeicDecoder:
 
     @classmethod
     def decode_display(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, size=None,
-                       mode: str = "contain", tiles: str = "all"):
+                       mode: str = "contain", tiles: str = "all", colorspace: Optional[str] = None):
         """The picture a viewer shows: decodes the primary image and, when it
         has one (display.alpha_item_id), its alpha plane, then renders
         (DecodeContext.render) with clap / irot / imir applied.  fmt None picks
@@ -726,15 +816,18 @@ class HeicDecoder:
         size = (h, w) renders it into that box instead (DecodeContext.render_scaled
         with `mode`); None is the full size.  tiles="window" decodes only the
         grid tiles the rendered window reads (of the alpha image too): the same
-        pixels, bit for bit, for less work when `mode` or a clap crops."""
+        pixels, bit for bit, for less work when `mode` or a clap crops.
+        colorspace "srgb" / "display-p3" converts the picture from its ICC profile
+        or nclx description to that space (DecodeContext.render); None leaves it
+        in its own, unlabelled."""
         ctx = cls.context(device)
         out, alpha = cls._decode_pair(data, device, size, mode, tiles, True)
         if fmt is None:
             fmt = ("rgba" if alpha is not None else "rgb") + ("16" if out.info.bit_depth > 8 else "8")
         alphas = [alpha] if alpha is not None else None
         if size is not None:
-            return ctx.render_scaled([out], size, mode, fmt, alphas)[0]
-        return ctx.render([out], fmt, alphas)[0]
+            return ctx.render_scaled([out], size, mode, fmt, alphas, colorspace=colorspace)[0]
+        return ctx.render([out], fmt, alphas, colorspace=colorspace)[0]
 
     @classmethod
     def decode_tensor(cls, data: bytes, size, mode: str = "cover", device: int = 0, flip: int = 0,
@@ -743,7 +836,7 @@ class HeicDecoder:
         primary image (and its alpha plane when `src` is an RGBA format and the
         file has one), then DecodeContext.render_tensor of that one picture:
         (C, h, w), or (h, w, C) for layout="hwc".  dtype, layout, mean, std, src
-        and scale_bias go through to render_tensor; tiles as in decode_display."""
+        scale_bias and colorspace go through to render_tensor; tiles as in decode_display."""
         ctx = cls.context(device)
         rgba = kw.get("src", "rgb8").startswith("rgba")
         out, alpha = cls._decode_pair(data, device, size, mode, tiles, rgba)

@@ -164,6 +164,27 @@ class TensorSurface(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("stride_c", ctypes.c_int64), ("stride_y", ctypes.c_int64)]
 
 
+class ColorInfo(ctypes.Structure):
+    """heifgpu_color_info: what defines an image's colour space (kind: COLOR_*), its
+    nclx codes, the profile's size, what a transform of it would answer (status) and,
+    when that is HEIFGPU_OK, the source colourants: X Y Z of R, of G, of B (D50)."""
+    _fields_ = [("kind", ctypes.c_uint32), ("has_nclx", ctypes.c_uint32), ("primaries", ctypes.c_uint32),
+                ("transfer", ctypes.c_uint32), ("icc_size", ctypes.c_uint32), ("status", ctypes.c_int32),
+                ("colorants", ctypes.c_double * 9)]
+
+
+class ColorTransform(ctypes.Structure):
+    """heifgpu_color_transform: the tables and the Q14 matrix of one source at one depth."""
+    _fields_ = [("bits", ctypes.c_uint32), ("identity", ctypes.c_uint32), ("dst", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("m", ctypes.c_int32 * 9), ("m_rounded", ctypes.c_int32 * 9),
+                ("in_lut", (ctypes.c_uint16 * 4096) * 3), ("out_lut", ctypes.c_uint16 * 4098)]
+
+
+COLOR_NONE, COLOR_ICC, COLOR_NCLX = 0, 1, 2
+COLOR_KINDS = {COLOR_NONE: "none", COLOR_ICC: "icc", COLOR_NCLX: "nclx"}
+CS_SRGB, CS_DISPLAY_P3 = 0, 1
+COLORSPACES = {"srgb": CS_SRGB, "display-p3": CS_DISPLAY_P3}
+
 ELEM_F32, ELEM_F16, ELEM_BF16 = 0, 1, 2
 LAYOUT_CHW, LAYOUT_HWC = 0, 1
 LAYOUTS = {"chw": LAYOUT_CHW, "hwc": LAYOUT_HWC}
@@ -194,6 +215,8 @@ EXPORTS = (
     "heifgpu_image_get_display", "heifgpu_render_batch", "heifgpu_scale_fit", "heifgpu_render_batch_scaled",
     "heifgpu_render_batch_tensor", "heifgpu_window_source_rect", "heifgpu_image_tiles_for_rect",
     "heifgpu_batch_prepare_rects", "heifgpu_batch_count_pictures", "heifgpu_batch_picture_count",
+    "heifgpu_image_get_color", "heifgpu_image_get_icc", "heifgpu_color_transform_make", "heifgpu_color_apply",
+    "heifgpu_render_batch_color", "heifgpu_render_batch_scaled_color", "heifgpu_render_batch_tensor_color",
 )
 
 
@@ -277,11 +300,23 @@ def _load() -> ctypes.CDLL:
         "heifgpu_batch_prepare_rects": (I32, [VP, P(VP), SZ, P(BatchOpts), P(Rect), P(VP)]),
         "heifgpu_batch_count_pictures": (I32, [P(VP), SZ, P(BatchOpts), P(Rect), P(U32)]),
         "heifgpu_batch_picture_count": (I32, [VP, P(U32)]),
+        "heifgpu_image_get_color": (I32, [VP, P(ColorInfo)]),
+        "heifgpu_image_get_icc": (I32, [VP, u8p, SZ, P(SZ)]),
+        "heifgpu_color_transform_make": (I32, [VP, U32, U32, P(ColorTransform)]),
+        "heifgpu_color_apply": (I32, [P(ColorTransform), P(ctypes.c_uint16), SZ, P(ctypes.c_uint16)]),
+        "heifgpu_render_batch_color": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), U32, P(VP), P(Surface), VP]),
+        "heifgpu_render_batch_scaled_color": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), U32, P(Scale), P(VP),
+                                                    P(Surface), VP]),
+        "heifgpu_render_batch_tensor_color": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), P(TensorFormat), P(Scale),
+                                                    P(U32), P(VP), P(TensorSurface), VP]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     # (and no window decode: DecodeContext.prepare without windows then goes through prepare_ex)
     optional = {"heifgpu_batch_lanes_variant", "heifgpu_window_source_rect", "heifgpu_image_tiles_for_rect",
-                "heifgpu_batch_prepare_rects", "heifgpu_batch_count_pictures", "heifgpu_batch_picture_count"}
+                "heifgpu_batch_prepare_rects", "heifgpu_batch_count_pictures", "heifgpu_batch_picture_count",
+                # the colour-managed render (colorspace= then needs a build that has it)
+                "heifgpu_image_get_color", "heifgpu_image_get_icc", "heifgpu_color_transform_make", "heifgpu_color_apply",
+                "heifgpu_render_batch_color", "heifgpu_render_batch_scaled_color", "heifgpu_render_batch_tensor_color"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue

@@ -17,6 +17,8 @@
 #include "common/desc.hpp"
 #include "host/batch.hpp"
 #include "host/heic_image.hpp"
+#include "host/icc.hpp"
+#include "kernels/color_xform.hpp"
 #include "kernels/cabac.hpp"
 #include "kernels/kernels.hpp"
 
@@ -61,6 +63,7 @@ static_assert(sizeof(heifgpu_tile_params) == 55 * 4 + 64 * 4, "heifgpu_tile_para
 // 17.86 / 17.77 Gpix/s, profiles/r03d/ab_pipeline_sets.txt).
 constexpr int kTimingSlots = 32;
 struct RenderRing;  // heifgpu_render_batch's descriptor staging (below)
+struct ColorCache;  // the colour-managed renders' tables on the device (below)
 struct heifgpu_ctx {
     int device = 0;
     bool timing = false;
@@ -78,6 +81,7 @@ struct heifgpu_ctx {
     int timed_calls = 0, folded = 0;
     double acc[6] = {};
     RenderRing *render = nullptr;  // created by the first heifgpu_render_batch
+    ColorCache *color = nullptr;   // created by the first colour-managed render
 };
 
 namespace {
@@ -526,6 +530,139 @@ int heifgpu_image_get_display(const heifgpu_image *img, heifgpu_display_info *ou
     return HEIFGPU_OK;
 }
 
+// ---- colour-managed render (include/heifgpu.h): description, transform, tables --
+int heifgpu_image_get_color(const heifgpu_image *img, heifgpu_color_info *out) {
+    if (!img || !out) return fail(HEIFGPU_E_INVALID, "null argument");
+    const ColorDesc &c = img->img.color;
+    std::memset(out, 0, sizeof(*out));
+    out->kind = c.has_icc ? HEIFGPU_COLOR_ICC : c.has_nclx ? HEIFGPU_COLOR_NCLX : HEIFGPU_COLOR_NONE;
+    out->has_nclx = c.has_nclx;
+    out->primaries = c.primaries;
+    out->transfer = c.transfer;
+    out->icc_size = uint32_t(c.icc.size());
+    ColorSource src;
+    std::string err;
+    out->status = color_source(c, src, err);
+    if (out->status == HEIFGPU_OK)
+        for (int k = 0; k < 9; ++k) out->colorants[k] = src.col[k];
+    return HEIFGPU_OK;
+}
+
+int heifgpu_image_get_icc(const heifgpu_image *img, uint8_t *buf, size_t cap, size_t *len) {
+    if (!img || !len) return fail(HEIFGPU_E_INVALID, "null argument");
+    const std::vector<uint8_t> &icc = img->img.color.icc;
+    *len = icc.size();
+    if (buf && cap >= icc.size() && !icc.empty()) std::memcpy(buf, icc.data(), icc.size());
+    return HEIFGPU_OK;
+}
+
+int heifgpu_color_transform_make(const heifgpu_image *img, uint32_t dst, uint32_t bits, heifgpu_color_transform *out) {
+    if (!img || !out) return fail(HEIFGPU_E_INVALID, "null argument");
+    ColorSource src;
+    std::string err;
+    if (int rc = color_source(img->img.color, src, err)) return fail(rc, err);
+    if (int rc = color_transform_build(src, dst, bits, *out, err)) return fail(rc, err);
+    return HEIFGPU_OK;
+}
+
+int heifgpu_color_apply(const heifgpu_color_transform *t, const uint16_t *rgb_in, size_t n_pixels, uint16_t *rgb_out) {
+    if (!t || !rgb_in || !rgb_out) return fail(HEIFGPU_E_INVALID, "null argument");
+    if (t->bits < 8 || t->bits > 12) return fail(HEIFGPU_E_INVALID, "transform depth outside 8..12");
+    const int n = 1 << t->bits;
+    // the tables as the device holds them: three of n entries, one after the other
+    std::vector<uint16_t> in_lut(size_t(3) * n);
+    for (int c = 0; c < 3; ++c) std::memcpy(in_lut.data() + size_t(c) * n, t->in_lut[c], size_t(n) * 2);
+    for (size_t i = 0; i < 3 * n_pixels; ++i)
+        if (rgb_in[i] >= n) return fail(HEIFGPU_E_INVALID, "code above maxv");
+    const uint16_t *in = in_lut.data();
+    const XfOutLut<const uint16_t *> out{t->out_lut};
+    for (size_t i = 0; i < n_pixels; ++i) {
+        uint32_t r = rgb_in[3 * i], g = rgb_in[3 * i + 1], b = rgb_in[3 * i + 2];
+        color_xform_px(in, n, out, t->m, r, g, b);
+        rgb_out[3 * i] = uint16_t(r), rgb_out[3 * i + 1] = uint16_t(g), rgb_out[3 * i + 2] = uint16_t(b);
+    }
+    return HEIFGPU_OK;
+}
+
+// The tables of the transforms on the device, keyed by content: in_lut[3][1 << B] then
+// out_lut as 4096 pairs (xf_out_pair), as ColorRef::lut addresses them.  An entry is written once, by a blocking
+// copy before the call that first uses it launches anything, and never again, so no
+// launch in flight can see a table change; a steady-state call finds its tables here.
+// When kColorCacheMax tables are held the cache is emptied after a device synchronise.
+constexpr size_t kColorCacheMax = 256;
+struct ColorCache {
+    struct Entry {
+        std::vector<uint16_t> key;
+        uint16_t *dev = nullptr;
+    };
+    std::vector<Entry> entries;
+    void clear() {
+        for (Entry &e : entries)
+            if (e.dev) (void)hipFree(e.dev);
+        entries.clear();
+    }
+    ~ColorCache() { clear(); }
+};
+
+// refs[i] for the images of a render call (empty when no image is to be transformed:
+// the call is then the unmanaged call).  Every check runs before anything is launched.
+static int color_refs_fill(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, uint32_t format,
+                           const heifgpu_color_transform *const *xf, std::vector<ColorRef> &refs) {
+    refs.clear();
+    if (!xf) return HEIFGPU_OK;
+    bool any = false;
+    for (size_t i = 0; i < n; ++i) {
+        const heifgpu_color_transform *t = xf[i];
+        if (!t) continue;
+        heifgpu_image_info info;
+        heifgpu_image_get_info(imgs[i], &info);
+        const uint32_t depth = format >= HEIFGPU_PIX_RGB16 ? info.bit_depth : 8;
+        if (t->bits != depth || t->bits < 8 || t->bits > 12)
+            return fail(HEIFGPU_E_INVALID, "transform made for another depth than the image is rendered at");
+        any = any || !t->identity;
+    }
+    if (!any) return HEIFGPU_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->color) ctx->color = new ColorCache;
+    ColorCache &cache = *ctx->color;
+    if (cache.entries.size() >= kColorCacheMax) {  // (checked once per call: a call may go past it by its own tables)
+        HIP_TRY(hipDeviceSynchronize());  // nothing in flight reads a table that is freed
+        cache.clear();
+    }
+    refs.assign(n, ColorRef{});
+    std::vector<uint16_t> key;
+    for (size_t i = 0; i < n; ++i) {
+        const heifgpu_color_transform *t = xf[i];
+        if (!t || t->identity) continue;  // lut == 0: untouched
+        const size_t tn = size_t(1) << t->bits;
+        key.resize(3 * tn + 2 * kXfPairEntries);
+        for (int c = 0; c < 3; ++c) std::memcpy(key.data() + c * tn, t->in_lut[c], tn * 2);
+        for (int k = 0; k < kXfPairEntries; ++k) {
+            const uint32_t w = xf_out_pair(t->out_lut, k);
+            std::memcpy(key.data() + 3 * tn + 2 * k, &w, 4);
+        }
+        ColorCache::Entry *hit = nullptr;
+        for (ColorCache::Entry &e : cache.entries)
+            if (e.key == key) hit = &e;
+        if (!hit) {
+            ColorCache::Entry e;
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e.dev), key.size() * 2));
+            const hipError_t up = hipMemcpy(e.dev, key.data(), key.size() * 2, hipMemcpyHostToDevice);  // blocking
+            if (up != hipSuccess) {
+                (void)hipFree(e.dev);
+                return fail(HEIFGPU_E_DEVICE, std::string("colour table upload: ") + hipGetErrorString(up));
+            }
+            e.key = key;
+            cache.entries.push_back(std::move(e));
+            hit = &cache.entries.back();
+        }
+        refs[i].lut = reinterpret_cast<uint64_t>(hit->dev);
+        refs[i].n = int32_t(tn);
+        for (int k = 0; k < 9; ++k) refs[i].m[k] = t->m[k];
+    }
+    return HEIFGPU_OK;
+}
+
 // What heifgpu_render_batch and heifgpu_render_batch_scaled check and fill alike for
 // image i: dm is the map the kernel reads through (for the scaled call the window is
 // folded in; dm.out_width x out_height is then the window), ow x oh the size written.
@@ -607,9 +744,9 @@ static int render_ring_slot(heifgpu_ctx *ctx, RenderRing::Slot **out) {
     return HEIFGPU_OK;
 }
 
-int heifgpu_render_batch(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
-                         const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
-                         const heifgpu_surface *out, void *stream) {
+static int render_batch_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                             const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                             const heifgpu_color_transform *const *xf, const heifgpu_surface *out, void *stream) {
     if (!ctx || !imgs || !in || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
     if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
     if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
@@ -627,19 +764,37 @@ int heifgpu_render_batch(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, siz
         d.tiles = d.tiles_x * ((d.out_h + th - 1) / th);
         max_tiles = std::max(max_tiles, d.tiles);
     }
+    std::vector<ColorRef> refs;
+    if (int rc = color_refs_fill(ctx, imgs, n, format, xf, refs)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     RenderRing::Slot *slot = nullptr;
     if (int rc = render_ring_slot(ctx, &slot)) return rc;
     RenderRing::Slot &sl = *slot;
-    const size_t bytes = n * sizeof(RenderDesc);
+    const size_t dbytes = n * sizeof(RenderDesc), bytes = dbytes + refs.size() * sizeof(ColorRef);
     HIP_TRY(sl.host.reserve(bytes));
-    HIP_TRY(sl.dev.alloc(n));
-    std::memcpy(sl.host.p, descs.data(), bytes);
+    HIP_TRY(sl.dev.alloc((bytes + sizeof(RenderDesc) - 1) / sizeof(RenderDesc)));
+    std::memcpy(sl.host.p, descs.data(), dbytes);
+    if (!refs.empty()) std::memcpy(sl.host.p + dbytes, refs.data(), bytes - dbytes);  // behind the descriptors: one copy
     HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_render(sl.dev.p, int(n), max_tiles, int(format), bps, s));  // the one launch
+    if (refs.empty())
+        HIP_TRY(launch_render(sl.dev.p, int(n), max_tiles, int(format), bps, s));  // the one launch
+    else
+        HIP_TRY(launch_render_color(sl.dev.p, int(n), max_tiles, int(format), bps, s));
     HIP_TRY(hipEventRecord(sl.done, s));
     sl.pending = true;
     return HEIFGPU_OK;
+}
+
+int heifgpu_render_batch(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                         const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                         const heifgpu_surface *out, void *stream) {
+    return render_batch_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, nullptr, out, stream);
+}
+
+int heifgpu_render_batch_color(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                               const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                               const heifgpu_color_transform *const *xf, const heifgpu_surface *out, void *stream) {
+    return render_batch_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, xf, out, stream);
 }
 
 // round_half_up(n / d) = floor((2n + d) / 2d); n, d < 2^32
@@ -724,9 +879,10 @@ static int scale_desc_fill(size_t i, const heifgpu_image *const *imgs, const hei
     return HEIFGPU_OK;
 }
 
-int heifgpu_render_batch_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
-                                const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
-                                const heifgpu_scale *scale, const heifgpu_surface *out, void *stream) {
+static int render_scaled_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                              const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                              const heifgpu_scale *scale, const heifgpu_color_transform *const *xf,
+                              const heifgpu_surface *out, void *stream) {
     // (the context is looked at last: every check of the arguments answers without one)
     if (!imgs || !in || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
     if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
@@ -739,25 +895,46 @@ int heifgpu_render_batch_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *im
         max_tiles = std::max(max_tiles, descs[i].r.tiles);
     }
     if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
+    std::vector<ColorRef> refs;
+    if (int rc = color_refs_fill(ctx, imgs, n, format, xf, refs)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     RenderRing::Slot *slot = nullptr;
     if (int rc = render_ring_slot(ctx, &slot)) return rc;
     RenderRing::Slot &sl = *slot;
-    const size_t bytes = n * sizeof(ScaleDesc);
+    const size_t dbytes = n * sizeof(ScaleDesc), bytes = dbytes + refs.size() * sizeof(ColorRef);
     HIP_TRY(sl.host.reserve(bytes));
-    HIP_TRY(sl.sdev.alloc(n));
-    std::memcpy(sl.host.p, descs.data(), bytes);
+    HIP_TRY(sl.sdev.alloc((bytes + sizeof(ScaleDesc) - 1) / sizeof(ScaleDesc)));
+    std::memcpy(sl.host.p, descs.data(), dbytes);
+    if (!refs.empty()) std::memcpy(sl.host.p + dbytes, refs.data(), bytes - dbytes);  // behind the descriptors: one copy
     HIP_TRY(hipMemcpyAsync(sl.sdev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_render_scaled(sl.sdev.p, int(n), max_tiles, int(format), bps, s));  // the one launch
+    if (refs.empty())
+        HIP_TRY(launch_render_scaled(sl.sdev.p, int(n), max_tiles, int(format), bps, s));  // the one launch
+    else
+        HIP_TRY(launch_render_scaled_color(sl.sdev.p, int(n), max_tiles, int(format), bps, s));
     HIP_TRY(hipEventRecord(sl.done, s));
     sl.pending = true;
     return HEIFGPU_OK;
 }
 
-int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
-                                const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in,
-                                const heifgpu_tensor_format *fmt, const heifgpu_scale *scale, const uint32_t *flip,
-                                const heifgpu_tensor_surface *out, void *stream) {
+int heifgpu_render_batch_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                                const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                                const heifgpu_scale *scale, const heifgpu_surface *out, void *stream) {
+    return render_scaled_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, scale, nullptr, out, stream);
+}
+
+int heifgpu_render_batch_scaled_color(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                      const heifgpu_planes *in, const heifgpu_image *const *alpha_imgs,
+                                      const heifgpu_planes *alpha_in, uint32_t format, const heifgpu_scale *scale,
+                                      const heifgpu_color_transform *const *xf, const heifgpu_surface *out,
+                                      void *stream) {
+    return render_scaled_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, scale, xf, out, stream);
+}
+
+static int render_tensor_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                              const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in,
+                              const heifgpu_tensor_format *fmt, const heifgpu_scale *scale, const uint32_t *flip,
+                              const heifgpu_color_transform *const *xf, const heifgpu_tensor_surface *out,
+                              void *stream) {
     // (the context is looked at last, as in heifgpu_render_batch_scaled)
     if (!imgs || !in || !fmt || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
     if (fmt->src > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "source format");
@@ -797,19 +974,41 @@ int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *im
         max_tiles = std::max(max_tiles, td.s.r.tiles);
     }
     if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
+    std::vector<ColorRef> refs;
+    if (int rc = color_refs_fill(ctx, imgs, n, fmt->src, xf, refs)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     RenderRing::Slot *slot = nullptr;
     if (int rc = render_ring_slot(ctx, &slot)) return rc;
     RenderRing::Slot &sl = *slot;
-    const size_t bytes = n * sizeof(TensorDesc);
+    const size_t dbytes = n * sizeof(TensorDesc), bytes = dbytes + refs.size() * sizeof(ColorRef);
     HIP_TRY(sl.host.reserve(bytes));
-    HIP_TRY(sl.tdev.alloc(n));
-    std::memcpy(sl.host.p, descs.data(), bytes);
+    HIP_TRY(sl.tdev.alloc((bytes + sizeof(TensorDesc) - 1) / sizeof(TensorDesc)));
+    std::memcpy(sl.host.p, descs.data(), dbytes);
+    if (!refs.empty()) std::memcpy(sl.host.p + dbytes, refs.data(), bytes - dbytes);  // behind the descriptors: one copy
     HIP_TRY(hipMemcpyAsync(sl.tdev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_render_tensor(sl.tdev.p, int(n), max_tiles, int(fmt->src), bps, s));  // the one launch
+    if (refs.empty())
+        HIP_TRY(launch_render_tensor(sl.tdev.p, int(n), max_tiles, int(fmt->src), bps, s));  // the one launch
+    else
+        HIP_TRY(launch_render_tensor_color(sl.tdev.p, int(n), max_tiles, int(fmt->src), bps, s));
     HIP_TRY(hipEventRecord(sl.done, s));
     sl.pending = true;
     return HEIFGPU_OK;
+}
+
+int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                                const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in,
+                                const heifgpu_tensor_format *fmt, const heifgpu_scale *scale, const uint32_t *flip,
+                                const heifgpu_tensor_surface *out, void *stream) {
+    return render_tensor_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, fmt, scale, flip, nullptr, out, stream);
+}
+
+int heifgpu_render_batch_tensor_color(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                      const heifgpu_planes *in, const heifgpu_image *const *alpha_imgs,
+                                      const heifgpu_planes *alpha_in, const heifgpu_tensor_format *fmt,
+                                      const heifgpu_scale *scale, const uint32_t *flip,
+                                      const heifgpu_color_transform *const *xf, const heifgpu_tensor_surface *out,
+                                      void *stream) {
+    return render_tensor_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, fmt, scale, flip, xf, out, stream);
 }
 
 void heifgpu_image_free(heifgpu_image *img) { delete img; }
@@ -868,6 +1067,7 @@ void heifgpu_destroy(heifgpu_ctx *ctx) {
     if (ctx->upload) (void)hipStreamDestroy(ctx->upload);
     if (ctx->prep) (void)hipStreamDestroy(ctx->prep);
     delete ctx->render;
+    delete ctx->color;
     delete ctx;
 }
 

@@ -206,13 +206,20 @@ ParsedImage parse_heic(const uint8_t *data, size_t len, uint32_t item_id) {
     for (uint32_t idx : pi->properties) {
         if (idx == 0 || idx > heif.properties.size()) continue;
         const Property &p = heif.properties[idx - 1];
-        if (p.type != fourcc('c', 'o', 'l', 'r') || p.length < 11) continue;
+        if (p.type != fourcc('c', 'o', 'l', 'r') || p.length < 4) continue;
         const uint8_t *q = data + p.offset;
-        if (((uint32_t(q[0]) << 24) | (uint32_t(q[1]) << 16) | (uint32_t(q[2]) << 8) | q[3]) != fourcc('n', 'c', 'l', 'x'))
-            continue;
+        const uint32_t kind = (uint32_t(q[0]) << 24) | (uint32_t(q[1]) << 16) | (uint32_t(q[2]) << 8) | q[3];
+        if ((kind == fourcc('p', 'r', 'o', 'f') || kind == fourcc('r', 'I', 'C', 'C')) && !img.color.has_icc) {
+            img.color.has_icc = true;  // the profile defines the colour space; its bytes are kept unread
+            img.color.icc.assign(q + 4, q + p.length);
+        }
+        if (kind != fourcc('n', 'c', 'l', 'x') || p.length < 11) continue;
         img.nclx = true;
         img.nclx_matrix = (uint32_t(q[8]) << 8) | q[9];
         img.nclx_full_range = q[10] >> 7;
+        img.color.has_nclx = true;
+        img.color.primaries = (uint32_t(q[4]) << 8) | q[5];
+        img.color.transfer = (uint32_t(q[6]) << 8) | q[7];
     }
     img.num_thumbnails = heif.num_thumbnails();
 

@@ -5,6 +5,7 @@
 
 #include "heif_reader.hpp"
 #include "hevc_ps.hpp"
+#include "icc.hpp"
 
 namespace hg {
 
@@ -66,6 +67,9 @@ struct ParsedImage {
     uint32_t aux_item_id = 0;  // first auxiliary image of the primary ('auxl'), 0 if none
     bool nclx = false;         // the item has an nclx colr (overrides the VUI colour description)
     uint32_t nclx_matrix = 0, nclx_full_range = 0;
+    // every colr of the item: the profile's bytes, the nclx primaries and transfer (icc.hpp);
+    // nothing is read out of the profile here, a file with an odd one parses and decodes
+    ColorDesc color;
     uint32_t rows = 1, cols = 1, out_width = 0, out_height = 0;
     uint32_t tile_width = 0, tile_height = 0, coded_bytes = 0;
     // the item's transformative properties (clap / irot / imir) in ipma order, folded

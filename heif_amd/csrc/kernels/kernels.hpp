@@ -131,6 +131,7 @@ inline void color_coefs(uint32_t matrix, bool full, ColorArgs &c) {
 // m[2]*ox + m[3]*oy + t[1]); the host has checked that the whole output maps
 // inside the w x h planes.
 enum : int { RENDER_RGB8 = 0, RENDER_RGBA8 = 1, RENDER_RGB16 = 2, RENDER_RGBA16 = 3 };
+constexpr int kRenderXf = 4;  // added to a kernel's format parameter: the colour-managed instantiation
 constexpr int kRenderTile = 64;                   // axis-swapping images: 64 x 64 output pixels per workgroup
 constexpr int kRenderRowW = 256, kRenderRowH = 16;  // the others: 256 x 16
 struct RenderDesc {
@@ -209,6 +210,18 @@ struct TensorDesc {
     int32_t elem, layout;
     float a[4], b[4];
 };
+
+// The colour-managed renders (heifgpu_render_batch_color and its kin): one ColorRef per
+// image, in the same device array behind the call's descriptors.  lut addresses the
+// transform's tables in the context's cache, in_lut[3][n] (uint16) then 4096 words out_lut[i] | out_lut[i + 1] << 16;
+// 0 leaves the image as the unmanaged render writes it.  color_xform.hpp has the arithmetic.
+struct ColorRef {
+    uint64_t lut;
+    int32_t n;     // 1 << B
+    int32_t m[9];  // Q14
+    int32_t pad[2];
+};
+static_assert(sizeof(ColorRef) == 56, "ColorRef: a multiple of 8 bytes behind the descriptors");
 
 // parse modes (BatchArgs::parse_mode; heifgpu_batch_opts::parse_mode)
 // (4 was r05's row waves, HEIFGPU_PARSE_ROWS: removed in ABI 6, prepare answers HEIFGPU_E_UNSUPPORTED)
@@ -291,6 +304,13 @@ hipError_t launch_render_scaled(const ScaleDesc *descs, int n_images, int max_ti
                                 hipStream_t s);
 hipError_t launch_render_tensor(const TensorDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
                                 hipStream_t s);
+// the same three with a ColorRef per image behind the n_images descriptors (lut == 0: image i untouched)
+hipError_t launch_render_color(const RenderDesc *descs, int n_images, int max_tiles, int format,
+                               int bytes_per_sample, hipStream_t s);
+hipError_t launch_render_scaled_color(const ScaleDesc *descs, int n_images, int max_tiles,
+                                      int format, int bytes_per_sample, hipStream_t s);
+hipError_t launch_render_tensor_color(const TensorDesc *descs, int n_images, int max_tiles,
+                                      int format, int bytes_per_sample, hipStream_t s);
 hipError_t launch_parse(const BatchArgs &a, hipStream_t s);
 // (launch_parse's: the kernels of parse_solo.hip and parse_lean.hip)
 hipError_t launch_parse_solo(const BatchArgs &a, hipStream_t s);

@@ -33,8 +33,21 @@
 // convert()'s arithmetic and store_row.  With a TensorDesc the same kernel ends in
 // store_tensor instead (heifgpu_render_batch_tensor): the same integers, scaled
 // and biased per channel, as f32 / f16 / bf16, planar or interleaved.
+//
+// The colour-managed calls (heifgpu_render_batch_color and its kin) run the same
+// bodies compiled with XF: a ColorRef per image names the transform's tables in
+// device memory (out_lut as pairs: six gathers per pixel), and color_xform_px
+// (color_xform.hpp) turns every RGB triple
+// into the destination space: behind convert() in k_render, on the rounded
+// averages in the result tile of k_render_scaled, before either store.  The
+// tables are read where they lie (global loads that the L1 / L2 serve, out of
+// 17.5 KiB at 8 bits, 40 KiB at 12), not staged
+// through LDS: k_render's axis-keeping path has no barrier to stage behind, and
+// the 16-bit formats already sit at the LDS occupancy limit.  The unmanaged
+// kernels are the XF = false instantiations under their old names and arguments.
 #include <type_traits>
 
+#include "color_xform.hpp"
 #include "kernels.hpp"
 
 namespace hg {
@@ -50,6 +63,24 @@ template <typename T>
 __device__ __forceinline__ int sample(uint64_t plane, int32_t pitch, int x, int y) {
     return (int)*reinterpret_cast<const T *>(reinterpret_cast<const uint8_t *>(plane) + (size_t)y * (size_t)pitch +
                                              (size_t)x * sizeof(T));
+}
+
+// the transform's tables through global-address-space pointers (global_load, not flat_load)
+typedef const uint16_t __attribute__((address_space(1))) *XfLut;
+
+// the transform of one RGB triple, in place (x.lut != 0); staged: the same tables copied
+// to LDS (the HG_XF_LDS build, an A/B of where the tables are read from), else null
+__device__ __forceinline__ void xform_rgb(const ColorRef &x, uint32_t &R, uint32_t &G, uint32_t &B,
+                                          const uint16_t *staged = nullptr) {
+    if (staged) {
+        const XfOutPairs<const uint32_t *> out{reinterpret_cast<const uint32_t *>(staged + 3 * x.n)};
+        color_xform_px(staged, x.n, out, x.m, R, G, B);
+        return;
+    }
+    typedef const uint32_t __attribute__((address_space(1))) *XfWords;
+    const XfLut in = (XfLut)x.lut;
+    const XfOutPairs<XfWords> out{(XfWords)(x.lut + 6 * (uint64_t)x.n)};
+    color_xform_px(in, x.n, out, x.m, R, G, B);
 }
 
 template <typename Pel, int FMT>
@@ -142,13 +173,44 @@ __device__ __forceinline__ void store_row(const RenderDesc &d, int oy, int oxw, 
     }
 }
 
-template <typename Pel, int FMT>
+// the transform of a converted pixel, in place (alpha kept)
+template <int FMT>
+__device__ __forceinline__ void xform_pixel(const ColorRef &x, Px &p, const uint16_t *staged) {
+    uint32_t R, G, B;
+    if (FMT >= RENDER_RGB16) R = p.lo & 0xffffu, G = p.lo >> 16, B = p.hi & 0xffffu;
+    else R = p.lo & 0xffu, G = (p.lo >> 8) & 0xffu, B = (p.lo >> 16) & 0xffu;
+    xform_rgb(x, R, G, B, staged);
+    if (FMT >= RENDER_RGB16) p = {R | (G << 16), B | (p.hi & 0xffff0000u)};
+    else p = {R | (G << 8) | (B << 16) | (p.lo & 0xff000000u), 0};
+}
+
+// FMTX: the pixel format, plus kRenderXf for the colour-managed instantiations, whose
+// ColorRefs lie behind the call's gridDim.y descriptors
+template <typename Pel, int FMTX>
 __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
+    constexpr int FMT = FMTX & 3;
+    constexpr bool XF = (FMTX & kRenderXf) != 0;
     constexpr bool WIDE = FMT >= RENDER_RGB16;
     constexpr int T = kRenderTile, LP = kRenderTile + 1;  // LDS pitch in dwords: 65, not 64 (bank conflicts)
     __shared__ uint32_t tile_lds[(WIDE ? 2 : 1) * T * LP];
     const RenderDesc d = descs[blockIdx.y];
     if ((int)blockIdx.x >= d.tiles) return;  // (a smaller image of the batch: the whole workgroup leaves)
+    ColorRef x{};
+    if constexpr (XF) x = reinterpret_cast<const ColorRef *>(descs + gridDim.y)[blockIdx.y];
+    const uint16_t *staged = nullptr;
+#if defined(HG_XF_LDS)
+    // the A/B of DESIGN 5.25: every workgroup copies its image's tables (1.5 + 16 KiB at 8 bits,
+    // 24 + 16 KiB at 12) into LDS first and reads them there
+    __shared__ uint32_t xf_lds[XF ? (3 * (WIDE ? 4096 : 256)) / 2 + kXfPairEntries : 1];
+    if constexpr (XF) {
+        if (x.lut) {  // (uniform)
+            const uint32_t __attribute__((address_space(1))) *src = (const uint32_t __attribute__((address_space(1))) *)x.lut;
+            for (int i = (int)threadIdx.x; i < 3 * x.n / 2 + kXfPairEntries; i += 256) xf_lds[i] = src[i];
+            __syncthreads();
+            staged = reinterpret_cast<const uint16_t *>(xf_lds);
+        }
+    }
+#endif
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int tx = (int)blockIdx.x % d.tiles_x, ty = (int)blockIdx.x / d.tiles_x;
     const Px none = {0, 0};
@@ -159,7 +221,11 @@ __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
         for (int r = 0; r < kRenderRowH; ++r) {
             const int oy = ty * kRenderRowH + r;
             if (oy >= d.out_h) break;
-            store_row<FMT>(d, oy, oxw, lane, valid ? convert<Pel, FMT>(d, ox, oy) : none, valid);
+            Px p = valid ? convert<Pel, FMT>(d, ox, oy) : none;
+            if constexpr (XF) {
+                if (x.lut) xform_pixel<FMT>(x, p, staged);  // (uniform: the image's transform, or none)
+            }
+            store_row<FMT>(d, oy, oxw, lane, p, valid);
         }
         return;
     }
@@ -168,7 +234,10 @@ __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
     for (int i = 0; i < T / 4; ++i) {
         const int oxl = wave * (T / 4) + i, ox = ox0 + oxl, oy = oy0 + lane;
         if (ox < d.out_w && oy < d.out_h) {
-            const Px p = convert<Pel, FMT>(d, ox, oy);
+            Px p = convert<Pel, FMT>(d, ox, oy);
+            if constexpr (XF) {
+                if (x.lut) xform_pixel<FMT>(x, p, staged);
+            }
             tile_lds[oxl * LP + lane] = p.lo;
             if (WIDE) tile_lds[T * LP + oxl * LP + lane] = p.hi;
         }
@@ -185,6 +254,16 @@ __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
             if (WIDE) p.hi = tile_lds[T * LP + lane * LP + oyl];
         }
         store_row<FMT>(d, oy, ox0, lane, p, valid);
+    }
+}
+
+template <typename Pel>
+void launch_fmt_xf(const RenderDesc *descs, dim3 grid, int format, hipStream_t s) {
+    switch (format) {
+    case RENDER_RGB8: hipLaunchKernelGGL((k_render<Pel, RENDER_RGB8 | kRenderXf>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGBA8: hipLaunchKernelGGL((k_render<Pel, RENDER_RGBA8 | kRenderXf>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGB16: hipLaunchKernelGGL((k_render<Pel, RENDER_RGB16 | kRenderXf>), grid, dim3(256), 0, s, descs); break;
+    default: hipLaunchKernelGGL((k_render<Pel, RENDER_RGBA16 | kRenderXf>), grid, dim3(256), 0, s, descs); break;
     }
 }
 
@@ -435,8 +514,10 @@ __device__ __forceinline__ void store_tensor(const TensorDesc &td, int oy, int o
 __device__ __forceinline__ const ScaleDesc &scale_of(const ScaleDesc &s) { return s; }
 __device__ __forceinline__ const ScaleDesc &scale_of(const TensorDesc &t) { return t.s; }
 
-template <typename Pel, int FMT, typename Desc>
+template <typename Pel, int FMTX, typename Desc>
 __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
+    constexpr int FMT = FMTX & 3;
+    constexpr bool XF = (FMTX & kRenderXf) != 0;  // (as k_render's)
     constexpr bool TENSOR = std::is_same<Desc, TensorDesc>::value;  // (else ScaleDesc: the integer surfaces)
     constexpr bool WIDE = FMT >= RENDER_RGB16;
     constexpr int NCH = (FMT & 1) ? 4 : 3;
@@ -515,6 +596,26 @@ __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
         }
     }
     __syncthreads();
+    if constexpr (XF) {
+        // the transform of the tile's rounded averages, in place in the result tile
+        const ColorRef x = reinterpret_cast<const ColorRef *>(descs + gridDim.y)[blockIdx.y];
+        if (x.lut) {  // (uniform)
+            const int nbv = b1 - b0, cnt = (a1 - a0) * nbv;
+            for (int idx = t; idx < cnt; idx += 256) {
+                const int al = idx / nbv, at = al * lp + (idx - al * nbv);
+                Px p = {res[at], WIDE ? res[RES + at] : 0u};
+                uint32_t R = px_channel<FMT>(p, 0), G = px_channel<FMT>(p, 1), B = px_channel<FMT>(p, 2);
+                xform_rgb(x, R, G, B);
+                if (WIDE) {
+                    res[at] = R | (G << 16);
+                    res[RES + at] = B | (p.hi & 0xffff0000u);
+                } else {
+                    res[at] = R | (G << 8) | (B << 16) | (p.lo & 0xff000000u);
+                }
+            }
+            __syncthreads();
+        }
+    }
     // write: lanes along the output's x, 64 pixels of a row per wave and step
     const Px none = {0, 0};
     if (!d.swap) {
@@ -557,6 +658,16 @@ __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
     }
 }
 
+template <typename Pel, typename Desc>
+void launch_scaled_fmt_xf(const Desc *descs, dim3 grid, int format, hipStream_t s) {
+    switch (format) {
+    case RENDER_RGB8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB8 | kRenderXf, Desc>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGBA8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA8 | kRenderXf, Desc>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGB16: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB16 | kRenderXf, Desc>), grid, dim3(256), 0, s, descs); break;
+    default: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA16 | kRenderXf, Desc>), grid, dim3(256), 0, s, descs); break;
+    }
+}
+
 // Desc = ScaleDesc: the integer surfaces; TensorDesc: the tensor epilogue (element type
 // and layout are uniform branches in store_tensor, so the heavy body is compiled once
 // per sample width and source format for each of the two)
@@ -585,6 +696,31 @@ hipError_t launch_render_tensor(const TensorDesc *descs, int n_images, int max_t
     const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
     if (bytes_per_sample == 1) launch_scaled_fmt<uint8_t>(descs, grid, format, s);
     else launch_scaled_fmt<uint16_t>(descs, grid, format, s);
+    return hipGetLastError();
+}
+
+// (the ColorRefs lie behind the n_images descriptors, where the kernels look for them)
+hipError_t launch_render_color(const RenderDesc *descs, int n_images, int max_tiles, int format,
+                               int bytes_per_sample, hipStream_t s) {
+    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
+    if (bytes_per_sample == 1) launch_fmt_xf<uint8_t>(descs, grid, format, s);
+    else launch_fmt_xf<uint16_t>(descs, grid, format, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_render_scaled_color(const ScaleDesc *descs, int n_images, int max_tiles,
+                                      int format, int bytes_per_sample, hipStream_t s) {
+    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
+    if (bytes_per_sample == 1) launch_scaled_fmt_xf<uint8_t>(descs, grid, format, s);
+    else launch_scaled_fmt_xf<uint16_t>(descs, grid, format, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_render_tensor_color(const TensorDesc *descs, int n_images, int max_tiles,
+                                      int format, int bytes_per_sample, hipStream_t s) {
+    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
+    if (bytes_per_sample == 1) launch_scaled_fmt_xf<uint8_t>(descs, grid, format, s);
+    else launch_scaled_fmt_xf<uint16_t>(descs, grid, format, s);
     return hipGetLastError();
 }
 

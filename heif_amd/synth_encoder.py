@@ -293,7 +293,7 @@ def _len_prefixed(nal: bytes) -> bytes:
 
 
 def grid_heic(out_w: int, out_h: int, p: SynthParams, seed: int = 0, pictures: Optional[List[bytes]] = None,
-              layout: Optional[BoxLayout] = None, transforms: Tuple[bytes, ...] = (), colr: Optional[bytes] = None,
+              layout: Optional[BoxLayout] = None, transforms: Tuple[bytes, ...] = (), colr=None,
               aux: Tuple["AuxImage", ...] = ()) -> bytes:
     """A grid HEIC of ceil(out_w/W) x ceil(out_h/H) synthetic tiles of p's
     size, tile k drawn with seed (seed << 16) + k.  `colr` (nclx_box) and then
@@ -318,7 +318,7 @@ def grid_heic(out_w: int, out_h: int, p: SynthParams, seed: int = 0, pictures: O
     for k in range(n):
         items.append((k + 2, b"hvc1", items_data[k]))
     grid_idx = [3]
-    for box in ([colr] if colr else []) + list(transforms):
+    for box in _colr_boxes(colr) + list(transforms):
         props.append(box)
         grid_idx.append(len(props))
     assoc = [(grid_id, grid_idx)] + [(k + 2, [1, 2]) for k in range(n)]
@@ -383,6 +383,78 @@ def nclx_box(primaries: int, transfer: int, matrix: int, full_range: bool) -> by
     return _box(b"colr", b"nclx" + struct.pack(">HHHB", primaries, transfer, matrix, 0x80 if full_range else 0))
 
 
+def icc_box(profile: bytes, kind: bytes = b"prof") -> bytes:
+    """A colr box that carries an ICC profile (kind b"prof", or b"rICC")."""
+    return _box(b"colr", kind + profile)
+
+
+def _colr_boxes(colr) -> List[bytes]:
+    """colr= of display_heic / grid_heic: None, one box, or a sequence of boxes."""
+    if not colr:
+        return []
+    return [colr] if isinstance(colr, (bytes, bytearray)) else list(colr)
+
+
+def _s15f16(v: float) -> bytes:
+    return _be(int(round(v * 65536.0)), 4)
+
+
+def icc_curv(values=()) -> bytes:
+    """A curveType tag: no values = the identity, one float = a u8.8 gamma, more = a
+    table of 16-bit entries (given as integers 0..65535)."""
+    if len(values) == 1:
+        body = struct.pack(">H", int(round(values[0] * 256.0)))
+    else:
+        body = b"".join(struct.pack(">H", int(v)) for v in values)
+    return b"curv" + bytes(4) + struct.pack(">I", len(values)) + body
+
+
+def icc_para(function_type: int, params, raw: bool = False) -> bytes:
+    """A parametricCurveType tag: function type 0..4 with its 1, 3, 4, 5 or 7
+    parameters g a b c d e f (ICC.1:2010 table 68) as floats, or with raw=True as
+    s15.16 integers."""
+    body = b"".join(_be(int(v), 4) if raw else _s15f16(v) for v in params)
+    return b"para" + bytes(4) + struct.pack(">HH", function_type, 0) + body
+
+
+# the sRGB curve as Display P3 profiles state it: para type 3, s15.16
+ICC_SRGB_PARA = icc_para(3, (0x26666, 0xF2A7, 0x0D59, 0x13D0, 0x0A5B), raw=True)
+# X Y Z of R, G, B (D50) as s15.16 integers
+ICC_COLORANTS_DISPLAY_P3 = ((0x83DF, 0x3DBF, -0x45), (0x4ABF, 0xB137, 0x0AB9), (0x2838, 0x110B, 0xC8B9))
+ICC_COLORANTS_SRGB = ((0x6FA2, 0x38F5, 0x0390), (0x6299, 0xB785, 0x18DA), (0x24A0, 0x0F84, 0xB6CF))
+
+
+def icc_profile(colorants, trc, version: int = 4, extra_tags=(), data_space: bytes = b"RGB ", pcs: bytes = b"XYZ ",
+                raw_colorants: bool = False) -> bytes:
+    """A small three-component matrix/TRC ICC profile: `colorants` are X Y Z of
+    R, G, B (floats, or s15.16 integers with raw_colorants), `trc` one tag body
+    (icc_curv / icc_para) shared by the three channels, or three of them.
+    extra_tags: (signature, body) pairs appended to the tag table (a b"A2B0"
+    for a LUT profile, say); colorants None leaves rXYZ / gXYZ / bXYZ out."""
+    trcs = [trc] * 3 if isinstance(trc, (bytes, bytearray)) else list(trc)
+    tags = []
+    if colorants is not None:
+        for sig, xyz in zip((b"rXYZ", b"gXYZ", b"bXYZ"), colorants):
+            tags.append((sig, b"XYZ " + bytes(4) + b"".join(_be(int(v), 4) if raw_colorants else _s15f16(v) for v in xyz)))
+    for sig, body in zip((b"rTRC", b"gTRC", b"bTRC"), trcs):
+        tags.append((sig, bytes(body)))
+    tags += [(bytes(sig), bytes(body)) for sig, body in extra_tags]
+    table_end = 132 + 12 * len(tags)
+    blobs, where, entries, off = [], {}, [], table_end
+    for sig, body in tags:
+        if body not in where:  # equal tags share their data, as the TRCs of real profiles do
+            where[body] = off
+            pad = -len(body) % 4
+            blobs.append(body + bytes(pad))
+            off += len(body) + pad
+        entries.append(sig + struct.pack(">II", where[body], len(body)))
+    size = off
+    header = (struct.pack(">I", size) + bytes(4) + struct.pack(">I", version << 24) + b"mntr" + data_space + pcs +
+              bytes(12) + b"acsp" + bytes(28) + struct.pack(">III", 0xF6D6, 0x10000, 0xD32D) + bytes(48))
+    assert len(header) == 128
+    return header + struct.pack(">I", len(tags)) + b"".join(entries) + b"".join(blobs)
+
+
 def auxc_box(urn: str) -> bytes:
     return _fbox(b"auxC", 0, 0, urn.encode() + b"\0")
 
@@ -398,17 +470,18 @@ class AuxImage:
 
 
 def display_heic(p: SynthParams, seed: int = 0, transforms: Tuple[bytes, ...] = (), aux: Tuple[AuxImage, ...] = (),
-                 colr: Optional[bytes] = None, layout: Optional[BoxLayout] = None) -> bytes:
+                 colr=None, layout: Optional[BoxLayout] = None) -> bytes:
     """single_heic plus what a viewer needs: `transforms` (property boxes from
     clap_box / irot_box / imir_box, or raw bytes) are associated with the
     primary after hvcC and ispe in the order given, which is the order a reader
-    applies them in; `colr` (nclx_box) goes in front of them.  Every `aux`
+    applies them in; `colr` (nclx_box or icc_box, or a sequence of them: an
+    item may carry a profile and an nclx) goes in front of them.  Every `aux`
     entry becomes an item of its own with hvcC, ispe and auxC, an 'auxl'
     reference to the primary and, when premultiplied, a 'prem' reference from
     the primary."""
     props = [hvcc(p, *parameter_sets(p)), _ispe(p.width - p.conf_right, p.height - p.conf_bottom)]
     primary_idx = [1, 2]
-    for box in ([colr] if colr else []) + list(transforms):
+    for box in _colr_boxes(colr) + list(transforms):
         props.append(box)
         primary_idx.append(len(props))
     items = [(1, b"hvc1", picture_item(p, seed))]

@@ -405,6 +405,126 @@ int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *im
                                 const heifgpu_tensor_format *fmt, const heifgpu_scale *scale,
                                 const uint32_t *flip, const heifgpu_tensor_surface *out, void *stream);
 
+/* ---- colour-managed render: ICC / nclx source to sRGB or Display P3 ----------
+ * (added within ABI 6: new entry points only.)
+ * The renders above apply the colr matrix and range and nothing else: their RGB
+ * is in the image's own colour space.  The calls below describe that space and
+ * convert every RGB triple of a render to a destination space in the same launch.
+ *
+ * THE SOURCE (ISO/IEC 23008-12 6.5.5).  Every colr of the decoded item is kept.
+ * An ICC profile ('prof' / 'rICC') defines the colour space; an nclx in the same
+ * item still supplies the YCbCr matrix and range.  Without a profile an nclx
+ * defines it; with no colr, or for colour_primaries or transfer_characteristics
+ * 2 (unspecified), sRGB is assumed.
+ *   ICC: three-component matrix/TRC profiles, v2 and v4, data space 'RGB ', PCS
+ *   'XYZ ': rXYZ / gXYZ / bXYZ (XYZType, D50-adapted as they are; chad and wtpt
+ *   are read past) and rTRC / gTRC / bTRC, which may share an offset: 'curv' with
+ *   count 0 (identity), 1 (u8.8 gamma) or n (a table, interpolated linearly) and
+ *   'para' function types 0..4 (ICC.1:2010 table 68).  LUT-only profiles, a Lab
+ *   PCS, another data space or a 'para' type above 4 are HEIFGPU_E_UNSUPPORTED; a
+ *   size field beyond the box, a tag offset or length outside the profile, a
+ *   'curv' count beyond its tag are HEIFGPU_E_PARSE.  Both are answered when a
+ *   transform is asked for, never at parse or decode: such files decode as before.
+ *   nclx: primaries 1 (BT.709 / sRGB), 9 (BT.2020), 12 (P3 D65) from their
+ *   chromaticities to XYZ, Bradford-adapted to the ICC D50 white (s15.16 F6D6
+ *   10000 D32D), in double.  Transfer 1, 6, 13, 14, 15: the sRGB curve (709-coded
+ *   stills are shown as sRGB, as browsers and libheif show them); 8: linear; 4:
+ *   gamma 2.2; 16 (PQ) and 18 (HLG) need tone mapping and every other code is
+ *   HEIFGPU_E_UNSUPPORTED.
+ * THE DESTINATIONS both encode with the sRGB curve g; colourants (X Y Z, s15.16):
+ *   HEIFGPU_CS_SRGB        R 6FA2 38F5 0390      G 6299 B785 18DA   B 24A0 0F84 B6CF
+ *   HEIFGPU_CS_DISPLAY_P3  R 83DF 3DBF FFFFFFBB  G 4ABF B137 0AB9   B 2838 110B C8B9
+ * THE TRANSFORM is made for the depth B the render computes at (8 for the 8-bit
+ * formats, the image's depth, at most 12, for the 16-bit ones), maxv = (1<<B)-1:
+ *   in_lut[c][v] = round_half_up(65535 * clamp(f_c(v / maxv), 0, 1)),  v in [0, 1<<B),
+ *                  f_c channel c's TRC
+ *   m            = inv(Dst) * Src in double, each row divided by its sum (the s15.16
+ *                  colourants of two spaces sum to whites that differ in the last
+ *                  digits, sRGB's to F6DB FFFE D339 and Display P3's to F6D6 10001
+ *                  D32D: row sums of 1 +- 3e-4 otherwise), then in Q14, each entry
+ *                  rounded to nearest (m_rounded), then the largest entry of each row
+ *                  adjusted so that the row sums to 16384 exactly (neutral in,
+ *                  neutral out when the TRCs are equal); an nclx source of the
+ *                  destination's own primaries code gets exactly 16384 * I
+ *   out_lut[i]   = round_half_up(16 * maxv * g(min(16 * i, 65535) / 65535)),  i in [0, 4096]
+ *                  (1/16 code; 16 bits hold it up to B = 12)
+ *   identity     = m == 16384 * I and every code 0..maxv of every channel maps to
+ *                  itself; a render given an identity transform takes the unmanaged path
+ * Per pixel, with (c_0, c_1, c_2) the R, G, B integers the unmanaged render gives:
+ *   L_c  = in_lut[c][c_c]
+ *   L'_k = clamp((m[3k]*L_0 + m[3k+1]*L_1 + m[3k+2]*L_2 + 8192) >> 14, 0, 65535)
+ *          (64-bit sum, arithmetic shift)
+ *   i = L'_k >> 4, f = L'_k & 15
+ *   out_k = (out_lut[i]*(16-f) + out_lut[i+1]*f + 128) >> 8
+ * Alpha is not touched.  numpy reproduces this bit for bit (tests/color_ref.py);
+ * kernels/color_xform.hpp is its one statement in code, shared by the kernels and
+ * heifgpu_color_apply.  The scaled and tensor renders transform the rounded
+ * average R (what heifgpu_render_batch_scaled writes), not each source pixel:
+ * averaging in linear light is another feature and is not done here. */
+enum { HEIFGPU_CS_SRGB = 0, HEIFGPU_CS_DISPLAY_P3 = 1 };
+enum { HEIFGPU_COLOR_NONE = 0, HEIFGPU_COLOR_ICC = 1, HEIFGPU_COLOR_NCLX = 2 };
+typedef struct {
+    uint32_t kind;                    /* HEIFGPU_COLOR_*: what defines the colour space */
+    uint32_t has_nclx;                /* the item has an nclx colr (beside a profile or alone) */
+    uint32_t primaries, transfer;     /* of that nclx; 2 (unspecified) without one */
+    uint32_t icc_size;                /* bytes of the profile, 0 without one */
+    int32_t status;                   /* HEIFGPU_OK, or what a transform of this source answers */
+    double colorants[9];              /* X Y Z of R, then of G, then of B (D50); zeros unless status is OK */
+} heifgpu_color_info;
+typedef struct {
+    uint32_t bits;                    /* B */
+    uint32_t identity;
+    uint32_t dst;                     /* HEIFGPU_CS_* */
+    uint32_t reserved;
+    int32_t m[9];
+    int32_t m_rounded[9];             /* m before the row fix-up (informative) */
+    uint16_t in_lut[3][4096];         /* the first 1 << B entries of each are used */
+    uint16_t out_lut[4098];           /* 4097 used */
+} heifgpu_color_transform;
+/* host only, always HEIFGPU_OK for a parsed image */
+int heifgpu_image_get_color(const heifgpu_image *img, heifgpu_color_info *out);
+/* host only: the profile's bytes into buf (cap bytes; buf NULL or cap too small:
+ * only *len is set, to the profile's size; 0 without a profile) */
+int heifgpu_image_get_icc(const heifgpu_image *img, uint8_t *buf, size_t cap, size_t *len);
+/* host only: the transform of img's colour space to dst at depth bits (8..12). */
+int heifgpu_color_transform_make(const heifgpu_image *img, uint32_t dst, uint32_t bits,
+                                 heifgpu_color_transform *out);
+/* host only: the per-pixel formula over n_pixels R G B triples of codes
+ * 0..maxv (a larger code is HEIFGPU_E_INVALID); an identity transform is applied
+ * like any other.  rgb_out may be rgb_in. */
+int heifgpu_color_apply(const heifgpu_color_transform *t, const uint16_t *rgb_in, size_t n_pixels,
+                        uint16_t *rgb_out);
+/* The three renders with one transform pointer per image: xf[i] NULL or an
+ * identity transform leaves image i exactly as the unmanaged call writes it (xf
+ * NULL: all of them, and the call is the unmanaged call).  xf[i]->bits must be
+ * the depth image i is rendered at, else HEIFGPU_E_INVALID.  Still ONE launch and
+ * one descriptor copy whatever the mix of sources and depths is.  The tables live
+ * in device memory owned by the context, cached by content: a steady-state call
+ * uploads nothing, and a cached table is never rewritten (the cache is emptied,
+ * after a device synchronise, when it holds 256 tables).  The transforms are read
+ * during the call only. */
+int heifgpu_render_batch_color(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                               const heifgpu_planes *in,
+                               const heifgpu_image *const *alpha_imgs,
+                               const heifgpu_planes *alpha_in,
+                               uint32_t format, const heifgpu_color_transform *const *xf,
+                               const heifgpu_surface *out, void *stream);
+int heifgpu_render_batch_scaled_color(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                      const heifgpu_planes *in,
+                                      const heifgpu_image *const *alpha_imgs,
+                                      const heifgpu_planes *alpha_in,
+                                      uint32_t format, const heifgpu_scale *scale,
+                                      const heifgpu_color_transform *const *xf,
+                                      const heifgpu_surface *out, void *stream);
+int heifgpu_render_batch_tensor_color(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                      const heifgpu_planes *in,
+                                      const heifgpu_image *const *alpha_imgs,
+                                      const heifgpu_planes *alpha_in,
+                                      const heifgpu_tensor_format *fmt, const heifgpu_scale *scale,
+                                      const uint32_t *flip,
+                                      const heifgpu_color_transform *const *xf,
+                                      const heifgpu_tensor_surface *out, void *stream);
+
 /* ---- window decode: decode only the pictures a window reads ----------------
  * (added within ABI 6: new entry points only; heifgpu_batch_opts keeps its layout.)
  * A render of a window of the displayed picture (heifgpu_scale's x, y, width,

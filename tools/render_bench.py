@@ -40,7 +40,18 @@ spread (max - min over runs) of the two; f16_chw - scaled is reported.  Before
 timing, f16_chw is compared bit for bit with float32(R) * a + b of `scaled`'s
 integers computed by torch (a product, then a sum), at the size timed.
 
-usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json] [--scaled | --tensor]
+--color measures the colour-managed render (heifgpu_render_batch_color and its
+kin), Display P3 (halfmoonbay's profile) to sRGB, against the
+unmanaged call on the same images, the variants alternated in one process in
+each of the --runs runs:
+  rgb8_rot0 / rgb8_rot3   heifgpu_render_batch RGB8 at full size, rotation 0 and 3
+  rgba16_10bit            the same in RGBA16 of a 10-bit batch
+  tensor224_f16           heifgpu_render_batch_tensor, COVER to 224 x 224, f16 CHW
+each as `plain` and as `managed`.  With a library that has no colour entry
+points (HEIFGPU_LIBRARY naming the parent commit's build) only `plain` is
+measured: that is the A/B of the unmanaged kernels across the two commits.
+
+usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json] [--scaled | --tensor | --color]
 """
 import argparse
 import ctypes
@@ -286,6 +297,128 @@ def tensor_main(args):
         pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
 
 
+def color_main(args):
+    n = args.images
+    dev = torch.device("cuda", 0)
+    ctx = H.DecodeContext(0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    golden = (ROOT / "tests" / "golden" / "halfmoonbay.heic").read_bytes()
+    managed_ok = hasattr(_lib.lib, "heifgpu_render_batch_color")
+    g = torch.Generator(device=dev).manual_seed(1)
+
+    def planes_of(dtype, top):
+        ys = [torch.randint(0, top, (HGT, W), generator=g, device=dev, dtype=torch.int32).to(dtype) for _ in range(n)]
+        cs = [[torch.randint(0, top, (HGT // 2, W // 2), generator=g, device=dev, dtype=torch.int32).to(dtype)
+               for _ in range(n)] for _ in range(2)]
+        arr = (_lib.Planes * n)()
+        for i in range(n):
+            for c, t in enumerate((ys[i], cs[0][i], cs[1][i])):
+                arr[i].plane[c] = t.data_ptr()
+                arr[i].pitch[c] = t.stride(0) * t.element_size()
+        return arr, (ys, cs)
+
+    def transforms(img, bits):
+        if not managed_ok:
+            return None, None
+        t = img.color_transform("srgb", bits)
+        assert not t.identity
+        return (ctypes.c_void_p * n)(*[ctypes.addressof(t)] * n), t
+
+    px = n * W * HGT
+    result = {"images": n, "width": W, "height": HGT, "reps": args.reps, "runs": args.runs,
+              "device": torch.cuda.get_device_name(0), "hbm_peak_GBps": HBM_PEAK_GBS, "library": _lib.LIB_PATH.name,
+              "managed": managed_ok, "transform": "Display P3 profile (halfmoonbay) -> sRGB", "cases": {}}
+    cases = []  # (name, plain, managed or None, algorithmic bytes, what to keep alive)
+    planes8, keep8 = planes_of(torch.uint8, 256)
+    for rot in (0, 3):
+        img = H.HeifImage.parse(forced_rotation(golden, rot))
+        d = img.display
+        outs = [torch.empty((d.out_height, d.out_width, 3), dtype=torch.uint8, device=dev) for _ in range(n)]
+        surf = (_lib.Surface * n)()
+        for i, t in enumerate(outs):
+            surf[i].pixels, surf[i].pitch = t.data_ptr(), t.stride(0)
+        imgs = (ctypes.c_void_p * n)(*[img._h.value] * n)
+        xf, keep = transforms(img, 8)
+
+        def plain(imgs=imgs, surf=surf):
+            _lib.check(_lib.lib.heifgpu_render_batch(ctx._h, imgs, n, planes8, None, None, _lib.PIX_RGB8, surf, stream))
+
+        def managed(imgs=imgs, surf=surf, xf=xf):
+            _lib.check(_lib.lib.heifgpu_render_batch_color(ctx._h, imgs, n, planes8, None, None, _lib.PIX_RGB8, xf, surf,
+                                                           stream))
+        cases.append((f"rgb8_rot{rot}", plain, managed if managed_ok else None, px * 4.5, (img, outs, keep)))
+        if rot == 3:  # the tensor render of the same pictures
+            sc = (_lib.Scale * n)()
+            for i in range(n):
+                _lib.check(_lib.lib.heifgpu_scale_fit(ctypes.byref(d), 224, 224, _lib.FIT_COVER, ctypes.byref(sc[i])))
+            out = torch.empty((n, 3, 224, 224), dtype=torch.float16, device=dev)
+            fmt = _lib.TensorFormat(src=_lib.PIX_RGB8, elem=_lib.ELEM_F16, layout=_lib.LAYOUT_CHW)
+            for c, (m_, s_) in enumerate(zip((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))):
+                fmt.a[c], fmt.b[c] = 1.0 / (255.0 * s_), -m_ / s_
+            ts = (_lib.TensorSurface * n)()
+            for i in range(n):
+                ts[i].data, ts[i].stride_c, ts[i].stride_y = out[i].data_ptr(), 224 * 224 * 2, 224 * 2
+
+            def tplain(imgs=imgs, sc=sc, ts=ts, fmt=fmt):
+                _lib.check(_lib.lib.heifgpu_render_batch_tensor(ctx._h, imgs, n, planes8, None, None, ctypes.byref(fmt), sc,
+                                                                None, ts, stream))
+
+            def tmanaged(imgs=imgs, sc=sc, ts=ts, fmt=fmt, xf=xf):
+                _lib.check(_lib.lib.heifgpu_render_batch_tensor_color(ctx._h, imgs, n, planes8, None, None,
+                                                                      ctypes.byref(fmt), sc, None, xf, ts, stream))
+            window_px = (sc[0].width or d.out_width) * (sc[0].height or d.out_height)
+            cases.append(("tensor224_f16", tplain, tmanaged if managed_ok else None,
+                          n * (window_px * 1.5 + 224 * 224 * 6), (out,)))
+    # RGBA16 of a 10-bit batch of the same geometry carrying the same profile (only the host parse is needed)
+    p10 = S.SynthParams(bit_depth=10)
+    colr = S.icc_box(H.HeifImage.parse(golden).icc_profile) if managed_ok else None
+    img10 = H.HeifImage.parse(S.grid_heic(W, HGT, p10, pictures=[S.picture(p10, 1)] * 48, colr=colr))
+    planes10, keep10 = planes_of(torch.int16, 1024)
+    outs16 = [torch.empty((HGT, W, 4), dtype=torch.int16, device=dev) for _ in range(n)]
+    surf16 = (_lib.Surface * n)()
+    for i, t in enumerate(outs16):
+        surf16[i].pixels, surf16[i].pitch = t.data_ptr(), t.stride(0) * 2
+    imgs10 = (ctypes.c_void_p * n)(*[img10._h.value] * n)
+    xf10, keep_t10 = transforms(img10, 10)
+
+    def plain16():
+        _lib.check(_lib.lib.heifgpu_render_batch(ctx._h, imgs10, n, planes10, None, None, _lib.PIX_RGBA16, surf16, stream))
+
+    def managed16():
+        _lib.check(_lib.lib.heifgpu_render_batch_color(ctx._h, imgs10, n, planes10, None, None, _lib.PIX_RGBA16, xf10,
+                                                       surf16, stream))
+    cases.append(("rgba16_10bit", plain16, managed16 if managed_ok else None, px * 11.0, (img10, keep_t10)))
+
+    variants = []
+    for name, plain, managed, nbytes, _ in cases:
+        variants.append((name, "plain", plain, nbytes))
+        if managed is not None:
+            variants.append((name, "managed", managed, nbytes))
+    for *_, fn, _ in variants:  # warm-up (and the tables' one upload)
+        fn()
+    torch.cuda.synchronize()
+    ms = {(name, kind): [] for name, kind, _, _ in variants}
+    for _ in range(args.runs):
+        for name, kind, fn, _ in variants:
+            ms[(name, kind)].append(timed(fn, args.reps))
+    for name, kind, _, nbytes in variants:
+        r = summary(ms[(name, kind)], nbytes)
+        r["spread_ms"] = round(r["ms_max"] - r["ms_min"], 4)
+        result["cases"].setdefault(name, {})[kind] = r
+    for name, r in result["cases"].items():
+        if "managed" in r:
+            r["managed_over_plain"] = round(r["managed"]["ms_per_batch"] / r["plain"]["ms_per_batch"], 4)
+            r["managed_minus_plain_ms"] = round(r["managed"]["ms_per_batch"] - r["plain"]["ms_per_batch"], 4)
+            r["difference_inside_spread"] = bool(abs(r["managed_minus_plain_ms"]) <=
+                                                 max(r["managed"]["spread_ms"], r["plain"]["spread_ms"]))
+        print(f"{name}: " + ", ".join(f"{k} {r[k]['ms_per_batch']:.3f} ms ({r[k]['GBps']:.0f} GB/s, spread "
+                                      f"{r[k]['spread_ms']:.3f})" for k in ("plain", "managed") if k in r), flush=True)
+    print(json.dumps(result))
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=128)
@@ -294,7 +427,10 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--scaled", action="store_true", help="measure heifgpu_render_batch_scaled (see above)")
     ap.add_argument("--tensor", action="store_true", help="measure heifgpu_render_batch_tensor (see above)")
+    ap.add_argument("--color", action="store_true", help="measure the colour-managed render (see above)")
     args = ap.parse_args()
+    if args.color:
+        return color_main(args)
     if args.scaled:
         return scaled_main(args)
     if args.tensor:
