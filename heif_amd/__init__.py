@@ -428,34 +428,77 @@ class DecodeContext:
         alpha untouched); a source the library cannot transform raises
         UnsupportedError before anything is launched."""
         torch = self._torch
-        n = len(outs)
         f = _lib.PIX_FORMATS[fmt]
         ch, wide = (4 if f & 1 else 3), f >= _lib.PIX_RGB16
-        if any(o.image is None for o in outs) or (alphas is not None and any(a is not None and a.image is None for a in alphas)):
-            raise ValueError("render needs images that carry their HeifImage (alloc_outputs)")
-        if alphas is not None and len(alphas) != n:
-            raise ValueError("alphas must have one entry per image")
+        self._check_images("render", outs, alphas)
         for i, o in enumerate(outs):
             _check_valid("render", i, o, alphas[i] if alphas is not None else None, None)
         dev = torch.device("cuda", self.device)
-        res, surf = [], (_lib.Surface * max(n, 1))()
-        for i, o in enumerate(outs):
-            d = o.image.display
-            t = torch.empty((d.out_height, d.out_width, ch), dtype=torch.int16 if wide else torch.uint8, device=dev)
+        res = [torch.empty((o.image.display.out_height, o.image.display.out_width, ch),
+                           dtype=torch.int16 if wide else torch.uint8, device=dev) for o in outs]
+        self._submit("heifgpu_render_batch", outs, alphas, colorspace, wide, stream, (f,), self._surfaces(res))
+        return res
+
+    @staticmethod
+    def _check_images(what, outs, alphas, **more):
+        """ValueError unless every image and alpha image carries its HeifImage and
+        alphas and the sequences of `more` have one entry per image."""
+        if any(o.image is None for o in outs) or (alphas is not None and any(a is not None and a.image is None for a in alphas)):
+            raise ValueError(f"{what} needs images that carry their HeifImage (alloc_outputs)")
+        for name, v in dict(alphas=alphas, **more).items():
+            if v is not None and len(v) != len(outs):
+                raise ValueError(f"{name} must have one entry per image")
+
+    @staticmethod
+    def _surfaces(tensors):
+        """The heifgpu_surface array of (h, w, C) device tensors."""
+        surf = (_lib.Surface * max(len(tensors), 1))()
+        for i, t in enumerate(tensors):
             surf[i].pixels = t.data_ptr()
             surf[i].pitch = t.stride(0) * t.element_size()
-            res.append(t)
+        return surf
+
+    def _submit(self, name, outs, alphas, colorspace, wide, stream, mid, surf):
+        """The one call of a render: lib.<name>, or lib.<name>_color with the images'
+        transforms in front of the surfaces when a colorspace is asked for.  mid: the
+        arguments between the alpha planes and the surfaces."""
         imgs, aimgs, aplanes = self._render_args(outs, alphas)
-        xf, keep = self._transforms(outs, colorspace, wide)
         if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        if xf is None:
-            _lib.check(lib.heifgpu_render_batch(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f, surf,
-                                                ctypes.c_void_p(stream)))
-        else:
-            _lib.check(lib.heifgpu_render_batch_color(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f,
-                                                      xf, surf, ctypes.c_void_p(stream)))
-        return res
+            stream = self._torch.cuda.current_stream(self.device).cuda_stream
+        xf, keep = self._transforms(outs, colorspace, wide)
+        fn, mid = (getattr(lib, name), mid) if xf is None else (getattr(lib, name + "_color"), mid + (xf,))
+        _lib.check(fn(self._h, imgs, len(outs), DecodeContext.planes_of(outs), aimgs, aplanes, *mid, surf,
+                      ctypes.c_void_p(stream)))
+
+    def _scales(self, what, outs, alphas, size, mode, windows):
+        """(box height, box width, the heifgpu_scale of every image) of a scaled render:
+        windows[i], else the fit of `mode`; ValueError if one reads samples that a
+        window decode did not write."""
+        bh, bw = int(size[0]), int(size[1])
+        scales = (_lib.Scale * max(len(outs), 1))()
+        for i, o in enumerate(outs):
+            if windows is not None:
+                x, y, w, h = (int(v) for v in windows[i])
+                scales[i] = _lib.Scale(bw, bh, x, y, w, h)
+            else:
+                d = o.image.display
+                _lib.check(lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_MODES[mode], ctypes.byref(scales[i])))
+        for i, o in enumerate(outs):
+            sc = scales[i]
+            _check_valid(what, i, o, alphas[i] if alphas is not None else None, (sc.x, sc.y, sc.width, sc.height))
+        return bh, bw, scales
+
+    def _scaled_outputs(self, n, scales, box, shape, dtype):
+        """(one batch tensor, its n slices) when every output has the size of `box`
+        (h, w), else (None, a tensor per image of its scale's size); shape(h, w) is
+        the shape of one output."""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        if box is not None:
+            whole = torch.empty((n,) + shape(*box), dtype=dtype, device=dev)
+            return whole, [whole[i] for i in range(n)]
+        return None, [torch.empty(shape(scales[i].out_height, scales[i].out_width), dtype=dtype, device=dev)
+                      for i in range(n)]
 
     @staticmethod
     def _transforms(outs, colorspace, wide):
@@ -507,49 +550,13 @@ class DecodeContext:
         ch, wide = (4 if f & 1 else 3), f >= _lib.PIX_RGB16
         if mode not in _lib.FIT_MODES:
             raise ValueError(f"mode {mode!r}: one of {sorted(_lib.FIT_MODES)}")
-        if any(o.image is None for o in outs) or (alphas is not None and any(a is not None and a.image is None for a in alphas)):
-            raise ValueError("render_scaled needs images that carry their HeifImage (alloc_outputs)")
-        if alphas is not None and len(alphas) != n:
-            raise ValueError("alphas must have one entry per image")
-        if windows is not None and len(windows) != n:
-            raise ValueError("windows must have one entry per image")
-        bh, bw = int(size[0]), int(size[1])
-        scales = (_lib.Scale * max(n, 1))()
-        for i, o in enumerate(outs):
-            if windows is not None:
-                x, y, w, h = (int(v) for v in windows[i])
-                scales[i] = _lib.Scale(bw, bh, x, y, w, h)
-            else:
-                d = o.image.display
-                _lib.check(lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_MODES[mode], ctypes.byref(scales[i])))
-        for i, o in enumerate(outs):
-            sc = scales[i]
-            _check_valid("render_scaled", i, o, alphas[i] if alphas is not None else None,
-                         (sc.x, sc.y, sc.width, sc.height))
-        dev = torch.device("cuda", self.device)
-        dt = torch.int16 if wide else torch.uint8
-        if windows is not None or mode != "contain":
-            whole = torch.empty((n, bh, bw, ch), dtype=dt, device=dev)
-            res = [whole[i] for i in range(n)]
-        else:
-            whole = None
-            res = [torch.empty((scales[i].out_height, scales[i].out_width, ch), dtype=dt, device=dev) for i in range(n)]
-        if n == 0:
-            return whole if whole is not None else res
-        surf = (_lib.Surface * n)()
-        for i, t in enumerate(res):
-            surf[i].pixels = t.data_ptr()
-            surf[i].pitch = t.stride(0) * t.element_size()
-        imgs, aimgs, aplanes = self._render_args(outs, alphas)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        xf, keep = self._transforms(outs, colorspace, wide)
-        if xf is None:
-            _lib.check(lib.heifgpu_render_batch_scaled(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes, f,
-                                                       scales, surf, ctypes.c_void_p(stream)))
-        else:
-            _lib.check(lib.heifgpu_render_batch_scaled_color(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs,
-                                                             aplanes, f, scales, xf, surf, ctypes.c_void_p(stream)))
+        self._check_images("render_scaled", outs, alphas, windows=windows)
+        bh, bw, scales = self._scales("render_scaled", outs, alphas, size, mode, windows)
+        whole, res = self._scaled_outputs(n, scales, (bh, bw) if windows is not None or mode != "contain" else None,
+                                          lambda h, w: (h, w, ch), torch.int16 if wide else torch.uint8)
+        if n:
+            self._submit("heifgpu_render_batch_scaled", outs, alphas, colorspace, wide, stream, (f, scales),
+                         self._surfaces(res))
         return whole if whole is not None else res
 
     def render_tensor(self, outs: Sequence[DecodedImage], size, mode: str = "cover", dtype=None, layout: str = "chw",
@@ -583,11 +590,7 @@ class DecodeContext:
             raise ValueError(f"layout {layout!r}: one of {sorted(_lib.LAYOUTS)}")
         if mode not in _lib.FIT_MODES:
             raise ValueError(f"mode {mode!r}: one of {sorted(_lib.FIT_MODES)}")
-        if any(o.image is None for o in outs) or (alphas is not None and any(a is not None and a.image is None for a in alphas)):
-            raise ValueError("render_tensor needs images that carry their HeifImage (alloc_outputs)")
-        for name, v in (("alphas", alphas), ("windows", windows), ("flips", flips)):
-            if v is not None and len(v) != n:
-                raise ValueError(f"{name} must have one entry per image")
+        self._check_images("render_tensor", outs, alphas, windows=windows, flips=flips)
         if flips is not None and any(int(v) not in (0, 1, 2, 3) for v in flips):
             raise ValueError("flips[i] is 0, 1 (columns), 2 (rows) or 3 (both)")
         tf = _lib.TensorFormat(src=f, elem=elems[dtype], layout=_lib.LAYOUTS[layout])
@@ -606,32 +609,10 @@ class DecodeContext:
             a, b = [1.0 / (maxv * s) for s in std], [-m / s for m, s in zip(mean, std)]  # in double, rounded once below
         for c in range(ch):
             tf.a[c], tf.b[c] = a[c], b[c]
-        bh, bw = int(size[0]), int(size[1])
-        scales = (_lib.Scale * max(n, 1))()
-        for i, o in enumerate(outs):
-            if windows is not None:
-                x, y, w, h = (int(v) for v in windows[i])
-                scales[i] = _lib.Scale(bw, bh, x, y, w, h)
-            else:
-                d = o.image.display
-                _lib.check(lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_MODES[mode], ctypes.byref(scales[i])))
-        for i, o in enumerate(outs):
-            sc = scales[i]
-            _check_valid("render_tensor", i, o, alphas[i] if alphas is not None else None,
-                         (sc.x, sc.y, sc.width, sc.height))
-        dev = torch.device("cuda", self.device)
+        bh, bw, scales = self._scales("render_tensor", outs, alphas, size, mode, windows)
         chw = layout == "chw"
-
-        def shape(h, w):
-            return (ch, h, w) if chw else (h, w, ch)
-
-        if windows is not None or mode != "contain":
-            whole = torch.empty((n,) + shape(bh, bw), dtype=dtype, device=dev)
-            res = [whole[i] for i in range(n)]
-        else:
-            whole = None
-            res = [torch.empty(shape(scales[i].out_height, scales[i].out_width), dtype=dtype, device=dev)
-                   for i in range(n)]
+        whole, res = self._scaled_outputs(n, scales, (bh, bw) if windows is not None or mode != "contain" else None,
+                                          lambda h, w: (ch, h, w) if chw else (h, w, ch), dtype)
         if n == 0:
             return whole if whole is not None else res
         surf = (_lib.TensorSurface * n)()
@@ -640,17 +621,8 @@ class DecodeContext:
             surf[i].stride_c = t.stride(0) * t.element_size() if chw else 0
             surf[i].stride_y = t.stride(1 if chw else 0) * t.element_size()
         fl = None if flips is None else (ctypes.c_uint32 * n)(*[int(v) for v in flips])
-        imgs, aimgs, aplanes = self._render_args(outs, alphas)
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        xf, keep = self._transforms(outs, colorspace, wide)
-        if xf is None:
-            _lib.check(lib.heifgpu_render_batch_tensor(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs, aplanes,
-                                                       ctypes.byref(tf), scales, fl, surf, ctypes.c_void_p(stream)))
-        else:
-            _lib.check(lib.heifgpu_render_batch_tensor_color(self._h, imgs, n, DecodeContext.planes_of(outs), aimgs,
-                                                             aplanes, ctypes.byref(tf), scales, fl, xf, surf,
-                                                             ctypes.c_void_p(stream)))
+        self._submit("heifgpu_render_batch_tensor", outs, alphas, colorspace, wide, stream,
+                     (ctypes.byref(tf), scales, fl), surf)
         return whole if whole is not None else res
 
 

@@ -1,0 +1,438 @@
+// render.cpp — the render family of the C ABI: heifgpu_render_batch, _scaled and _tensor
+// with their _color forms, and heifgpu_scale_fit.  Each call checks its arguments and
+// fills its descriptors; render_submit sends any of the three descriptor types.
+// (The calls take their C linkage from the declarations of include/heifgpu.h.)
+#include <cmath>
+#include <memory>
+#include <vector>
+
+#include "../common/desc.hpp"
+#include "../kernels/color_xform.hpp"
+#include "api.hpp"
+
+using namespace hg;
+
+// The descriptors of a render call travel through a ring of slots,
+// each a pinned host image, a device array and an event recorded behind the kernel
+// that reads them: a call never rewrites descriptors that an earlier call's
+// copy or kernel may still read (the host waits only when the ring wraps).
+constexpr int kRenderSlots = 4;
+struct RenderRing {
+    struct Slot {
+        PinnedBuf host;
+        DevBuf<uint8_t> dev;  // n descriptors of the call's type, then its ColorRefs
+        hipEvent_t done = nullptr;
+        bool pending = false;
+    } slot[kRenderSlots];
+    int next = 0;
+    ~RenderRing() {
+        for (Slot &s : slot)
+            if (s.done) (void)hipEventDestroy(s.done);
+    }
+};
+
+// The tables of the transforms on the device, keyed by content: in_lut[3][1 << B] then
+// out_lut as 4096 pairs (xf_out_pair), as ColorRef::lut addresses them.  An entry is written once, by a blocking
+// copy before the call that first uses it launches anything, and never again, so no
+// launch in flight can see a table change; a steady-state call finds its tables here.
+// When kColorCacheMax tables are held the cache is emptied after a device synchronise.
+constexpr size_t kColorCacheMax = 256;
+struct ColorCache {
+    struct Entry {
+        std::vector<uint16_t> key;
+        uint16_t *dev = nullptr;
+    };
+    std::vector<Entry> entries;
+    void clear() {
+        for (Entry &e : entries)
+            if (e.dev) (void)hipFree(e.dev);
+        entries.clear();
+    }
+    ~ColorCache() { clear(); }
+};
+
+void hg::render_state_free(heifgpu_ctx *ctx) {
+    delete ctx->render;
+    delete ctx->color;
+}
+
+// refs[i] for the images of a render call (empty when no image is to be transformed:
+// the call is then the unmanaged call).  Every check runs before anything is launched.
+static int color_refs_fill(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, uint32_t format,
+                           const heifgpu_color_transform *const *xf, std::vector<ColorRef> &refs) {
+    refs.clear();
+    if (!xf) return HEIFGPU_OK;
+    bool any = false;
+    for (size_t i = 0; i < n; ++i) {
+        const heifgpu_color_transform *t = xf[i];
+        if (!t) continue;
+        heifgpu_image_info info;
+        heifgpu_image_get_info(imgs[i], &info);
+        const uint32_t depth = format >= HEIFGPU_PIX_RGB16 ? info.bit_depth : 8;
+        if (t->bits != depth || t->bits < 8 || t->bits > 12)
+            return fail(HEIFGPU_E_INVALID, "transform made for another depth than the image is rendered at");
+        any = any || !t->identity;
+    }
+    if (!any) return HEIFGPU_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->color) ctx->color = new ColorCache;
+    ColorCache &cache = *ctx->color;
+    if (cache.entries.size() >= kColorCacheMax) {  // (checked once per call: a call may go past it by its own tables)
+        HIP_TRY(hipDeviceSynchronize());  // nothing in flight reads a table that is freed
+        cache.clear();
+    }
+    refs.assign(n, ColorRef{});
+    std::vector<uint16_t> key;
+    for (size_t i = 0; i < n; ++i) {
+        const heifgpu_color_transform *t = xf[i];
+        if (!t || t->identity) continue;  // lut == 0: untouched
+        const size_t tn = size_t(1) << t->bits;
+        key.resize(3 * tn + 2 * kXfPairEntries);
+        for (int c = 0; c < 3; ++c) std::memcpy(key.data() + c * tn, t->in_lut[c], tn * 2);
+        for (int k = 0; k < kXfPairEntries; ++k) {
+            const uint32_t w = xf_out_pair(t->out_lut, k);
+            std::memcpy(key.data() + 3 * tn + 2 * k, &w, 4);
+        }
+        ColorCache::Entry *hit = nullptr;
+        for (ColorCache::Entry &e : cache.entries)
+            if (e.key == key) hit = &e;
+        if (!hit) {
+            ColorCache::Entry e;
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e.dev), key.size() * 2));
+            const hipError_t up = hipMemcpy(e.dev, key.data(), key.size() * 2, hipMemcpyHostToDevice);  // blocking
+            if (up != hipSuccess) {
+                (void)hipFree(e.dev);
+                return fail(HEIFGPU_E_DEVICE, std::string("colour table upload: ") + hipGetErrorString(up));
+            }
+            e.key = key;
+            cache.entries.push_back(std::move(e));
+            hit = &cache.entries.back();
+        }
+        refs[i].lut = reinterpret_cast<uint64_t>(hit->dev);
+        refs[i].n = int32_t(tn);
+        for (int k = 0; k < 9; ++k) refs[i].m[k] = t->m[k];
+    }
+    return HEIFGPU_OK;
+}
+
+// What heifgpu_render_batch and heifgpu_render_batch_scaled check and fill alike for
+// image i: dm is the map the kernel reads through (for the scaled call the window is
+// folded in; dm.out_width x out_height is then the window), ow x oh the size written.
+// out == nullptr (heifgpu_render_batch_tensor): the caller checks and fills its own output.
+static int render_desc_fill(size_t i, const heifgpu_image *const *imgs, const heifgpu_planes *in,
+                            const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                            const heifgpu_surface *out, const DisplayMap &dm, uint32_t ow, uint32_t oh, int &bps,
+                            RenderDesc &d) {
+    const bool wide = format >= HEIFGPU_PIX_RGB16, with_alpha = (format & 1) != 0;
+    const int bpp = (with_alpha ? 4 : 3) * (wide ? 2 : 1);
+    heifgpu_image_info info;
+    heifgpu_image_get_info(imgs[i], &info);
+    if (!in[i].plane[0] || (out && !out[i].pixels)) return fail(HEIFGPU_E_INVALID, "missing plane or surface");
+    if (info.chroma_format_idc && (!in[i].plane[1] || !in[i].plane[2]))
+        return fail(HEIFGPU_E_INVALID, "missing chroma plane");
+    if (info.bit_depth < 8 || info.bit_depth > (wide ? 12u : 16u)) return fail(HEIFGPU_E_INVALID, "bit depth");
+    if (bps && bps != int(info.bytes_per_sample))
+        return fail(HEIFGPU_E_UNSUPPORTED, "images of 1-byte and 2-byte samples in one render call");
+    bps = int(info.bytes_per_sample);
+    if (out && int64_t(out[i].pitch) < int64_t(bpp) * ow)
+        return fail(HEIFGPU_E_INVALID, "surface pitch smaller than the output row");
+    if (out && wide && ((reinterpret_cast<uintptr_t>(out[i].pixels) | uint32_t(out[i].pitch)) & 1))
+        return fail(HEIFGPU_E_INVALID, "16-bit surface not 2-byte aligned");
+    // the map's corners inside the decoded planes (parse_heic built it so; the kernel reads unchecked)
+    for (int c = 0; c < 4; ++c) {
+        const int64_t ox = (c & 1) ? int64_t(dm.out_width) - 1 : 0, oy = (c & 2) ? int64_t(dm.out_height) - 1 : 0;
+        const int64_t x = dm.m[0] * ox + dm.m[1] * oy + dm.t[0], y = dm.m[2] * ox + dm.m[3] * oy + dm.t[1];
+        if (x < 0 || y < 0 || x >= int64_t(info.width) || y >= int64_t(info.height))
+            return fail(HEIFGPU_E_INVALID, "display map outside the decoded image");
+    }
+    d = RenderDesc{};
+    for (int k = 0; k < 3; ++k) {
+        d.plane[k] = reinterpret_cast<uint64_t>(in[i].plane[k]);
+        d.pitch[k] = in[i].pitch[k];
+    }
+    if (out) {
+        d.out = reinterpret_cast<uint64_t>(out[i].pixels);
+        d.out_pitch = out[i].pitch;
+    }
+    d.out_w = int32_t(ow);
+    d.out_h = int32_t(oh);
+    for (int k = 0; k < 4; ++k) d.m[k] = dm.m[k];
+    d.t[0] = dm.t[0];
+    d.t[1] = dm.t[1];
+    d.swap = dm.m[0] == 0;
+    d.chroma = int32_t(info.chroma_format_idc);
+    const int depth = wide ? int(info.bit_depth) : 8;  // the depth the arithmetic runs at
+    d.shift = int32_t(info.bit_depth) - depth;
+    render_coefs(info.matrix_coeffs, info.full_range != 0, depth, d);
+    if (with_alpha && alpha_imgs && alpha_imgs[i]) {
+        if (!alpha_in || !alpha_in[i].plane[0]) return fail(HEIFGPU_E_INVALID, "missing alpha plane");
+        heifgpu_image_info ai;
+        heifgpu_image_get_info(alpha_imgs[i], &ai);
+        if (ai.width != info.width || ai.height != info.height)
+            return fail(HEIFGPU_E_UNSUPPORTED, "alpha image of another size than its colour image");
+        if (int(ai.bytes_per_sample) != bps)
+            return fail(HEIFGPU_E_UNSUPPORTED, "images of 1-byte and 2-byte samples in one render call");
+        d.alpha = reinterpret_cast<uint64_t>(alpha_in[i].plane[0]);
+        d.alpha_pitch = alpha_in[i].pitch[0];
+        d.alpha_bps = int32_t(ai.bytes_per_sample);
+        d.alpha_shift = int32_t(ai.bit_depth) - depth;  // right when positive, left when negative
+    }
+    return HEIFGPU_OK;
+}
+
+// The next slot of the context's descriptor ring, drained of the call that used it last.
+static int render_ring_slot(heifgpu_ctx *ctx, RenderRing::Slot **out) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->render) {
+        auto ring = std::make_unique<RenderRing>();
+        for (RenderRing::Slot &sl : ring->slot) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+        ctx->render = ring.release();
+    }
+    RenderRing::Slot &sl = ctx->render->slot[ctx->render->next];
+    ctx->render->next = (ctx->render->next + 1) % kRenderSlots;
+    if (sl.pending) HIP_TRY(hipEventSynchronize(sl.done));  // the call that used this slot last
+    sl.pending = false;
+    *out = &sl;
+    return HEIFGPU_OK;
+}
+
+// What every render call ends in, for Desc = RenderDesc, ScaleDesc or TensorDesc: the
+// colour refs, a ring slot, the descriptors then the refs in one staging image, one
+// copy, the one launch and the slot's event.
+template <class Desc>
+static int render_submit(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, const std::vector<Desc> &descs,
+                         int max_tiles, uint32_t format, int bps, const heifgpu_color_transform *const *xf,
+                         void *stream) {
+    static_assert(sizeof(Desc) % 8 == 0, "the ColorRefs behind the descriptors are 8-byte aligned");
+    const size_t n = descs.size();
+    std::vector<ColorRef> refs;
+    if (int rc = color_refs_fill(ctx, imgs, n, format, xf, refs)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RenderRing::Slot *slot = nullptr;
+    if (int rc = render_ring_slot(ctx, &slot)) return rc;
+    RenderRing::Slot &sl = *slot;
+    const size_t dbytes = n * sizeof(Desc), bytes = dbytes + refs.size() * sizeof(ColorRef);
+    HIP_TRY(sl.host.reserve(bytes));
+    HIP_TRY(sl.dev.alloc(bytes));
+    std::memcpy(sl.host.p, descs.data(), dbytes);
+    if (!refs.empty()) std::memcpy(sl.host.p + dbytes, refs.data(), bytes - dbytes);  // behind the descriptors: one copy
+    HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_render(reinterpret_cast<const Desc *>(sl.dev.p), int(n), max_tiles, int(format), bps, !refs.empty(),
+                          s));  // the one launch
+    HIP_TRY(hipEventRecord(sl.done, s));
+    sl.pending = true;
+    return HEIFGPU_OK;
+}
+
+static int render_batch_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                             const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                             const heifgpu_color_transform *const *xf, const heifgpu_surface *out, void *stream) {
+    if (!ctx || !imgs || !in || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    std::vector<RenderDesc> descs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
+        const DisplayMap &dm = imgs[i]->img.display;
+        RenderDesc &d = descs[i];
+        if (int rc = render_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, out, dm, dm.out_width, dm.out_height,
+                                      bps, d))
+            return rc;
+        const int tw = d.swap ? kRenderTile : kRenderRowW, th = d.swap ? kRenderTile : kRenderRowH;
+        d.tiles_x = (d.out_w + tw - 1) / tw;
+        d.tiles = d.tiles_x * ((d.out_h + th - 1) / th);
+        max_tiles = std::max(max_tiles, d.tiles);
+    }
+    return render_submit(ctx, imgs, descs, max_tiles, format, bps, xf, stream);
+}
+
+int heifgpu_render_batch(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                         const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                         const heifgpu_surface *out, void *stream) {
+    return render_batch_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, nullptr, out, stream);
+}
+
+int heifgpu_render_batch_color(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                               const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                               const heifgpu_color_transform *const *xf, const heifgpu_surface *out, void *stream) {
+    return render_batch_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, xf, out, stream);
+}
+
+// round_half_up(n / d) = floor((2n + d) / 2d); n, d < 2^32
+static uint64_t round_div(uint64_t n, uint64_t d) { return (2 * n + d) / (2 * d); }
+
+int heifgpu_scale_fit(const heifgpu_display_info *d, uint32_t box_w, uint32_t box_h, uint32_t mode, heifgpu_scale *out) {
+    if (!d || !out) return fail(HEIFGPU_E_INVALID, "null argument");
+    if (!box_w || !box_h) return fail(HEIFGPU_E_INVALID, "empty box");
+    if (mode > HEIFGPU_FIT_COVER) return fail(HEIFGPU_E_INVALID, "fit mode");
+    if (!d->out_width || !d->out_height) return fail(HEIFGPU_E_INVALID, "empty picture");
+    const uint64_t dw = d->out_width, dh = d->out_height, bw = box_w, bh = box_h;
+    heifgpu_scale s{};
+    s.out_width = box_w;
+    s.out_height = box_h;  // STRETCH; x = y = width = height = 0: the whole picture
+    const bool wider = dw * bh >= dh * bw;  // the picture is at least as wide as the box, relatively
+    if (mode == HEIFGPU_FIT_CONTAIN) {
+        if (wider) s.out_height = uint32_t(std::max<uint64_t>(1, round_div(dh * bw, dw)));
+        else s.out_width = uint32_t(std::max<uint64_t>(1, round_div(dw * bh, dh)));
+    } else if (mode == HEIFGPU_FIT_COVER) {
+        s.width = d->out_width;
+        s.height = d->out_height;
+        if (wider) {
+            s.width = uint32_t(std::max<uint64_t>(1, round_div(dh * bw, bh)));
+            s.x = (d->out_width - s.width) / 2;
+        } else {
+            s.height = uint32_t(std::max<uint64_t>(1, round_div(dw * bh, bw)));
+            s.y = (d->out_height - s.height) / 2;
+        }
+    }
+    *out = s;
+    return HEIFGPU_OK;
+}
+
+// What heifgpu_render_batch_scaled and heifgpu_render_batch_tensor check and fill alike
+// for image i: the window, then `flip` (bit 0: columns, bit 1: rows of the rendered
+// picture, which is the mirrored window rendered: the weights are symmetric) as further
+// steps of the display map, render_desc_fill through that map, and the tile geometry.
+static int scale_desc_fill(size_t i, const heifgpu_image *const *imgs, const heifgpu_planes *in,
+                           const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                           const heifgpu_scale &sc, uint32_t flip, const heifgpu_surface *out, int &bps, ScaleDesc &sd) {
+    if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
+    DisplayMap dm = imgs[i]->img.display;
+    if (!sc.out_width || !sc.out_height || sc.out_width > 65535 || sc.out_height > 65535)
+        return fail(HEIFGPU_E_INVALID, "rendered size outside 1..65535");
+    if (sc.width || sc.height) {
+        if (!sc.width || !sc.height || sc.x >= dm.out_width || sc.y >= dm.out_height ||
+            sc.width > dm.out_width - sc.x || sc.height > dm.out_height - sc.y)
+            return fail(HEIFGPU_E_INVALID, "window empty or outside the displayed picture");
+        display_window(dm, sc.x, sc.y, sc.width, sc.height);
+    }
+    if (flip & 1) display_imir(dm, 0);
+    if (flip & 2) display_imir(dm, 1);
+    if (dm.out_width > 65535 || dm.out_height > 65535)
+        return fail(HEIFGPU_E_UNSUPPORTED, "window side above 65535");  // (the 32-bit line sums of the kernel)
+    sd = ScaleDesc{};
+    RenderDesc &d = sd.r;
+    if (int rc = render_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, out, dm, sc.out_width, sc.out_height, bps,
+                                  d))
+        return rc;
+    // the source's axes: a runs along its y, b along its x (kernels.hpp)
+    const int32_t cw = int32_t(dm.out_width), ch = int32_t(dm.out_height);
+    if (d.swap) {
+        sd.ca = cw, sd.oa = d.out_w, sd.ma = d.m[2], sd.ta = d.t[1];
+        sd.cb = ch, sd.ob = d.out_h, sd.mb = d.m[1], sd.tb = d.t[0];
+        // 64 pixels along the output's x (store_row); along its y as many as keep the footprint
+        // within a chunk of kScaleCols source columns, 16 at the least
+        sd.na = kScaleTile, sd.nb = kScaleTile;
+        while (sd.nb > 16 && int64_t(sd.nb) * sd.cb > int64_t(kScaleCols) * sd.ob) sd.nb /= 2;
+    } else {
+        sd.ca = ch, sd.oa = d.out_h, sd.ma = d.m[3], sd.ta = d.t[1];
+        sd.cb = cw, sd.ob = d.out_w, sd.mb = d.m[0], sd.tb = d.t[0];
+        // as many columns as fill a chunk of kScaleCols source columns, 64 at ratios from 4 up
+        sd.na = kScaleRowsA;
+        sd.nb = 64;
+        while (sd.nb < 256 && int64_t(2 * sd.nb) * sd.cb <= int64_t(kScaleCols) * sd.ob) sd.nb *= 2;
+    }
+    for (sd.nb_log2 = 4; (1 << sd.nb_log2) < sd.nb;) ++sd.nb_log2;
+    sd.den = 2 * uint64_t(cw) * uint64_t(ch);
+    sd.inv_den = 1.0 / double(sd.den);
+    d.tiles_x = (sd.ob + sd.nb - 1) / sd.nb;
+    d.tiles = d.tiles_x * ((sd.oa + sd.na - 1) / sd.na);
+    return HEIFGPU_OK;
+}
+
+static int render_scaled_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                              const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                              const heifgpu_scale *scale, const heifgpu_color_transform *const *xf,
+                              const heifgpu_surface *out, void *stream) {
+    // (the context is looked at last: every check of the arguments answers without one)
+    if (!imgs || !in || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    std::vector<ScaleDesc> descs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (int rc = scale_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, scale[i], 0, out, bps, descs[i]))
+            return rc;
+        max_tiles = std::max(max_tiles, descs[i].r.tiles);
+    }
+    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
+    return render_submit(ctx, imgs, descs, max_tiles, format, bps, xf, stream);
+}
+
+int heifgpu_render_batch_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                                const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                                const heifgpu_scale *scale, const heifgpu_surface *out, void *stream) {
+    return render_scaled_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, scale, nullptr, out, stream);
+}
+
+int heifgpu_render_batch_scaled_color(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                      const heifgpu_planes *in, const heifgpu_image *const *alpha_imgs,
+                                      const heifgpu_planes *alpha_in, uint32_t format, const heifgpu_scale *scale,
+                                      const heifgpu_color_transform *const *xf, const heifgpu_surface *out,
+                                      void *stream) {
+    return render_scaled_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, scale, xf, out, stream);
+}
+
+static int render_tensor_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                              const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in,
+                              const heifgpu_tensor_format *fmt, const heifgpu_scale *scale, const uint32_t *flip,
+                              const heifgpu_color_transform *const *xf, const heifgpu_tensor_surface *out,
+                              void *stream) {
+    // (the context is looked at last, as in heifgpu_render_batch_scaled)
+    if (!imgs || !in || !fmt || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (fmt->src > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "source format");
+    if (fmt->elem > HEIFGPU_ELEM_BF16) return fail(HEIFGPU_E_INVALID, "element type");
+    if (fmt->layout > HEIFGPU_LAYOUT_HWC) return fail(HEIFGPU_E_INVALID, "layout");
+    const int nch = (fmt->src & 1) ? 4 : 3;
+    for (int c = 0; c < nch; ++c)
+        if (!std::isfinite(fmt->a[c]) || !std::isfinite(fmt->b[c]))
+            return fail(HEIFGPU_E_INVALID, "scale or bias not finite");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    const int64_t esz = fmt->elem == HEIFGPU_ELEM_F32 ? 4 : 2;
+    std::vector<TensorDesc> descs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t fl = flip ? flip[i] : 0;
+        if (fl > 3) return fail(HEIFGPU_E_INVALID, "flip above 3");
+        TensorDesc &td = descs[i];
+        if (int rc = scale_desc_fill(i, imgs, in, alpha_imgs, alpha_in, fmt->src, scale[i], fl, nullptr, bps, td.s))
+            return rc;
+        const heifgpu_tensor_surface &o = out[i];
+        if (!o.data || (reinterpret_cast<uintptr_t>(o.data) & uintptr_t(esz - 1)))
+            return fail(HEIFGPU_E_INVALID, "tensor data null or not aligned to its element");
+        const int64_t row = int64_t(td.s.r.out_w) * esz * (fmt->layout == HEIFGPU_LAYOUT_HWC ? nch : 1);
+        if (o.stride_y < row || (o.stride_y & (esz - 1)))
+            return fail(HEIFGPU_E_INVALID, "stride_y below the row or not a multiple of the element size");
+        if (fmt->layout == HEIFGPU_LAYOUT_CHW && (o.stride_c & (esz - 1)))
+            return fail(HEIFGPU_E_INVALID, "stride_c not a multiple of the element size");
+        td.s.r.out = reinterpret_cast<uint64_t>(o.data);
+        td.stride_c = fmt->layout == HEIFGPU_LAYOUT_CHW ? o.stride_c : 0;
+        td.stride_y = o.stride_y;
+        td.elem = int32_t(fmt->elem);
+        td.layout = int32_t(fmt->layout);
+        for (int c = 0; c < 4; ++c) {
+            td.a[c] = c < nch ? fmt->a[c] : 0.f;
+            td.b[c] = c < nch ? fmt->b[c] : 0.f;
+        }
+        max_tiles = std::max(max_tiles, td.s.r.tiles);
+    }
+    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
+    return render_submit(ctx, imgs, descs, max_tiles, fmt->src, bps, xf, stream);
+}
+
+int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                                const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in,
+                                const heifgpu_tensor_format *fmt, const heifgpu_scale *scale, const uint32_t *flip,
+                                const heifgpu_tensor_surface *out, void *stream) {
+    return render_tensor_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, fmt, scale, flip, nullptr, out, stream);
+}
+
+int heifgpu_render_batch_tensor_color(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                      const heifgpu_planes *in, const heifgpu_image *const *alpha_imgs,
+                                      const heifgpu_planes *alpha_in, const heifgpu_tensor_format *fmt,
+                                      const heifgpu_scale *scale, const uint32_t *flip,
+                                      const heifgpu_color_transform *const *xf, const heifgpu_tensor_surface *out,
+                                      void *stream) {
+    return render_tensor_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, fmt, scale, flip, xf, out, stream);
+}

@@ -1,6 +1,6 @@
 // color_xform.hpp — the colour-managed render's per-pixel arithmetic, the one
 // statement of it in code: k_render / k_render_scaled (render.hip) and
-// heifgpu_color_apply (api.cpp) both call color_xform_px, so the CPU suite runs
+// heifgpu_color_apply (api/image.cpp) both call color_xform_px, so the CPU suite runs
 // the very function the GPU runs.  include/heifgpu.h states the contract
 // (heifgpu_color_transform); tests/color_ref.py restates it in numpy.
 //

@@ -297,20 +297,12 @@ void emu_sao_out(const BatchArgs &a);
 hipError_t launch_rbsp(const BatchArgs &a, hipStream_t s);
 hipError_t launch_ycbcr_rgb(const ColorArgs &c, int bytes_per_sample, hipStream_t s);
 hipError_t launch_gather_tiles(const GatherArgs &g, hipStream_t s);
-// one launch over (max_tiles, n_images); descs on the device
-hipError_t launch_render(const RenderDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+// one launch over (max_tiles, n_images); descs on the device.  color: the colour-managed
+// kernels, with a ColorRef per image behind the n_images descriptors (lut == 0: image i untouched)
+// Desc: RenderDesc, ScaleDesc or TensorDesc (instantiated in render.hip)
+template <typename Desc>
+hipError_t launch_render(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, bool color,
                          hipStream_t s);
-hipError_t launch_render_scaled(const ScaleDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
-                                hipStream_t s);
-hipError_t launch_render_tensor(const TensorDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
-                                hipStream_t s);
-// the same three with a ColorRef per image behind the n_images descriptors (lut == 0: image i untouched)
-hipError_t launch_render_color(const RenderDesc *descs, int n_images, int max_tiles, int format,
-                               int bytes_per_sample, hipStream_t s);
-hipError_t launch_render_scaled_color(const ScaleDesc *descs, int n_images, int max_tiles,
-                                      int format, int bytes_per_sample, hipStream_t s);
-hipError_t launch_render_tensor_color(const TensorDesc *descs, int n_images, int max_tiles,
-                                      int format, int bytes_per_sample, hipStream_t s);
 hipError_t launch_parse(const BatchArgs &a, hipStream_t s);
 // (launch_parse's: the kernels of parse_solo.hip and parse_lean.hip)
 hipError_t launch_parse_solo(const BatchArgs &a, hipStream_t s);

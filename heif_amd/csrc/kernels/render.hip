@@ -257,23 +257,14 @@ __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
     }
 }
 
-template <typename Pel>
-void launch_fmt_xf(const RenderDesc *descs, dim3 grid, int format, hipStream_t s) {
-    switch (format) {
-    case RENDER_RGB8: hipLaunchKernelGGL((k_render<Pel, RENDER_RGB8 | kRenderXf>), grid, dim3(256), 0, s, descs); break;
-    case RENDER_RGBA8: hipLaunchKernelGGL((k_render<Pel, RENDER_RGBA8 | kRenderXf>), grid, dim3(256), 0, s, descs); break;
-    case RENDER_RGB16: hipLaunchKernelGGL((k_render<Pel, RENDER_RGB16 | kRenderXf>), grid, dim3(256), 0, s, descs); break;
-    default: hipLaunchKernelGGL((k_render<Pel, RENDER_RGBA16 | kRenderXf>), grid, dim3(256), 0, s, descs); break;
-    }
-}
-
-template <typename Pel>
+// XF: kRenderXf for the colour-managed instantiations, else 0
+template <typename Pel, int XF>
 void launch_fmt(const RenderDesc *descs, dim3 grid, int format, hipStream_t s) {
     switch (format) {
-    case RENDER_RGB8: hipLaunchKernelGGL((k_render<Pel, RENDER_RGB8>), grid, dim3(256), 0, s, descs); break;
-    case RENDER_RGBA8: hipLaunchKernelGGL((k_render<Pel, RENDER_RGBA8>), grid, dim3(256), 0, s, descs); break;
-    case RENDER_RGB16: hipLaunchKernelGGL((k_render<Pel, RENDER_RGB16>), grid, dim3(256), 0, s, descs); break;
-    default: hipLaunchKernelGGL((k_render<Pel, RENDER_RGBA16>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGB8: hipLaunchKernelGGL((k_render<Pel, RENDER_RGB8 | XF>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGBA8: hipLaunchKernelGGL((k_render<Pel, RENDER_RGBA8 | XF>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGB16: hipLaunchKernelGGL((k_render<Pel, RENDER_RGB16 | XF>), grid, dim3(256), 0, s, descs); break;
+    default: hipLaunchKernelGGL((k_render<Pel, RENDER_RGBA16 | XF>), grid, dim3(256), 0, s, descs); break;
     }
 }
 
@@ -658,79 +649,52 @@ __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
     }
 }
 
-template <typename Pel, typename Desc>
-void launch_scaled_fmt_xf(const Desc *descs, dim3 grid, int format, hipStream_t s) {
+// Desc = ScaleDesc: the integer surfaces; TensorDesc: the tensor epilogue (element type
+// and layout are uniform branches in store_tensor, so the heavy body is compiled once
+// per sample width and source format for each of the two).  The overload for the two
+// descriptors of k_render_scaled; a RenderDesc takes the one above.
+template <typename Pel, int XF, typename Desc>
+void launch_fmt(const Desc *descs, dim3 grid, int format, hipStream_t s) {
     switch (format) {
-    case RENDER_RGB8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB8 | kRenderXf, Desc>), grid, dim3(256), 0, s, descs); break;
-    case RENDER_RGBA8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA8 | kRenderXf, Desc>), grid, dim3(256), 0, s, descs); break;
-    case RENDER_RGB16: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB16 | kRenderXf, Desc>), grid, dim3(256), 0, s, descs); break;
-    default: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA16 | kRenderXf, Desc>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGB8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB8 | XF, Desc>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGBA8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA8 | XF, Desc>), grid, dim3(256), 0, s, descs); break;
+    case RENDER_RGB16: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB16 | XF, Desc>), grid, dim3(256), 0, s, descs); break;
+    default: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA16 | XF, Desc>), grid, dim3(256), 0, s, descs); break;
     }
 }
 
-// Desc = ScaleDesc: the integer surfaces; TensorDesc: the tensor epilogue (element type
-// and layout are uniform branches in store_tensor, so the heavy body is compiled once
-// per sample width and source format for each of the two)
-template <typename Pel, typename Desc>
-void launch_scaled_fmt(const Desc *descs, dim3 grid, int format, hipStream_t s) {
-    switch (format) {
-    case RENDER_RGB8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB8, Desc>), grid, dim3(256), 0, s, descs); break;
-    case RENDER_RGBA8: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA8, Desc>), grid, dim3(256), 0, s, descs); break;
-    case RENDER_RGB16: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGB16, Desc>), grid, dim3(256), 0, s, descs); break;
-    default: hipLaunchKernelGGL((k_render_scaled<Pel, RENDER_RGBA16, Desc>), grid, dim3(256), 0, s, descs); break;
-    }
-}
+// The kernels lie in the code object in the order of these instantiations: the order the
+// six launchers before this one gave them, so that a build still compares byte for
+// byte with the earlier ones (tools/kernel_text_diff.py).
+#define HG_LAUNCH_FMT(XF, Desc)                                                   \
+    template void launch_fmt<uint8_t, XF>(const Desc *, dim3, int, hipStream_t); \
+    template void launch_fmt<uint16_t, XF>(const Desc *, dim3, int, hipStream_t)
+HG_LAUNCH_FMT(0, ScaleDesc);
+HG_LAUNCH_FMT(0, TensorDesc);
+HG_LAUNCH_FMT(kRenderXf, RenderDesc);
+HG_LAUNCH_FMT(kRenderXf, ScaleDesc);
+HG_LAUNCH_FMT(kRenderXf, TensorDesc);
+HG_LAUNCH_FMT(0, RenderDesc);
+#undef HG_LAUNCH_FMT
 
 }  // namespace
 
-hipError_t launch_render_scaled(const ScaleDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
-                                hipStream_t s) {
-    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
-    if (bytes_per_sample == 1) launch_scaled_fmt<uint8_t>(descs, grid, format, s);
-    else launch_scaled_fmt<uint16_t>(descs, grid, format, s);
-    return hipGetLastError();
-}
-
-hipError_t launch_render_tensor(const TensorDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
-                                hipStream_t s) {
-    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
-    if (bytes_per_sample == 1) launch_scaled_fmt<uint8_t>(descs, grid, format, s);
-    else launch_scaled_fmt<uint16_t>(descs, grid, format, s);
-    return hipGetLastError();
-}
-
-// (the ColorRefs lie behind the n_images descriptors, where the kernels look for them)
-hipError_t launch_render_color(const RenderDesc *descs, int n_images, int max_tiles, int format,
-                               int bytes_per_sample, hipStream_t s) {
-    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
-    if (bytes_per_sample == 1) launch_fmt_xf<uint8_t>(descs, grid, format, s);
-    else launch_fmt_xf<uint16_t>(descs, grid, format, s);
-    return hipGetLastError();
-}
-
-hipError_t launch_render_scaled_color(const ScaleDesc *descs, int n_images, int max_tiles,
-                                      int format, int bytes_per_sample, hipStream_t s) {
-    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
-    if (bytes_per_sample == 1) launch_scaled_fmt_xf<uint8_t>(descs, grid, format, s);
-    else launch_scaled_fmt_xf<uint16_t>(descs, grid, format, s);
-    return hipGetLastError();
-}
-
-hipError_t launch_render_tensor_color(const TensorDesc *descs, int n_images, int max_tiles,
-                                      int format, int bytes_per_sample, hipStream_t s) {
-    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
-    if (bytes_per_sample == 1) launch_scaled_fmt_xf<uint8_t>(descs, grid, format, s);
-    else launch_scaled_fmt_xf<uint16_t>(descs, grid, format, s);
-    return hipGetLastError();
-}
-
-hipError_t launch_render(const RenderDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+template <typename Desc>
+hipError_t launch_render(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, bool color,
                          hipStream_t s) {
     const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
-    if (bytes_per_sample == 1) launch_fmt<uint8_t>(descs, grid, format, s);
-    else launch_fmt<uint16_t>(descs, grid, format, s);
+    if (bytes_per_sample == 1) {
+        if (color) launch_fmt<uint8_t, kRenderXf>(descs, grid, format, s);
+        else launch_fmt<uint8_t, 0>(descs, grid, format, s);
+    } else {
+        if (color) launch_fmt<uint16_t, kRenderXf>(descs, grid, format, s);
+        else launch_fmt<uint16_t, 0>(descs, grid, format, s);
+    }
     return hipGetLastError();
 }
+template hipError_t launch_render(const RenderDesc *, int, int, int, int, bool, hipStream_t);
+template hipError_t launch_render(const ScaleDesc *, int, int, int, int, bool, hipStream_t);
+template hipError_t launch_render(const TensorDesc *, int, int, int, int, bool, hipStream_t);
 #endif
 
 }  // namespace hg

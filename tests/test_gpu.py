@@ -548,6 +548,41 @@ def test_reloaded_batches_alternate(H, ctx, oracle_tiles, halfmoonbay):
         b.free()
 
 
+def test_batch_reloaded_across_parse_modes(H, ctx, oracle_mod):
+    """One batch reloaded five times in place (reuse=, wait=False), each load decoded once
+    with nothing waited for in between, the parse mode changing with every load: the
+    spread-only and lanes-only arenas appear, and grow, on a batch that has decodes in
+    flight.  Each later load is at least once larger in bytes, pictures and rows than every
+    earlier one.  Every load's planes equal the oracle's and the status is clean."""
+    S = pytest.importorskip("heif_amd.synth_encoder")
+
+    small = dict(log2_ctb=4, log2_max_tb=4)  # 4, 6 and 8 WPP rows of CTB 16
+    shapes = {"a": dict(width=96, height=64, **small), "b": dict(width=160, height=96, **small),
+              "c": dict(width=224, height=128, **small), "d": dict(width=96, height=64, log2_ctb=5)}
+    loads = [("spread", "a"), ("lanes", "abd"), ("solo", "c"), ("lanes", "abcd"), ("spread", "cb")]
+    batch, results, seed = None, [], 40
+    for parse, names in loads:
+        datas = []
+        for k in names:
+            seed += 1
+            datas.append(S.single_heic(S.SynthParams(wpp=1, **shapes[k]), seed=seed))
+        imgs = [H.HeifImage.parse(d) for d in datas]
+        outs = ctx.alloc_outputs(imgs)
+        batch = ctx.prepare(imgs, reuse=batch, wait=False, parse=parse)
+        assert batch.parse_geometry()["mode"] == parse
+        batch.decode_async(outs)
+        results.append((parse, datas, outs))
+    torch.cuda.synchronize()
+    for parse, datas, outs in results:
+        for k, (d, o) in enumerate(zip(datas, outs)):
+            ref = oracle_mod.decode_heic(d, with_checks=False)
+            for got, want in zip(planes_np(o), (ref.y, ref.cb, ref.cr)):
+                assert got.shape == want.shape and np.array_equal(got, want), (parse, k)
+    assert not any(batch.status())
+    assert not any(batch.status_previous())
+    batch.free()
+
+
 def test_rows_mode_removed(H, ctx, halfmoonbay):
     """HEIFGPU_PARSE_ROWS (ABI 5's row waves) is gone in ABI 6:
     prepare answers HEIFGPU_E_UNSUPPORTED and the batch is not created."""
