@@ -136,16 +136,26 @@ class HeifImage:
             cache[key] = t
         return cache[key]
 
-    def source_rect(self, window=None):
+    def source_rect(self, window=None, size=None, filter: str = "area"):
         """(x, y, w, h) of the decoded planes that a render of `window` reads
         (heifgpu_window_source_rect): window = (x, y, w, h) in displayed
         coordinates, the tuples render_scaled(windows=) takes; None or
-        (0, 0, 0, 0) is the whole displayed picture.  ValueError for a window
-        that is empty or not inside the displayed picture."""
+        (0, 0, 0, 0) is the whole displayed picture.  filter "bilinear" or
+        "bicubic" with size = (h, w), the rendered size, widens the rectangle by
+        the halo the filter's taps reach beyond the window
+        (heifgpu_window_source_rect_resampled).  ValueError for a window that is
+        empty or not inside the displayed picture."""
         w = _lib.Rect(*(int(v) for v in window)) if window is not None else _lib.Rect()
         src = _lib.Rect()
+        f = _filter_code(filter)
         try:
-            _lib.check(lib.heifgpu_window_source_rect(self._h, ctypes.byref(w), ctypes.byref(src)))
+            if f == _lib.FILTER_AREA:
+                _lib.check(lib.heifgpu_window_source_rect(self._h, ctypes.byref(w), ctypes.byref(src)))
+            else:
+                if size is None:
+                    raise ValueError(f"source_rect(filter={filter!r}) needs the rendered size")
+                sc = _lib.Scale(int(size[1]), int(size[0]), w.x, w.y, w.width, w.height)
+                _lib.check(lib.heifgpu_window_source_rect_resampled(self._h, ctypes.byref(sc), f, ctypes.byref(src)))
         except HeifGpuError as e:
             raise ValueError(str(e)) from None
         return src.as_tuple()
@@ -214,13 +224,20 @@ def _inside(need, valid) -> bool:
             and need[1] + need[3] <= valid[1] + valid[3])
 
 
-def _check_valid(what: str, i: int, out: "DecodedImage", alpha, window) -> None:
+def _filter_code(filter: str) -> int:
+    if filter not in _lib.FILTERS:
+        raise ValueError(f"filter {filter!r}: one of {sorted(_lib.FILTERS)}")
+    return _lib.FILTERS[filter]
+
+
+def _check_valid(what: str, i: int, out: "DecodedImage", alpha, window, size=None, filter: str = "area") -> None:
     """ValueError if rendering `window` of out (None: the whole displayed picture)
-    would read samples a window decode did not write, of out or of its alpha image."""
+    would read samples a window decode did not write, of out or of its alpha image
+    (for a filtered render to `size`: the window and its taps' halo)."""
     parts = [(n, o) for n, o in (("image", out), ("alpha image", alpha)) if o is not None and o.valid is not None]
     if not parts:
         return
-    need = out.image.source_rect(window)
+    need = out.image.source_rect(window, size, filter)
     for name, o in parts:
         if not _inside(need, o.valid):
             raise ValueError(f"{what}: {name} {i} was decoded for the rectangle {o.valid} of its planes, "
@@ -306,7 +323,8 @@ class DecodeContext:
 
     def prepare(self, images: Sequence[HeifImage], tile_stride: int = 1, tile_offset: int = 0,
                 reuse: Optional["DeviceBatch"] = None, wait: bool = True, parse: str = "auto",
-                pics_per_wave: int = 0, pipeline_sets: int = 0, windows=None, rects=None) -> "DeviceBatch":
+                pics_per_wave: int = 0, pipeline_sets: int = 0, windows=None, rects=None, size=None,
+                filter: str = "area") -> "DeviceBatch":
         """Device batch of `images` (heifgpu_batch_prepare_ex).  tile_stride /
         tile_offset select the grid tiles k % tile_stride == tile_offset (the
         single-image tile split across GPUs); `reuse` reloads an existing batch
@@ -323,10 +341,14 @@ class DecodeContext:
         sub-pictures) that a render of that window reads are uploaded and
         decoded.  rects[i] = (x, y, w, h) gives the rectangle in decoded-plane
         coordinates instead and wins over windows[i]: an alpha image is
-        prepared with its colour image's HeifImage.source_rect(window).  The
+        prepared with its colour image's HeifImage.source_rect(window).  For a
+        filtered render (render_scaled / render_tensor with filter "bilinear"
+        or "bicubic") pass that filter and size = (h, w), the rendered size:
+        the windows' rectangles then include the halo the taps read.  The
         rectangles end up in DeviceBatch.rects and, at decode_async, in
         DecodedImage.valid."""
         n = len(images)
+        _filter_code(filter)
         for name, v in (("windows", windows), ("rects", rects)):
             if v is not None and len(v) != n:
                 raise ValueError(f"{name} must have one entry per image")
@@ -335,7 +357,7 @@ class DecodeContext:
             if rects is not None and rects[i] is not None:
                 chosen[i] = tuple(int(v) for v in rects[i])
             elif windows is not None and windows[i] is not None:
-                chosen[i] = im.source_rect(windows[i])
+                chosen[i] = im.source_rect(windows[i], size, filter)
             if chosen[i] is not None and chosen[i][2] == 0 and chosen[i][3] == 0:
                 chosen[i] = None  # the "everything" form
         src = None
@@ -466,14 +488,17 @@ class DecodeContext:
         if stream is None:
             stream = self._torch.cuda.current_stream(self.device).cuda_stream
         xf, keep = self._transforms(outs, colorspace, wide)
-        fn, mid = (getattr(lib, name), mid) if xf is None else (getattr(lib, name + "_color"), mid + (xf,))
+        if callable(mid):  # a filtered render: one entry point, its transforms (or NULL) where mid puts them
+            fn, mid = getattr(lib, name), mid(xf)
+        else:
+            fn, mid = (getattr(lib, name), mid) if xf is None else (getattr(lib, name + "_color"), mid + (xf,))
         _lib.check(fn(self._h, imgs, len(outs), DecodeContext.planes_of(outs), aimgs, aplanes, *mid, surf,
                       ctypes.c_void_p(stream)))
 
-    def _scales(self, what, outs, alphas, size, mode, windows):
+    def _scales(self, what, outs, alphas, size, mode, windows, filter="area"):
         """(box height, box width, the heifgpu_scale of every image) of a scaled render:
         windows[i], else the fit of `mode`; ValueError if one reads samples that a
-        window decode did not write."""
+        window decode did not write (through `filter`'s taps)."""
         bh, bw = int(size[0]), int(size[1])
         scales = (_lib.Scale * max(len(outs), 1))()
         for i, o in enumerate(outs):
@@ -485,7 +510,8 @@ class DecodeContext:
                 _lib.check(lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_MODES[mode], ctypes.byref(scales[i])))
         for i, o in enumerate(outs):
             sc = scales[i]
-            _check_valid(what, i, o, alphas[i] if alphas is not None else None, (sc.x, sc.y, sc.width, sc.height))
+            _check_valid(what, i, o, alphas[i] if alphas is not None else None, (sc.x, sc.y, sc.width, sc.height),
+                         (sc.out_height, sc.out_width), filter)
         return bh, bw, scales
 
     def _scaled_outputs(self, n, scales, box, shape, dtype):
@@ -530,7 +556,7 @@ class DecodeContext:
 
     def render_scaled(self, outs: Sequence[DecodedImage], size, mode: str = "cover", fmt: str = "rgb8",
                       alphas: Optional[Sequence[Optional[DecodedImage]]] = None, windows=None,
-                      stream: Optional[int] = None, colorspace: Optional[str] = None):
+                      stream: Optional[int] = None, colorspace: Optional[str] = None, filter: str = "area"):
         """render() onto a smaller grid: the exact area average of a window of
         every displayed picture, with ONE heifgpu_render_batch_scaled call (one
         kernel launch).  size = (h, w) is the box; mode "cover" (a centred
@@ -543,26 +569,34 @@ class DecodeContext:
         and a list of (h_i, w_i, C) tensors for "contain".  Dtypes, fmt,
         alphas and colorspace as in render(): with a colorspace the result is
         the transform of what render_scaled() writes without one (the rounded
-        averages are transformed, not the source pixels)."""
+        averages are transformed, not the source pixels).  filter "bilinear" or
+        "bicubic" resamples with Pillow's antialiased filter of that name
+        instead of the area average (heifgpu_render_batch_resampled): per
+        channel, for the 8-bit formats, exactly what PIL's
+        Image.resize(size, filter, box=window) makes of render()'s picture."""
         torch = self._torch
         n = len(outs)
         f = _lib.PIX_FORMATS[fmt]
         ch, wide = (4 if f & 1 else 3), f >= _lib.PIX_RGB16
+        filt = _filter_code(filter)
         if mode not in _lib.FIT_MODES:
             raise ValueError(f"mode {mode!r}: one of {sorted(_lib.FIT_MODES)}")
         self._check_images("render_scaled", outs, alphas, windows=windows)
-        bh, bw, scales = self._scales("render_scaled", outs, alphas, size, mode, windows)
+        bh, bw, scales = self._scales("render_scaled", outs, alphas, size, mode, windows, filter)
         whole, res = self._scaled_outputs(n, scales, (bh, bw) if windows is not None or mode != "contain" else None,
                                           lambda h, w: (h, w, ch), torch.int16 if wide else torch.uint8)
-        if n:
+        if n and filt == _lib.FILTER_AREA:
             self._submit("heifgpu_render_batch_scaled", outs, alphas, colorspace, wide, stream, (f, scales),
                          self._surfaces(res))
+        elif n:
+            self._submit("heifgpu_render_batch_resampled", outs, alphas, colorspace, wide, stream,
+                         lambda xf: (f, scales, filt, xf), self._surfaces(res))
         return whole if whole is not None else res
 
     def render_tensor(self, outs: Sequence[DecodedImage], size, mode: str = "cover", dtype=None, layout: str = "chw",
                       mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), src: str = "rgb8", windows=None,
                       flips=None, alphas: Optional[Sequence[Optional[DecodedImage]]] = None, scale_bias=None,
-                      stream: Optional[int] = None, colorspace: Optional[str] = None):
+                      stream: Optional[int] = None, colorspace: Optional[str] = None, filter: str = "area"):
         """render_scaled() as a loader wants it: crop, flip and normalise into
         float elements with ONE heifgpu_render_batch_tensor call (one kernel
         launch).  With R the integers render_scaled(fmt=src) gives, flipped
@@ -575,9 +609,12 @@ class DecodeContext:
         (pictures of different bit depths B then have no common a, b: ValueError).
         layout "chw" returns ONE (N, C, h, w) tensor, "hwc" ONE (N, h, w, C)
         tensor, for cover, stretch and windows; "contain" returns a list of
-        (C, h_i, w_i) or (h_i, w_i, C) tensors.  size, mode, windows, alphas
-        and colorspace as in render_scaled(): R is then what
-        render_scaled(colorspace=) gives."""
+        (C, h_i, w_i) or (h_i, w_i, C) tensors.  size, mode, windows, alphas,
+        colorspace and filter as in render_scaled(): R is then what
+        render_scaled(colorspace=, filter=) gives (with "bilinear" or "bicubic"
+        the pixels Pillow's resize gives, which is what most vision models were
+        trained on; a flip then acts on R, not on the taps)."""
+        filt = _filter_code(filter)
         torch = self._torch
         n = len(outs)
         f = _lib.PIX_FORMATS[src]
@@ -609,7 +646,7 @@ class DecodeContext:
             a, b = [1.0 / (maxv * s) for s in std], [-m / s for m, s in zip(mean, std)]  # in double, rounded once below
         for c in range(ch):
             tf.a[c], tf.b[c] = a[c], b[c]
-        bh, bw, scales = self._scales("render_tensor", outs, alphas, size, mode, windows)
+        bh, bw, scales = self._scales("render_tensor", outs, alphas, size, mode, windows, filter)
         chw = layout == "chw"
         whole, res = self._scaled_outputs(n, scales, (bh, bw) if windows is not None or mode != "contain" else None,
                                           lambda h, w: (ch, h, w) if chw else (h, w, ch), dtype)
@@ -621,8 +658,12 @@ class DecodeContext:
             surf[i].stride_c = t.stride(0) * t.element_size() if chw else 0
             surf[i].stride_y = t.stride(1 if chw else 0) * t.element_size()
         fl = None if flips is None else (ctypes.c_uint32 * n)(*[int(v) for v in flips])
-        self._submit("heifgpu_render_batch_tensor", outs, alphas, colorspace, wide, stream,
-                     (ctypes.byref(tf), scales, fl), surf)
+        if filt == _lib.FILTER_AREA:
+            self._submit("heifgpu_render_batch_tensor", outs, alphas, colorspace, wide, stream,
+                         (ctypes.byref(tf), scales, fl), surf)
+        else:
+            self._submit("heifgpu_render_batch_tensor_resampled", outs, alphas, colorspace, wide, stream,
+                         lambda xf: (ctypes.byref(tf), scales, filt, fl, xf), surf)
         return whole if whole is not None else res
 
 
@@ -764,15 +805,26 @@ class HeicDecoder:
         return (sc.x, sc.y, sc.width, sc.height) if sc.width or sc.height else None
 
     @classmethod
-    def _decode_pair(cls, data: bytes, device: int, size, mode: str, tiles: str, with_alpha: bool):
+    def _decode_pair(cls, data: bytes, device: int, size, mode: str, tiles: str, with_alpha: bool,
+                     filter: str = "area"):
         """The primary image and (with_alpha, when the file has one) its alpha
         image, decoded whole (tiles="all") or for the window that (size, mode)
-        reads (tiles="window")."""
+        reads through `filter` (tiles="window")."""
         if tiles not in ("all", "window"):
             raise ValueError(f"tiles {tiles!r}: 'all' or 'window'")
+        _filter_code(filter)
         ctx = cls.context(device)
         img = HeifImage.parse(data)
-        rect = img.source_rect(cls._fit_window(img, size, mode)) if tiles == "window" else None
+        rect = None
+        if tiles == "window":
+            rsize = None
+            if size is not None and filter != "area":  # the rendered size: the fit's, not the box ("contain")
+                sc = _lib.Scale()
+                d = img.display
+                _lib.check(lib.heifgpu_scale_fit(ctypes.byref(d), int(size[1]), int(size[0]), _lib.FIT_MODES[mode],
+                                                 ctypes.byref(sc)))
+                rsize = (sc.out_height, sc.out_width)
+            rect = img.source_rect(cls._fit_window(img, size, mode), rsize, filter if rsize is not None else "area")
         out = cls._decode_image(ctx, img, rect)
         aid = img.display.alpha_item_id
         alpha = cls._decode_image(ctx, HeifImage.parse(data, aid), rect) if aid and with_alpha else None
@@ -780,7 +832,8 @@ class HeicDecoder:
 
     @classmethod
     def decode_display(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, size=None,
-                       mode: str = "contain", tiles: str = "all", colorspace: Optional[str] = None):
+                       mode: str = "contain", tiles: str = "all", colorspace: Optional[str] = None,
+                       filter: str = "area"):
         """The picture a viewer shows: decodes the primary image and, when it
         has one (display.alpha_item_id), its alpha plane, then renders
         (DecodeContext.render) with clap / irot / imir applied.  fmt None picks
@@ -791,14 +844,16 @@ class HeicDecoder:
         pixels, bit for bit, for less work when `mode` or a clap crops.
         colorspace "srgb" / "display-p3" converts the picture from its ICC profile
         or nclx description to that space (DecodeContext.render); None leaves it
-        in its own, unlabelled."""
+        in its own, unlabelled.  filter, with a size: "area" (the area average,
+        right for reduction), "bilinear" or "bicubic" (Pillow's antialiased
+        filters, which also interpolate an enlargement as a viewer expects)."""
         ctx = cls.context(device)
-        out, alpha = cls._decode_pair(data, device, size, mode, tiles, True)
+        out, alpha = cls._decode_pair(data, device, size, mode, tiles, True, filter)
         if fmt is None:
             fmt = ("rgba" if alpha is not None else "rgb") + ("16" if out.info.bit_depth > 8 else "8")
         alphas = [alpha] if alpha is not None else None
         if size is not None:
-            return ctx.render_scaled([out], size, mode, fmt, alphas, colorspace=colorspace)[0]
+            return ctx.render_scaled([out], size, mode, fmt, alphas, colorspace=colorspace, filter=filter)[0]
         return ctx.render([out], fmt, alphas, colorspace=colorspace)[0]
 
     @classmethod
@@ -808,10 +863,10 @@ class HeicDecoder:
         primary image (and its alpha plane when `src` is an RGBA format and the
         file has one), then DecodeContext.render_tensor of that one picture:
         (C, h, w), or (h, w, C) for layout="hwc".  dtype, layout, mean, std, src
-        scale_bias and colorspace go through to render_tensor; tiles as in decode_display."""
+        scale_bias, colorspace and filter go through to render_tensor; tiles as in decode_display."""
         ctx = cls.context(device)
         rgba = kw.get("src", "rgb8").startswith("rgba")
-        out, alpha = cls._decode_pair(data, device, size, mode, tiles, rgba)
+        out, alpha = cls._decode_pair(data, device, size, mode, tiles, rgba, kw.get("filter", "area"))
         alphas = [alpha] if alpha is not None else None
         return ctx.render_tensor([out], size, mode, flips=[flip], alphas=alphas, **kw)[0]
 

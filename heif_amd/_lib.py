@@ -189,6 +189,9 @@ ELEM_F32, ELEM_F16, ELEM_BF16 = 0, 1, 2
 LAYOUT_CHW, LAYOUT_HWC = 0, 1
 LAYOUTS = {"chw": LAYOUT_CHW, "hwc": LAYOUT_HWC}
 
+FILTER_AREA, FILTER_BILINEAR, FILTER_BICUBIC = 0, 1, 2
+FILTERS = {"area": FILTER_AREA, "bilinear": FILTER_BILINEAR, "bicubic": FILTER_BICUBIC}
+
 FIT_STRETCH, FIT_CONTAIN, FIT_COVER = 0, 1, 2
 FIT_MODES = {"stretch": FIT_STRETCH, "contain": FIT_CONTAIN, "cover": FIT_COVER}
 
@@ -217,6 +220,8 @@ EXPORTS = (
     "heifgpu_batch_prepare_rects", "heifgpu_batch_count_pictures", "heifgpu_batch_picture_count",
     "heifgpu_image_get_color", "heifgpu_image_get_icc", "heifgpu_color_transform_make", "heifgpu_color_apply",
     "heifgpu_render_batch_color", "heifgpu_render_batch_scaled_color", "heifgpu_render_batch_tensor_color",
+    "heifgpu_render_batch_resampled", "heifgpu_render_batch_tensor_resampled", "heifgpu_resample_coeffs",
+    "heifgpu_resample_apply", "heifgpu_window_source_rect_resampled",
 )
 
 
@@ -309,6 +314,13 @@ def _load() -> ctypes.CDLL:
                                                     P(Surface), VP]),
         "heifgpu_render_batch_tensor_color": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), P(TensorFormat), P(Scale),
                                                     P(U32), P(VP), P(TensorSurface), VP]),
+        "heifgpu_render_batch_resampled": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), U32, P(Scale), U32, P(VP),
+                                                 P(Surface), VP]),
+        "heifgpu_render_batch_tensor_resampled": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), P(TensorFormat),
+                                                        P(Scale), U32, P(U32), P(VP), P(TensorSurface), VP]),
+        "heifgpu_resample_coeffs": (I32, [U32, U32, U32, U32, U32, U32, P(ctypes.c_int32), P(ctypes.c_int32), SZ, P(U32)]),
+        "heifgpu_resample_apply": (I32, [VP, U32, U32, U32, U32, P(Rect), U32, U32, U32, VP]),
+        "heifgpu_window_source_rect_resampled": (I32, [VP, P(Scale), U32, P(Rect)]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     # (and no window decode: DecodeContext.prepare without windows then goes through prepare_ex)
@@ -316,7 +328,10 @@ def _load() -> ctypes.CDLL:
                 "heifgpu_batch_prepare_rects", "heifgpu_batch_count_pictures", "heifgpu_batch_picture_count",
                 # the colour-managed render (colorspace= then needs a build that has it)
                 "heifgpu_image_get_color", "heifgpu_image_get_icc", "heifgpu_color_transform_make", "heifgpu_color_apply",
-                "heifgpu_render_batch_color", "heifgpu_render_batch_scaled_color", "heifgpu_render_batch_tensor_color"}
+                "heifgpu_render_batch_color", "heifgpu_render_batch_scaled_color", "heifgpu_render_batch_tensor_color",
+                # the filtered renders (filter= other than "area" then needs a build that has them)
+                "heifgpu_render_batch_resampled", "heifgpu_render_batch_tensor_resampled", "heifgpu_resample_coeffs",
+                "heifgpu_resample_apply", "heifgpu_window_source_rect_resampled"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue

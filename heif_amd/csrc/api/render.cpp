@@ -1,12 +1,14 @@
 // render.cpp — the render family of the C ABI: heifgpu_render_batch, _scaled and _tensor
-// with their _color forms, and heifgpu_scale_fit.  Each call checks its arguments and
-// fills its descriptors; render_submit sends any of the three descriptor types.
+// with their _color forms, heifgpu_scale_fit, and the filtered (bilinear / bicubic) forms
+// of the scaled and tensor renders with their host hooks.  Each call checks its arguments
+// and fills its descriptors; render_submit sends any of the descriptor types.
 // (The calls take their C linkage from the declarations of include/heifgpu.h.)
 #include <cmath>
 #include <memory>
 #include <vector>
 
 #include "../common/desc.hpp"
+#include "../host/resample.hpp"
 #include "../kernels/color_xform.hpp"
 #include "api.hpp"
 
@@ -426,6 +428,185 @@ int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *im
                                 const heifgpu_tensor_format *fmt, const heifgpu_scale *scale, const uint32_t *flip,
                                 const heifgpu_tensor_surface *out, void *stream) {
     return render_tensor_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, fmt, scale, flip, nullptr, out, stream);
+}
+
+// ---- the filtered renders (k_render_resampled) ----
+// heifgpu_scale's window of image img as (x, y, w, h) of its displayed picture
+static int scale_window(const heifgpu_image *img, const heifgpu_scale &sc, uint32_t (&w)[4]) {
+    if (!img) return fail(HEIFGPU_E_INVALID, "null image");
+    const DisplayMap &dm = img->img.display;
+    if (!sc.out_width || !sc.out_height || sc.out_width > 65535 || sc.out_height > 65535)
+        return fail(HEIFGPU_E_INVALID, "rendered size outside 1..65535");
+    w[0] = w[1] = 0, w[2] = dm.out_width, w[3] = dm.out_height;
+    if (sc.width || sc.height) {
+        if (!sc.width || !sc.height || sc.x >= dm.out_width || sc.y >= dm.out_height ||
+            sc.width > dm.out_width - sc.x || sc.height > dm.out_height - sc.y)
+            return fail(HEIFGPU_E_INVALID, "window empty or outside the displayed picture");
+        w[0] = sc.x, w[1] = sc.y, w[2] = sc.width, w[3] = sc.height;
+    }
+    if (dm.out_width > 65535 || dm.out_height > 65535)
+        return fail(HEIFGPU_E_UNSUPPORTED, "displayed side above 65535");
+    return HEIFGPU_OK;
+}
+
+// What the two filtered calls check and fill alike for image i: the window, render_desc_fill
+// through the map of the whole displayed picture, the two axes and the tile geometry.
+static int resample_desc_fill(size_t i, const heifgpu_image *const *imgs, const heifgpu_planes *in,
+                              const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                              const heifgpu_scale &sc, uint32_t filter, uint32_t flip, const heifgpu_surface *out,
+                              int &bps, RenderDesc &d, RsParams &p) {
+    uint32_t w[4];
+    if (int rc = scale_window(imgs[i], sc, w)) return rc;
+    const DisplayMap &dm = imgs[i]->img.display;
+    if (int rc = render_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, out, dm, sc.out_width, sc.out_height, bps, d))
+        return rc;
+    int depth = 8;
+    while ((1 << depth) - 1 < d.maxv) ++depth;
+    p = RsParams{};
+    p.ax = rs_axis(int(dm.out_width), int(w[0]), int(w[0] + w[2]), int(sc.out_width), int(filter));
+    p.ay = rs_axis(int(dm.out_height), int(w[1]), int(w[1] + w[3]), int(sc.out_height), int(filter));
+    p.P = rs_precision(depth);
+    p.flip = int32_t(flip);
+    p.sw = rs_subtile(p.ax);
+    d.tiles_x = (d.out_w + kRsTileW - 1) / kRsTileW;
+    d.tiles = d.tiles_x * ((d.out_h + kRsTileH - 1) / kRsTileH);
+    return HEIFGPU_OK;
+}
+
+int heifgpu_render_batch_resampled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                   const heifgpu_planes *in, const heifgpu_image *const *alpha_imgs,
+                                   const heifgpu_planes *alpha_in, uint32_t format, const heifgpu_scale *scale,
+                                   uint32_t filter, const heifgpu_color_transform *const *xf,
+                                   const heifgpu_surface *out, void *stream) {
+    if (filter > HEIFGPU_FILTER_BICUBIC) return fail(HEIFGPU_E_INVALID, "filter");
+    if (filter == HEIFGPU_FILTER_AREA)
+        return render_scaled_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, scale, xf, out, stream);
+    // (the context is looked at last, as in heifgpu_render_batch_scaled)
+    if (!imgs || !in || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    std::vector<ResampleDesc> descs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (int rc = resample_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, scale[i], filter, 0, out, bps,
+                                        descs[i].r, descs[i].p))
+            return rc;
+        max_tiles = std::max(max_tiles, descs[i].r.tiles);
+    }
+    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
+    return render_submit(ctx, imgs, descs, max_tiles, format, bps, xf, stream);
+}
+
+int heifgpu_render_batch_tensor_resampled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                          const heifgpu_planes *in, const heifgpu_image *const *alpha_imgs,
+                                          const heifgpu_planes *alpha_in, const heifgpu_tensor_format *fmt,
+                                          const heifgpu_scale *scale, uint32_t filter, const uint32_t *flip,
+                                          const heifgpu_color_transform *const *xf, const heifgpu_tensor_surface *out,
+                                          void *stream) {
+    if (filter > HEIFGPU_FILTER_BICUBIC) return fail(HEIFGPU_E_INVALID, "filter");
+    if (filter == HEIFGPU_FILTER_AREA)
+        return render_tensor_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, fmt, scale, flip, xf, out, stream);
+    if (!imgs || !in || !fmt || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (fmt->src > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "source format");
+    if (fmt->elem > HEIFGPU_ELEM_BF16) return fail(HEIFGPU_E_INVALID, "element type");
+    if (fmt->layout > HEIFGPU_LAYOUT_HWC) return fail(HEIFGPU_E_INVALID, "layout");
+    const int nch = (fmt->src & 1) ? 4 : 3;
+    for (int c = 0; c < nch; ++c)
+        if (!std::isfinite(fmt->a[c]) || !std::isfinite(fmt->b[c]))
+            return fail(HEIFGPU_E_INVALID, "scale or bias not finite");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    const int64_t esz = fmt->elem == HEIFGPU_ELEM_F32 ? 4 : 2;
+    std::vector<ResampleTensorDesc> descs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t fl = flip ? flip[i] : 0;
+        if (fl > 3) return fail(HEIFGPU_E_INVALID, "flip above 3");
+        TensorDesc &td = descs[i].t;
+        td = TensorDesc{};
+        if (int rc = resample_desc_fill(i, imgs, in, alpha_imgs, alpha_in, fmt->src, scale[i], filter, fl, nullptr, bps,
+                                        td.s.r, descs[i].p))
+            return rc;
+        const heifgpu_tensor_surface &o = out[i];
+        if (!o.data || (reinterpret_cast<uintptr_t>(o.data) & uintptr_t(esz - 1)))
+            return fail(HEIFGPU_E_INVALID, "tensor data null or not aligned to its element");
+        const int64_t row = int64_t(td.s.r.out_w) * esz * (fmt->layout == HEIFGPU_LAYOUT_HWC ? nch : 1);
+        if (o.stride_y < row || (o.stride_y & (esz - 1)))
+            return fail(HEIFGPU_E_INVALID, "stride_y below the row or not a multiple of the element size");
+        if (fmt->layout == HEIFGPU_LAYOUT_CHW && (o.stride_c & (esz - 1)))
+            return fail(HEIFGPU_E_INVALID, "stride_c not a multiple of the element size");
+        td.s.r.out = reinterpret_cast<uint64_t>(o.data);
+        td.stride_c = fmt->layout == HEIFGPU_LAYOUT_CHW ? o.stride_c : 0;
+        td.stride_y = o.stride_y;
+        td.elem = int32_t(fmt->elem);
+        td.layout = int32_t(fmt->layout);
+        for (int c = 0; c < 4; ++c) {
+            td.a[c] = c < nch ? fmt->a[c] : 0.f;
+            td.b[c] = c < nch ? fmt->b[c] : 0.f;
+        }
+        max_tiles = std::max(max_tiles, td.s.r.tiles);
+    }
+    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
+    return render_submit(ctx, imgs, descs, max_tiles, fmt->src, bps, xf, stream);
+}
+
+// ---- host only: the resampling's coefficients, its two passes, its source rectangle ----
+int heifgpu_resample_coeffs(uint32_t in_size, uint32_t in0, uint32_t in1, uint32_t out_size, uint32_t filter,
+                            uint32_t bits, int32_t *bounds, int32_t *kk, size_t cap, uint32_t *ksize) {
+    if (!ksize) return fail(HEIFGPU_E_INVALID, "null argument");
+    if (!resample_axis_ok(in_size, in0, in1, out_size, filter, bits))
+        return fail(HEIFGPU_E_INVALID, "side, window, size, filter or depth outside the resampling's range");
+    const uint32_t ks = uint32_t(resample_coeffs(int(in_size), int(in0), int(in1), int(out_size), int(filter), int(bits),
+                                                 nullptr, nullptr));
+    *ksize = ks;
+    if (kk && cap < size_t(ks) * out_size) return fail(HEIFGPU_E_INVALID, "kk holds fewer than out_size * ksize entries");
+    if (bounds || kk)
+        resample_coeffs(int(in_size), int(in0), int(in1), int(out_size), int(filter), int(bits), bounds, kk);
+    return HEIFGPU_OK;
+}
+
+int heifgpu_resample_apply(const void *in, uint32_t in_width, uint32_t in_height, uint32_t channels, uint32_t bits,
+                           const heifgpu_rect *window, uint32_t out_width, uint32_t out_height, uint32_t filter,
+                           void *out) {
+    if (!in || !out) return fail(HEIFGPU_E_INVALID, "null argument");
+    if (channels < 1 || channels > 4) return fail(HEIFGPU_E_INVALID, "channels outside 1..4");
+    heifgpu_rect w{0, 0, in_width, in_height};
+    if (window && (window->width || window->height)) w = *window;
+    if (!resample_axis_ok(in_width, w.x, uint64_t(w.x) + w.width, out_width, filter, bits) ||
+        !resample_axis_ok(in_height, w.y, uint64_t(w.y) + w.height, out_height, filter, bits))
+        return fail(HEIFGPU_E_INVALID, "side, window, size, filter or depth outside the resampling's range");
+    const size_t count = size_t(in_width) * in_height * channels;
+    const uint32_t maxv = (1u << bits) - 1;
+    for (size_t k = 0; bits > 8 && k < count; ++k)
+        if (static_cast<const uint16_t *>(in)[k] > maxv) return fail(HEIFGPU_E_INVALID, "code above maxv");
+    resample_apply(in, bits > 8 ? 2 : 1, int(in_width), int(in_height), int(channels), int(bits), int(w.x), int(w.y),
+                   int(w.width), int(w.height), int(out_width), int(out_height), int(filter), out);
+    return HEIFGPU_OK;
+}
+
+int heifgpu_window_source_rect_resampled(const heifgpu_image *img, const heifgpu_scale *scale, uint32_t filter,
+                                         heifgpu_rect *src) {
+    if (!img || !scale || !src) return fail(HEIFGPU_E_INVALID, "null argument");
+    if (filter > HEIFGPU_FILTER_BICUBIC) return fail(HEIFGPU_E_INVALID, "filter");
+    uint32_t w[4];
+    if (int rc = scale_window(img, *scale, w)) return rc;
+    if (filter != HEIFGPU_FILTER_AREA) {
+        // per axis the taps of the first output to those of the last, in the displayed picture
+        const DisplayMap &dm = img->img.display;
+        const uint32_t side[2] = {dm.out_width, dm.out_height}, outs[2] = {scale->out_width, scale->out_height};
+        for (int k = 0; k < 2; ++k) {
+            const RsAxis a = rs_axis(int(side[k]), int(w[k]), int(w[k] + w[2 + k]), int(outs[k]), int(filter));
+            int lo, hi, skip;
+            rs_bounds(a, 0, lo, skip);
+            rs_bounds(a, int(outs[k]) - 1, skip, hi);
+            w[k] = uint32_t(lo);
+            w[2 + k] = uint32_t(hi - lo);
+        }
+    }
+    Rect r;
+    if (!window_source_rect(img->img, Rect{w[0], w[1], w[2], w[3]}, r))
+        return fail(HEIFGPU_E_INVALID, "window empty or outside the displayed picture");
+    *src = heifgpu_rect{r.x, r.y, r.w, r.h};
+    return HEIFGPU_OK;
 }
 
 int heifgpu_render_batch_tensor_color(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,

@@ -12,6 +12,7 @@
 //   5. k_sao_out    SAO (8.7.3) + crop + grid placement into the caller's planes
 #pragma once
 #include "../common/desc.hpp"
+#include "resample.hpp"
 #include "wave.hpp"
 #include <cstdlib>
 #include <vector>
@@ -211,6 +212,40 @@ struct TensorDesc {
     float a[4], b[4];
 };
 
+// k_render_resampled (resample.hip): one descriptor per image of a heifgpu_render_batch_resampled
+// call.  r is the image's RenderDesc with the map of the WHOLE displayed picture D (no window
+// folded in: taps reach beyond the window) and out_w x out_h the rendered size; ax and ay are
+// the resampling along D's x and y (resample.hpp), in D's coordinates.  Stored pixel (sx, sy)
+// shows output (flip & 1 ? out_w - 1 - sx : sx, flip & 2 ? out_h - 1 - sy : sy).
+constexpr int kRsTileW = 64, kRsTileH = 16;  // stored pixels of a workgroup
+constexpr int kRsRows = 16, kRsCols = 256;   // rows x columns of D in one chunk
+constexpr int kRsCoefCap = 2048;             // the coefficient table in LDS: sw * min(ax.ksize, kRsCols) entries
+struct RsParams {
+    RsAxis ax, ay;
+    int32_t P;       // rs_precision(depth)
+    int32_t flip;
+    int32_t sw;      // columns of the tile taken together, 1..64
+    int32_t pad;
+};
+struct ResampleDesc {
+    RenderDesc r;
+    RsParams p;
+};
+// with the tensor epilogue: t.s.r as ResampleDesc::r, t's own fields as in TensorDesc
+// (the ScaleDesc fields between them are unused)
+struct ResampleTensorDesc {
+    TensorDesc t;
+    RsParams p;
+};
+// the sub-tile width for an axis: the widest whose footprint fits a chunk and whose
+// coefficients fit the table (a wider footprint is walked in several chunks, one column at a time)
+inline int rs_subtile(const RsAxis &ax) {
+    const int kw = ax.ksize < kRsCols ? ax.ksize : kRsCols;
+    int sw = kRsTileW;
+    while (sw > 1 && (double(sw - 1) * ax.scale + double(ax.ksize) + 1.0 > double(kRsCols) || sw * kw > kRsCoefCap)) --sw;
+    return sw;
+}
+
 // The colour-managed renders (heifgpu_render_batch_color and its kin): one ColorRef per
 // image, in the same device array behind the call's descriptors.  lut addresses the
 // transform's tables in the context's cache, in_lut[3][n] (uint16) then 4096 words out_lut[i] | out_lut[i + 1] << 16;
@@ -303,6 +338,13 @@ hipError_t launch_gather_tiles(const GatherArgs &g, hipStream_t s);
 template <typename Desc>
 hipError_t launch_render(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, bool color,
                          hipStream_t s);
+// (the two descriptors of k_render_resampled: specialised in resample.hip)
+template <>
+hipError_t launch_render<ResampleDesc>(const ResampleDesc *descs, int n_images, int max_tiles, int format,
+                                       int bytes_per_sample, bool color, hipStream_t s);
+template <>
+hipError_t launch_render<ResampleTensorDesc>(const ResampleTensorDesc *descs, int n_images, int max_tiles, int format,
+                                             int bytes_per_sample, bool color, hipStream_t s);
 hipError_t launch_parse(const BatchArgs &a, hipStream_t s);
 // (launch_parse's: the kernels of parse_solo.hip and parse_lean.hip)
 hipError_t launch_parse_solo(const BatchArgs &a, hipStream_t s);

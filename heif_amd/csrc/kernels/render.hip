@@ -49,140 +49,12 @@
 
 #include "color_xform.hpp"
 #include "kernels.hpp"
+#include "render_px.hpp"  // Px, convert, xform_rgb, store_row, store_tensor (shared with resample.hip)
 
 namespace hg {
 
 #if !defined(HG_HOST_EMU)
 namespace {
-
-struct Px {
-    uint32_t lo, hi;  // 8-bit formats: lo = R | G << 8 | B << 16 | A << 24; 16-bit: lo = R | G << 16, hi = B | A << 16
-};
-
-template <typename T>
-__device__ __forceinline__ int sample(uint64_t plane, int32_t pitch, int x, int y) {
-    return (int)*reinterpret_cast<const T *>(reinterpret_cast<const uint8_t *>(plane) + (size_t)y * (size_t)pitch +
-                                             (size_t)x * sizeof(T));
-}
-
-// the transform's tables through global-address-space pointers (global_load, not flat_load)
-typedef const uint16_t __attribute__((address_space(1))) *XfLut;
-
-// the transform of one RGB triple, in place (x.lut != 0); staged: the same tables copied
-// to LDS (the HG_XF_LDS build, an A/B of where the tables are read from), else null
-__device__ __forceinline__ void xform_rgb(const ColorRef &x, uint32_t &R, uint32_t &G, uint32_t &B,
-                                          const uint16_t *staged = nullptr) {
-    if (staged) {
-        const XfOutPairs<const uint32_t *> out{reinterpret_cast<const uint32_t *>(staged + 3 * x.n)};
-        color_xform_px(staged, x.n, out, x.m, R, G, B);
-        return;
-    }
-    typedef const uint32_t __attribute__((address_space(1))) *XfWords;
-    const XfLut in = (XfLut)x.lut;
-    const XfOutPairs<XfWords> out{(XfWords)(x.lut + 6 * (uint64_t)x.n)};
-    color_xform_px(in, x.n, out, x.m, R, G, B);
-}
-
-template <typename Pel, int FMT>
-__device__ __forceinline__ Px convert(const RenderDesc &d, int ox, int oy) {
-    const int x = d.m[0] * ox + d.m[1] * oy + d.t[0], y = d.m[2] * ox + d.m[3] * oy + d.t[1];
-    const int ys = sample<Pel>(d.plane[0], d.pitch[0], x, y) >> d.shift;
-    int cb = 0, cr = 0;
-    if (d.chroma) {
-        const int xc = x >> chroma_sx(d.chroma), yc = y >> chroma_sy(d.chroma);
-        cb = (sample<Pel>(d.plane[1], d.pitch[1], xc, yc) >> d.shift) - d.cmid;
-        cr = (sample<Pel>(d.plane[2], d.pitch[2], xc, yc) >> d.shift) - d.cmid;
-    }
-    const int yv = d.ys * (ys - d.yoff);
-    const uint32_t R = (uint32_t)min(max((yv + d.cr_r * cr + 32768) >> 16, 0), d.maxv);
-    const uint32_t G = (uint32_t)min(max((yv - d.cb_g * cb - d.cr_g * cr + 32768) >> 16, 0), d.maxv);
-    const uint32_t B = (uint32_t)min(max((yv + d.cb_b * cb + 32768) >> 16, 0), d.maxv);
-    uint32_t A = 0;
-    if (FMT & 1) {
-        A = (uint32_t)d.maxv;  // opaque
-        if (d.alpha) {
-            const int a = d.alpha_bps == 2 ? sample<uint16_t>(d.alpha, d.alpha_pitch, x, y)
-                                           : sample<uint8_t>(d.alpha, d.alpha_pitch, x, y);
-            A = (uint32_t)(d.alpha_shift >= 0 ? a >> d.alpha_shift : a << -d.alpha_shift);
-        }
-    }
-    if (FMT >= RENDER_RGB16) return {R | (G << 16), B | (A << 16)};
-    return {R | (G << 8) | (B << 16) | (A << 24), 0};
-}
-
-// One wave stores 64 pixels of output row oy starting at oxw (a multiple of 64);
-// every lane of the wave calls it (lanes past the row's end with valid = false).
-template <int FMT>
-__device__ __forceinline__ void store_row(const RenderDesc &d, int oy, int oxw, int lane, Px p, bool valid) {
-    uint8_t *row = reinterpret_cast<uint8_t *>(d.out) + (size_t)oy * (size_t)d.out_pitch;
-    const bool al4 = !(reinterpret_cast<uintptr_t>(row) & 3);  // (64 pixels of any format are a multiple of 4 bytes)
-    const int ox = oxw + lane;
-    if (FMT == RENDER_RGB8) {
-        const uint32_t nxt = __shfl_down(p.lo, 1);
-        const int q = lane & 3;
-        if (al4 && (ox | 3) < d.out_w) {
-            const uint32_t w = q == 0 ? p.lo | (nxt << 24) : q == 1 ? (p.lo >> 8) | (nxt << 16) : (p.lo >> 16) | (nxt << 8);
-            if (q < 3) reinterpret_cast<uint32_t *>(row + (size_t)oxw * 3)[lane - (lane >> 2)] = w;
-        } else if (valid) {
-            uint8_t *o = row + (size_t)ox * 3;
-            o[0] = (uint8_t)p.lo;
-            o[1] = (uint8_t)(p.lo >> 8);
-            o[2] = (uint8_t)(p.lo >> 16);
-        }
-    } else if (FMT == RENDER_RGBA8) {
-        if (!valid) return;
-        if (al4) {
-            reinterpret_cast<uint32_t *>(row)[ox] = p.lo;
-        } else {
-            uint8_t *o = row + (size_t)ox * 4;
-            o[0] = (uint8_t)p.lo;
-            o[1] = (uint8_t)(p.lo >> 8);
-            o[2] = (uint8_t)(p.lo >> 16);
-            o[3] = (uint8_t)(p.lo >> 24);
-        }
-    } else if (FMT == RENDER_RGB16) {
-        const uint32_t nxt = __shfl_down(p.lo, 1);
-        if (al4 && (ox | 1) < d.out_w) {
-            uint32_t *w = reinterpret_cast<uint32_t *>(row + (size_t)oxw * 6) + 3 * (lane >> 1);
-            if (lane & 1) {
-                w[2] = (p.lo >> 16) | (p.hi << 16);
-            } else {
-                w[0] = p.lo;
-                w[1] = (p.hi & 0xffffu) | (nxt << 16);
-            }
-        } else if (valid) {  // (the API requires 2-byte alignment of the 16-bit formats)
-            uint16_t *o = reinterpret_cast<uint16_t *>(row) + (size_t)ox * 3;
-            o[0] = (uint16_t)p.lo;
-            o[1] = (uint16_t)(p.lo >> 16);
-            o[2] = (uint16_t)p.hi;
-        }
-    } else {
-        if (!valid) return;
-        if (!(reinterpret_cast<uintptr_t>(row) & 7)) {
-            reinterpret_cast<uint2 *>(row)[ox] = make_uint2(p.lo, p.hi);
-        } else if (al4) {
-            reinterpret_cast<uint32_t *>(row)[2 * (size_t)ox] = p.lo;
-            reinterpret_cast<uint32_t *>(row)[2 * (size_t)ox + 1] = p.hi;
-        } else {
-            uint16_t *o = reinterpret_cast<uint16_t *>(row) + (size_t)ox * 4;
-            o[0] = (uint16_t)p.lo;
-            o[1] = (uint16_t)(p.lo >> 16);
-            o[2] = (uint16_t)p.hi;
-            o[3] = (uint16_t)(p.hi >> 16);
-        }
-    }
-}
-
-// the transform of a converted pixel, in place (alpha kept)
-template <int FMT>
-__device__ __forceinline__ void xform_pixel(const ColorRef &x, Px &p, const uint16_t *staged) {
-    uint32_t R, G, B;
-    if (FMT >= RENDER_RGB16) R = p.lo & 0xffffu, G = p.lo >> 16, B = p.hi & 0xffffu;
-    else R = p.lo & 0xffu, G = (p.lo >> 8) & 0xffu, B = (p.lo >> 16) & 0xffu;
-    xform_rgb(x, R, G, B, staged);
-    if (FMT >= RENDER_RGB16) p = {R | (G << 16), B | (p.hi & 0xffff0000u)};
-    else p = {R | (G << 8) | (B << 16) | (p.lo & 0xff000000u), 0};
-}
 
 // FMTX: the pixel format, plus kRenderXf for the colour-managed instantiations, whose
 // ColorRefs lie behind the call's gridDim.y descriptors
@@ -299,14 +171,6 @@ void launch_fmt(const RenderDesc *descs, dim3 grid, int format, hipStream_t s) {
 // pitch 65 dwords as in k_render).
 constexpr int kScaleRowGroup = 4;  // source rows whose loads are issued together
 
-// sample() through a global-address-space pointer (global_load, not flat_load: its
-// wait does not also count LDS traffic)
-template <typename T>
-__device__ __forceinline__ int sample_g(uint64_t plane, int32_t pitch, int x, int y) {
-    typedef const T __attribute__((address_space(1))) *gptr;
-    return (int)*(gptr)(plane + (size_t)y * (size_t)pitch + (size_t)x * sizeof(T));
-}
-
 struct ScaleChroma {
     int cb[2], cr[2];  // as loaded, for a thread's two columns
 };
@@ -400,105 +264,6 @@ __device__ __forceinline__ void scale_columns(const ScaleDesc &s, int x0, int x1
             const uint32_t w = min((uint32_t)(k + 1) * oa, ahi) - max((uint32_t)k * oa, alo);
             scale_acc<FMT>(d, ly[g], cc, la[g], w, sum);
         }
-    }
-}
-
-// ---- the tensor epilogue (heifgpu_render_batch_tensor) ------------------------
-// F = fadd_rn(fmul_rn(float(R), a[c]), b[c]) in binary32, then rounded to the
-// element type.  Two roundings: the pair must not become a fused multiply-add.
-// __fmul_rn / __fadd_rn would not keep it apart: they are a plain product and sum
-// in the header, compiled under -ffp-contract=fast, and the compiler fuses them.
-// The product and the sum are written out here under a pragma that takes
-// the contraction flag off both, so nothing later can fuse them.  f16 is the hardware's
-// round-to-nearest-even conversion with gradual underflow (the f16 denormal mode
-// is on by default), bf16 round-to-nearest-even on the bits (the inputs are finite).
-__device__ __forceinline__ uint32_t tensor_elem(uint32_t level, float a, float b, int elem) {
-#pragma clang fp contract(off)
-    const float m = (float)level * a;
-    const float f = m + b;
-    const uint32_t u = __float_as_uint(f);
-    if (elem == TENSOR_F32) return u;
-    if (elem == TENSOR_F16) return (uint32_t) __builtin_bit_cast(uint16_t, (_Float16)f);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
-template <int FMT>
-__device__ __forceinline__ uint32_t px_channel(Px p, int c) {
-    if (FMT >= RENDER_RGB16) return (((c & 2) ? p.hi : p.lo) >> (16 * (c & 1))) & 0xffffu;
-    return (p.lo >> (8 * c)) & 0xffu;
-}
-
-// v[c] for a c that differs between lanes (selects, not an indexed array: no scratch)
-__device__ __forceinline__ float pick4(const float (&v)[4], int c) {
-    return c == 0 ? v[0] : c == 1 ? v[1] : c == 2 ? v[2] : v[3];
-}
-
-// One wave stores pixels oxw .. oxw + 63 (oxw a multiple of 64) of output row oy; every
-// lane of the wave calls it.  px(i) reads pixel oxw + i of that row from the result
-// tile in LDS, for any i below the row's end (not only the lane's own), which is how
-// the interleaved layout gets whole dwords without an exchange between lanes:
-// - CHW: per channel 64 consecutive elements of one plane row.  f32 is a dword per
-//   lane; f16 / bf16 pack two pixels into a dword through the right neighbour, even
-//   lanes store (single elements where the plane row is not 4-byte aligned and for a
-//   ragged last pixel);
-// - HWC: the segment is 64 * C consecutive elements, written as consecutive dwords,
-//   lane l taking dwords l, 64 + l, ...: it converts the one or two elements of its
-//   dword, whichever pixels they belong to.  Lanes that read the same pixel read the
-//   same LDS word (a broadcast), neighbours read neighbouring pixels, so the tile's
-//   pitch (1 or 65 dwords per pixel) keeps the banks apart as in store_row's read.
-//   Single elements per pixel where the row is not 4-byte aligned, and for an odd last one.
-template <int FMT, typename Load>
-__device__ __forceinline__ void store_tensor(const TensorDesc &td, int oy, int oxw, int lane, Load px) {
-    constexpr int C = (FMT & 1) ? 4 : 3;
-    const RenderDesc &d = td.s.r;
-    const int elem = td.elem;
-    const int nv = min(64, d.out_w - oxw);  // the segment's pixels (at least 1)
-    uint8_t *row = reinterpret_cast<uint8_t *>(d.out) + (int64_t)oy * td.stride_y;
-    if (td.layout == TENSOR_CHW) {
-        const bool valid = lane < nv;
-        const Px p = valid ? px(lane) : Px{0, 0};
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const uint32_t e = tensor_elem(px_channel<FMT>(p, c), td.a[c], td.b[c], elem);
-            uint8_t *pl = row + (int64_t)c * td.stride_c;
-            if (elem == TENSOR_F32) {
-                if (valid) reinterpret_cast<uint32_t *>(pl)[oxw + lane] = e;
-            } else {
-                const uint32_t nxt = __shfl_down(e, 1);
-                if (!(reinterpret_cast<uintptr_t>(pl) & 3) && (lane | 1) < nv) {
-                    if (!(lane & 1)) reinterpret_cast<uint32_t *>(pl)[(oxw + lane) >> 1] = e | (nxt << 16);
-                } else if (valid) {
-                    reinterpret_cast<uint16_t *>(pl)[oxw + lane] = (uint16_t)e;
-                }
-            }
-        }
-        return;
-    }
-    const int ne = nv * C;  // the segment's elements
-    auto element = [&](int k) {  // element k of the segment
-        const int i = k / C, c = k - i * C;
-        return tensor_elem(px_channel<FMT>(px(i), c), pick4(td.a, c), pick4(td.b, c), elem);
-    };
-    if (elem == TENSOR_F32) {
-        uint32_t *seg = reinterpret_cast<uint32_t *>(row) + (size_t)oxw * C;
-#pragma unroll
-        for (int j = 0; j < C; ++j) {
-            const int k = j * 64 + lane;
-            if (k < ne) seg[k] = element(k);
-        }
-    } else if (!(reinterpret_cast<uintptr_t>(row) & 3)) {  // (64 pixels are a multiple of 4 bytes)
-        uint16_t *seg = reinterpret_cast<uint16_t *>(row) + (size_t)oxw * C;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {  // 32 * C dwords
-            const int k = 2 * (j * 64 + lane);
-            if (k + 1 < ne) reinterpret_cast<uint32_t *>(seg)[k >> 1] = element(k) | (element(k + 1) << 16);
-            else if (k < ne) seg[k] = (uint16_t)element(k);
-        }
-    } else if (lane < nv) {
-        uint16_t *o = reinterpret_cast<uint16_t *>(row) + (size_t)(oxw + lane) * C;
-        const Px p = px(lane);
-#pragma unroll
-        for (int c = 0; c < C; ++c) o[c] = (uint16_t)tensor_elem(px_channel<FMT>(p, c), td.a[c], td.b[c], elem);
     }
 }
 

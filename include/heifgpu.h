@@ -315,7 +315,9 @@ int heifgpu_render_batch(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, siz
  * with no intermediate rounding (acc is a 64-bit sum).  ow == cw and oh == ch
  * gives the window of D byte for byte; integer ratios give the rounded mean of
  * each block; enlargement follows the same formula.  The average is taken over
- * converted pixels, not over the YCbCr planes. */
+ * converted pixels, not over the YCbCr planes.  (The area average is a box
+ * filter; heifgpu_render_batch_resampled, further down, offers Pillow's
+ * bilinear and bicubic filters on the same window.) */
 typedef struct {
     uint32_t out_width, out_height;   /* rendered size, each 1..65535 */
     uint32_t x, y, width, height;     /* window of the displayed picture, in its coordinates;
@@ -585,6 +587,92 @@ int heifgpu_batch_count_pictures(const heifgpu_image *const *imgs, size_t n, con
                                  const heifgpu_rect *src, uint32_t *pictures);
 /* the pictures of a prepared batch */
 int heifgpu_batch_picture_count(const heifgpu_batch *batch, uint32_t *pictures);
+
+/* ---- filtered render: Pillow-exact bilinear and bicubic ---------------------
+ * (added within ABI 6: new entry points only.)
+ * The scaled and tensor renders above resample by the area average, a box
+ * filter.  The calls below resample the same window of the same D (what
+ * heifgpu_render_batch writes) by Pillow's antialiased BILINEAR or BICUBIC
+ * instead: for the 8-bit formats every channel c of the result equals
+ *     PIL.Image.fromarray(D[..., c]).resize((ow, oh), BILINEAR | BICUBIC,
+ *                                           box=(cx, cy, cx + cw, cy + ch))
+ * bit for bit.  Per axis, Pillow's precompute_coeffs in IEEE binary64, in exactly
+ * this order of operations, with in_size D's side, [in0, in1 = in0 + c) the
+ * window, out the rendered side and S the filter's support (1 bilinear, 2 bicubic):
+ *     scale = (in1 - in0) / out;  fs = max(scale, 1.0);  support = S * fs;  ss = 1.0 / fs
+ *     for X in [0, out):
+ *       center = in0 + (X + 0.5) * scale
+ *       xmin = (int)(center - support + 0.5);  if xmin < 0: xmin = 0         (C truncation)
+ *       xmax = (int)(center + support + 0.5);  if xmax > in_size: xmax = in_size
+ *       w[t] = f((t + xmin - center + 0.5) * ss),  t in [0, xmax - xmin)
+ *       ww = w[0] + w[1] + ...                                              (left to right)
+ *       if ww != 0: w[t] = w[t] / ww                       (a division, not a reciprocal)
+ *       k[t] = (int)(w[t] * (1 << P) + (w[t] < 0 ? -0.5 : 0.5))
+ *     bilinear f(x): x = |x|;  x < 1 ? 1 - x : 0
+ *     bicubic  f(x): x = |x|, a = -0.5;  x < 1 ? ((a+2)*x - (a+3))*x*x + 1
+ *                                      : x < 2 ? (((x-5)*x + 8)*x - 4)*a : 0
+ * No product and sum of these is fused.  Taps reach beyond the window into D,
+ * as Pillow's box does, and stop at D's edges.  Two passes, horizontal first,
+ * which means along D's x whatever the irot:
+ *     T[y][X] = clip((2^(P-1) + sum_t k[t] * D[y][xmin + t]) >> P, 0, maxv)
+ * then the same rule along y over T (>> is an arithmetic shift, sums are int32).
+ * The rounding and the clip between the passes are part of the result.
+ * P = 32 - 2 - max(8, B), B the depth the format computes at: 22 at 8 bits
+ * (Pillow's PRECISION_BITS), 20 at 10, 18 at 12.  The 16-bit formats follow the
+ * same rule at their P; Pillow has no such mode, so they are pinned to
+ * tests/resample_ref.py only.  Alpha is a channel like the others, nothing is
+ * premultiplied (Image.resize on an RGBA image premultiplies; the per-channel
+ * statement above does not).  A colour transform acts on the rounded result, as
+ * for the area average; the tensor epilogue is unchanged.  A tensor's flip acts
+ * on the result R at the store: the coefficients are those of D's coordinates,
+ * never of mirrored ones.  Identity (ow == cw, oh == ch) gives the window of D
+ * byte for byte.  kernels/resample.hpp is the one statement of this in code,
+ * shared by the kernel and the two host hooks below.
+ * `filter` is one value per call.  HEIFGPU_FILTER_AREA forwards to the calls
+ * above (xf NULL or not) and gives their bytes; an unknown filter is
+ * HEIFGPU_E_INVALID, reported like every check before ctx is looked at.  xf may
+ * be NULL.  Everything else (checks, mixed batches, ONE launch, the descriptor
+ * ring) is as in heifgpu_render_batch_scaled / _tensor; a displayed side above
+ * 65535 is HEIFGPU_E_UNSUPPORTED.  Ratios of any size work: the kernel walks
+ * footprints in chunks and is tuned for the reductions a loader asks for. */
+enum { HEIFGPU_FILTER_AREA = 0, HEIFGPU_FILTER_BILINEAR = 1, HEIFGPU_FILTER_BICUBIC = 2 };
+int heifgpu_render_batch_resampled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                   const heifgpu_planes *in,
+                                   const heifgpu_image *const *alpha_imgs,
+                                   const heifgpu_planes *alpha_in,
+                                   uint32_t format, const heifgpu_scale *scale, uint32_t filter,
+                                   const heifgpu_color_transform *const *xf /* may be NULL */,
+                                   const heifgpu_surface *out, void *stream);
+int heifgpu_render_batch_tensor_resampled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                          const heifgpu_planes *in,
+                                          const heifgpu_image *const *alpha_imgs,
+                                          const heifgpu_planes *alpha_in,
+                                          const heifgpu_tensor_format *fmt, const heifgpu_scale *scale,
+                                          uint32_t filter, const uint32_t *flip,
+                                          const heifgpu_color_transform *const *xf /* may be NULL */,
+                                          const heifgpu_tensor_surface *out, void *stream);
+/* host only: one axis's coefficients at P = 32 - 2 - max(8, bits).  *ksize is
+ * Pillow's row length, (int)ceil(support) * 2 + 1, always set when the sizes are
+ * valid; bounds (2 * out_size: xmin, xmax - xmin per output) and kk (out_size
+ * rows of ksize, padded with zeros; cap = the entries kk holds) are filled when
+ * not NULL.  in_size and out_size 1..65535, 0 <= in0 < in1 <= in_size, filter
+ * BILINEAR or BICUBIC, bits 8..12, cap >= out_size * ksize: else HEIFGPU_E_INVALID. */
+int heifgpu_resample_coeffs(uint32_t in_size, uint32_t in0, uint32_t in1, uint32_t out_size, uint32_t filter,
+                            uint32_t bits, int32_t *bounds, int32_t *kk, size_t cap, uint32_t *ksize);
+/* host only: the two passes over in, in_height x in_width x channels (1..4)
+ * interleaved samples without padding, uint8 for bits == 8 and uint16 for bits
+ * 9..12 (a code above maxv is HEIFGPU_E_INVALID), window NULL or 0, 0 sized: the
+ * whole of it; out receives out_height x out_width x channels in the same layout. */
+int heifgpu_resample_apply(const void *in, uint32_t in_width, uint32_t in_height, uint32_t channels, uint32_t bits,
+                           const heifgpu_rect *window, uint32_t out_width, uint32_t out_height, uint32_t filter,
+                           void *out);
+/* host only: heifgpu_window_source_rect for a filtered render, the taps' halo
+ * included: per axis the window becomes [xmin(0), xmax(out - 1)) of the formula
+ * above, in D; that rectangle then goes through the display map, is grown to the
+ * chroma grid and clipped as heifgpu_window_source_rect does.  HEIFGPU_FILTER_AREA
+ * gives heifgpu_window_source_rect of the scale's window. */
+int heifgpu_window_source_rect_resampled(const heifgpu_image *img, const heifgpu_scale *scale, uint32_t filter,
+                                         heifgpu_rect *src);
 
 /* ---- host test hooks (reference unit-test surface) -------------------- */
 size_t heifgpu_remove_emulation_prevention(const uint8_t *in, size_t n, uint8_t *out); /* rbsp_reader.rs:11-39 */

@@ -51,7 +51,22 @@ each as `plain` and as `managed`.  With a library that has no colour entry
 points (HEIFGPU_LIBRARY naming the parent commit's build) only `plain` is
 measured: that is the A/B of the unmanaged kernels across the two commits.
 
-usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json] [--scaled | --tensor | --color]
+--filter measures the filtered render (heifgpu_render_batch_resampled, DESIGN
+5.27), same images, RGB8, COVER to 224 x 224 and to 512 x 384, rotation 0 and 3,
+the variants alternated in one process in each of the --runs runs:
+  full                  heifgpu_render_batch at full size
+  coverNNN_area         heifgpu_render_batch_scaled (the area average)
+  coverNNN_bilinear     heifgpu_render_batch_resampled, Pillow's BILINEAR
+  coverNNN_bicubic      the same, BICUBIC
+  coverNNN_torch        today's route to such pixels: `full`, a float copy and
+                        torch.nn.functional.interpolate(mode="bicubic", antialias=True),
+                        image by image
+The condition of 5.27: each filtered cell faster than its box's torch route by
+more than the larger spread (max - min over runs) of the two; the ratios to the
+area render and to `full` are reported, not gated.
+
+usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json]
+                                    [--scaled | --tensor | --color | --filter]
 """
 import argparse
 import ctypes
@@ -419,6 +434,107 @@ def color_main(args):
         pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
 
 
+def filter_main(args):
+    n = args.images
+    dev = torch.device("cuda", 0)
+    ctx = H.DecodeContext(0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    golden = (ROOT / "tests" / "golden" / "halfmoonbay.heic").read_bytes()
+    g = torch.Generator(device=dev).manual_seed(1)
+    ys = [torch.randint(0, 256, (HGT, W), generator=g, device=dev, dtype=torch.int32).to(torch.uint8) for _ in range(n)]
+    cs = [[torch.randint(0, 256, (HGT // 2, W // 2), generator=g, device=dev, dtype=torch.int32).to(torch.uint8)
+           for _ in range(n)] for _ in range(2)]
+    planes = (_lib.Planes * n)()
+    for i in range(n):
+        for c, t in enumerate((ys[i], cs[0][i], cs[1][i])):
+            planes[i].plane[c] = t.data_ptr()
+            planes[i].pitch[c] = t.stride(0) * t.element_size()
+    boxes = (("cover224", 224, 224), ("cover512", 512, 384))
+    filters = (("bilinear", _lib.FILTER_BILINEAR), ("bicubic", _lib.FILTER_BICUBIC))
+    result = {"images": n, "width": W, "height": HGT, "reps": args.reps, "runs": args.runs,
+              "device": torch.cuda.get_device_name(0), "rgb8": {}}
+    for rot in (0, 3):
+        img = H.HeifImage.parse(forced_rotation(golden, rot))
+        d = img.display
+        imgs = (ctypes.c_void_p * n)(*[img._h.value] * n)
+        full_out = [torch.empty((d.out_height, d.out_width, 3), dtype=torch.uint8, device=dev) for _ in range(n)]
+        full_surf = (_lib.Surface * n)()
+        for i, t in enumerate(full_out):
+            full_surf[i].pixels, full_surf[i].pitch = t.data_ptr(), t.stride(0)
+
+        def full():
+            _lib.check(_lib.lib.heifgpu_render_batch(ctx._h, imgs, n, planes, None, None, _lib.PIX_RGB8, full_surf, stream))
+
+        variants, keep = [("full", full)], []
+        for box, bw, bh in boxes:
+            sc = (_lib.Scale * n)()
+            for i in range(n):
+                _lib.check(_lib.lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_COVER, ctypes.byref(sc[i])))
+
+            def surfaces():
+                out = torch.empty((n, bh, bw, 3), dtype=torch.uint8, device=dev)
+                surf = (_lib.Surface * n)()
+                for i in range(n):
+                    surf[i].pixels, surf[i].pitch = out[i].data_ptr(), out[i].stride(0)
+                keep.append(out)
+                return out, surf
+
+            _, asurf = surfaces()
+
+            def area(sc=sc, surf=asurf):
+                _lib.check(_lib.lib.heifgpu_render_batch_scaled(ctx._h, imgs, n, planes, None, None, _lib.PIX_RGB8, sc, surf,
+                                                                stream))
+            variants.append((f"{box}_area", area))
+            for fname, code in filters:
+                _, fsurf = surfaces()
+
+                def filtered(sc=sc, surf=fsurf, code=code):
+                    _lib.check(_lib.lib.heifgpu_render_batch_resampled(ctx._h, imgs, n, planes, None, None, _lib.PIX_RGB8,
+                                                                       sc, code, None, surf, stream))
+                variants.append((f"{box}_{fname}", filtered))
+            small = torch.empty((n, 3, bh, bw), dtype=torch.float32, device=dev)
+            keep.append(small)
+
+            def torch_route(sc=sc, small=small, bw=bw, bh=bh):
+                # today's route to a bicubic picture: the full-size render, a float copy and an antialiased
+                # interpolation, image by image (the float copy of a whole batch would not fit)
+                full()
+                for i in range(n):
+                    s = sc[i]
+                    win = full_out[i][s.y:s.y + s.height, s.x:s.x + s.width].permute(2, 0, 1)[None].float()
+                    small[i] = torch.nn.functional.interpolate(win, size=(bh, bw), mode="bicubic", antialias=True)[0]
+            variants.append((f"{box}_torch", torch_route))
+        for _, fn in variants:  # warm-up
+            fn()
+        torch.cuda.synchronize()
+        ms = {name: [] for name, _ in variants}
+        for _ in range(args.runs):
+            for name, fn in variants:
+                ms[name].append(timed(fn, args.reps if not name.endswith("_torch") else max(1, args.reps // 10)))
+        r = {}
+        for name, _ in variants:
+            v = ms[name]
+            r[name] = {"ms_per_batch": round(statistics.median(v), 4), "ms_min": round(min(v), 4),
+                       "ms_max": round(max(v), 4), "ms_runs": [round(x, 4) for x in v],
+                       "spread_ms": round(max(v) - min(v), 4)}
+        for box, _, _ in boxes:
+            for fname, _ in filters:
+                c, route = r[f"{box}_{fname}"], r[f"{box}_torch"]
+                pair = max(c["spread_ms"], route["spread_ms"])
+                c["torch_minus_it_ms"] = round(route["ms_per_batch"] - c["ms_per_batch"], 4)
+                c["beats_torch_route_beyond_spread"] = bool(route["ms_per_batch"] - c["ms_per_batch"] > pair)
+                c["of_area"] = round(c["ms_per_batch"] / r[f"{box}_area"]["ms_per_batch"], 3)
+                c["of_full"] = round(c["ms_per_batch"] / r["full"]["ms_per_batch"], 3)
+        result["rgb8"][f"rotation_{rot}"] = r
+        print(f"rotation {rot}: " + ", ".join(f"{name} {r[name]['ms_per_batch']:.3f} ms (spread {r[name]['spread_ms']:.3f})"
+                                              for name, _ in variants), flush=True)
+        del full_out, keep, variants
+    print(json.dumps(result))
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=128)
@@ -428,7 +544,10 @@ def main():
     ap.add_argument("--scaled", action="store_true", help="measure heifgpu_render_batch_scaled (see above)")
     ap.add_argument("--tensor", action="store_true", help="measure heifgpu_render_batch_tensor (see above)")
     ap.add_argument("--color", action="store_true", help="measure the colour-managed render (see above)")
+    ap.add_argument("--filter", action="store_true", help="measure the bilinear / bicubic render (see above)")
     args = ap.parse_args()
+    if args.filter:
+        return filter_main(args)
     if args.color:
         return color_main(args)
     if args.scaled:
