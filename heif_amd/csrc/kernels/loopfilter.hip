@@ -3,7 +3,9 @@
 // Deblocking, H.265 8.7.2: transform/prediction edges on the 8x8 grid, bS = 2
 // for intra, beta'/tC' tables 8-12, luma strong/normal decisions (dE, dEp,
 // dEq), chroma filtered only for bS = 2 on the 8x8 chroma grid with
-// QpC = table 8-10((QpQ + QpP + 1) >> 1 + cQpPicOffset); samples of
+// QpC = table 8-10((QpQ + QpP + 1) >> 1 + cQpPicOffset) in 4:2:0 and
+// Min(that index, 51) in 4:2:2 / 4:4:4, bS, QpY and the no-filter flag per
+// chroma line from the 4x4 luma block of the flag map it lies in; samples of
 // cu_transquant_bypass CUs are left untouched.  All vertical edges of a
 // picture are filtered before any horizontal edge, and the edges of one
 // direction never share a modified sample, so each direction is one launch
