@@ -21,6 +21,7 @@
 // filtering, prediction and residual add run one sample per lane — and the
 // finished CTU is written to the picture once.
 #include "kernels.hpp"
+#include "intra_rec.hpp"
 #include "xform.hpp"
 #if defined(HG_HOST_EMU)
 #include <cstdio>
@@ -103,30 +104,22 @@ int intra_waves(int log2ctb, int chroma, int bps, int max_rows) {
 #endif
 
 
-// 6.4.1 availability of a neighbouring luma location (xl, yl) for a TB of the
-// CTU at luma (bx0, by0), size csl.  Everything in the CTU row above (up to the
-// above-right CTU, which the wavefront has finished) and in the CTU to the
-// left is decoded; the CTUs below-left and right are not; inside the CTU a
+// 6.4.1 availability of a neighbouring luma location (lx, ly), relative to the
+// origin of the TB's CTU of luma size csl.  Everything in the CTU row above (up
+// to the above-right CTU, which the wavefront has finished) and in the CTU to
+// the left is decoded; the CTUs below-left and right are not; inside the CTU a
 // block is available iff it precedes the TB in z-scan order (MinTbAddrZs of
 // 6.5.2 at 4x4 granularity: the CTU's quadtrees are decoded in z-order, so a
 // 4x4 block is decoded before the TB iff its z-index is below the z-index zc
 // of the TB's first luma 4x4 block).
-__device__ __forceinline__ int zidx(int bx, int by) {  // bits of bx, by interleaved (bx, by < 16)
-    auto spread = [](int v) {
-        v = (v | (v << 2)) & 0x33;
-        return (v | (v << 1)) & 0x55;
-    };
-    return spread(bx) | (spread(by) << 1);
-}
 // (r06 A/B: as one expression of bitwise ands / ors with the z-index always
 // formed, k_intra VALU +0.45 G for SALU -0.2 G, the step not better: the early
 // returns stay)
-__device__ __forceinline__ bool nb_avail(int zc, int xl, int yl, int bx0, int by0, int csl) {
-    const int lx = xl - bx0, ly = yl - by0;
+__device__ __forceinline__ bool nb_avail(int zc, int lx, int ly, int csl) {
     if (ly < 0) return true;
     if (ly >= csl || lx >= csl) return false;
     if (lx < 0) return true;
-    return zidx(lx >> 2, ly >> 2) < zc;
+    return tb_zidx(lx >> 2, ly >> 2) < zc;
 }
 
 // ref[k] of 8.4.4.2.6 read in place: the main-side neighbour for k >= 0, the
@@ -152,16 +145,29 @@ struct QuadT<uint16_t> {
 template <typename Pel>
 using Quad = typename QuadT<Pel>::type;
 
-// One component's CTU window in LDS.
+// One component's CTU window in LDS and its place in the picture (the CTU
+// write-back and the load of the row above; a TB works on a TbWin)
 template <typename Pel>
 struct Win {
     Pel *cur, *left, *above;
-    const int16_t *res;  // the component's residual plane (k_transform), or in streaming mode the
-                         // current TB's residual in LDS
+    int csx, csy;  // CTB width, height in component samples (4:2:2 chroma: csy = 2 csx)
+    int cx0, cy0;  // CTB origin in component samples
+};
+
+// What a TB's prediction reads of its component's window, in coordinates
+// relative to the CTB's origin (the record's word A holds the TB's position
+// that way): the window, the part of the CTB inside the picture, whether the
+// picture has samples left of and above the CTB, and the TB's residual.
+template <typename Pel>
+struct TbWin {
+    Pel *cur, *left, *above;
+    int lsx;             // log2 of the window's pitch (the component CTB's width)
+    int vw, vh;          // columns, rows from the CTB's origin to the picture's edge (component samples)
+    int minx, miny;      // -1 where the picture has a column left of / a row above the CTB, else 0
+    int csl;             // CTB size in luma samples
+    const int16_t *rt;   // the TB's first residual: in the component's residual plane (k_transform), or in
+                         // streaming mode the TB's residual tile in LDS
     int rp;              // residual pitch (the plane width; streaming mode: the TB width)
-    int rx0, ry0;        // the sample res[0] holds (plane: 0, 0; streaming: the TB's origin)
-    int csx, csy;        // CTB width, height in component samples (4:2:2 chroma: csy = 2 csx)
-    int cx0, cy0;        // CTB origin in component samples
 #if defined(HG_HOST_EMU)
     // emulation only: the LDS objects the pointers must stay inside (the r04
     // gain-map fault was a residual pointer moved before its LDS buffer, which
@@ -185,17 +191,10 @@ struct Win {
         }
     }
 #endif
-    // a decoded neighbour (xn, yn) in picture coordinates; only called for
-    // available samples, which lie in the row above, the column to the left
-    // or the current CTU
-    __device__ __forceinline__ int fetch(int xn, int yn) const {
-        const int lx = xn - cx0, ly = yn - cy0;
-#if defined(HG_HOST_EMU)
-        check_blk(ly < 0 ? above + lx + 1 : lx < 0 ? left + ly : cur + ly * csx + lx, sizeof(Pel));
-#endif
-        if (ly < 0) return above[lx + 1];
-        if (lx < 0) return left[ly];
-        return cur[ly * csx + lx];
+    // a decoded neighbour (lx, ly); only called for available samples, which lie
+    // in the row above, the column to the left or the current CTU
+    __device__ __forceinline__ const Pel *at(int lx, int ly) const {
+        return ly < 0 ? above + lx + 1 : (lx < 0 ? left + ly : cur + (ly << lsx) + lx);
     }
 };
 
@@ -240,57 +239,43 @@ struct Frame {
         w.cur = reinterpret_cast<Pel *>(blk + cur);
         w.left = reinterpret_cast<Pel *>(blk + left);
         w.above = reinterpret_cast<Pel *>(blk + above);
-        w.res = resid + plane_off(k);
-        w.rp = pw(k);
-        w.rx0 = w.ry0 = 0;
         w.csx = sx;
         w.csy = sy;
         w.cx0 = c * sx;
         w.cy0 = r * sy;
-#if defined(HG_HOST_EMU)
-        w.blk_lo = blk;
-        w.blk_hi = blk + kS0 + b0 + (CF ? 2 * b1 : 0u);
-#endif
         return w;
     }
 };
 
-// Facts of one TB record that depend on the record and the picture only:
-// formed for 64 records at once, one per lane, when the wave loads them (the
-// per-TB checks on the scalar unit were a large part of k_intra's scalar
-// instructions), read back with one v_readlane per TB.  Bit 0 (TBM_OK): the
-// TB is this wave's component (cidx in [k0, k1)), has a mode of 8.4.2, and
-// lies inside the picture and inside the window of CTB tu.ctu of row r (the
-// parse keeps it so; the check keeps the tables in range).  Bit 1 (TBM_PAIR,
-// set by the caller): a 4x4 / 8x8 Cb TB whose next record is its Cr TB.
-// Bits 8-15: zc, the z-order index of the TB's first luma 4x4 block in its
-// CTU (6.4.1 availability).
-// Bit 2 (TBM_FILT): the TB's neighbours are filtered (8.4.4.2.3: luma, or
-// chroma with 4:4:4; not DC, not 4x4; the mode farther from horizontal and
-// vertical than the size's threshold).  A second word per record (tb_angle)
-// holds intraPredAngle and invAngle (8.4.4.2.6), read by one vector load per
-// 64 records instead of two scalar loads from constant memory per TB.
-enum : uint32_t { TBM_OK = 1u, TBM_PAIR = 2u, TBM_FILT = 4u };
+// The byte offsets of the luma and of the Cb window parts in a wave's block
+// (Cr: Cb's + Frame::b1): constants of a CTB row, so a TB's window is a select
+// on cIdx and an add.
+struct WinOffs {
+    uint32_t cur[2], left[2], above[2];
+};
 template <typename Pel, int CF>
-__device__ __forceinline__ uint32_t tb_meta(const TuRec &q, const Frame<Pel, CF> &F, int r, int k0, int k1) {
-    const int k = q.flags & TU_CIDX_MASK, n = 1 << q.log2;
-    const int subx = k ? chroma_sx(CF) : 0, suby = k ? chroma_sy(CF) : 0;
-    const int lcx = F.log2ctb - subx, lcy = F.log2ctb - suby;
-    const int cx0 = (int)q.ctu << lcx, cy0 = r << lcy;
-    const int PW = k ? F.cw : F.W, PH = k ? F.ch : F.H;
-    const bool ok = k < (CF ? 3 : 1) && k >= k0 && k < k1 && q.mode <= 34 && q.log2 >= 2 && q.log2 <= 5 &&
-                    q.x + n <= PW && q.y + n <= PH && q.x >= cx0 && q.y >= cy0 && q.x + n <= cx0 + (1 << lcx) &&
-                    q.y + n <= cy0 + (1 << lcy);
-    const int zc = ok ? zidx((((int)q.x - cx0) << subx) >> 2, (((int)q.y - cy0) << suby) >> 2) : 0;
-    const int dist = min(abs((int)q.mode - 26), abs((int)q.mode - 10));
-    const int thr = n == 8 ? 7 : (n == 16 ? 1 : 0);
-    const bool filt = (k == 0 || CF == 3) && q.mode != 1 && n != 4 && dist > thr;
-    return (ok ? TBM_OK : 0u) | (filt ? TBM_FILT : 0u) | ((uint32_t)zc << 8);
+__device__ __forceinline__ WinOffs win_offs(const Frame<Pel, CF> &F) {
+    WinOffs o;
+    const uint32_t bps = sizeof(Pel);
+    const int l2 = F.log2ctb, lx = l2 - chroma_sx(CF), ly = l2 - chroma_sy(CF);
+    o.cur[0] = F.kS0;
+    o.left[0] = o.cur[0] + F.al16(bps << (2 * l2));
+    o.above[0] = o.left[0] + F.al16(bps << l2);
+    o.cur[1] = F.kS0 + F.b0;
+    o.left[1] = o.cur[1] + F.al16(bps << (lx + ly));
+    o.above[1] = o.left[1] + F.al16(bps << ly);
+    return o;
 }
-// intraPredAngle (low byte, signed) and invAngle (high half, signed) of a record's mode
-__device__ __forceinline__ uint32_t tb_angle(const TuRec &q) {
-    const int m = q.mode <= 34 ? q.mode : 0;
-    return (uint32_t)(uint8_t)c_angle[m] | ((uint32_t)(uint16_t)c_inv_angle[m] << 16);
+
+// The facts of a TB record that depend on the record and on constants of its
+// CTB row are formed for 64 records at once, one per lane, when the wave loads
+// them, as the packed words of intra_rec.hpp (the per-TB checks and field
+// extracts on the scalar unit were a large part of k_intra's instructions).
+// intraPredAngle and invAngle (8.4.4.2.6) of a mode, for word B: one vector
+// load per 64 records instead of two scalar loads from constant memory per TB.
+__device__ __forceinline__ uint32_t tb_word_b(uint32_t a, const TbGeom &g) {
+    const int m = (a & TBA_OK) ? tba_mode(a) : 0;
+    return tb_pack_b(a, g, c_angle[m], c_inv_angle[m]);
 }
 
 #if !defined(HG_HOST_EMU)
@@ -308,26 +293,29 @@ __device__ __forceinline__ int group_sum(int v, int m) {
 }
 #endif
 
+// One TB from its record's words A and B (intra_rec.hpp) and its component's window.
 template <typename Pel, int CF>
-__device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L, const TuRec &tu, const Win<Pel> &w,
-                                                                 int PW, int PH, int cidx, int bd, bool strong,
-                                                                 int zc, bool filt, uint32_t am, int lane) {
+__device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L, uint32_t wa, uint32_t wb,
+                                                                 const TbWin<Pel> &w, int bd, bool strong, int lane) {
     constexpr int chroma = CF;
-    const int log2n = tu.log2, n = 1 << log2n, mode = tu.mode;
-    const int x0 = tu.x, y0 = tu.y;
-    // component → luma coordinates (6.4.1 takes luma locations)
+    const int log2n = tba_log2(wa), n = 1 << log2n, mode = tba_mode(wa), cidx = tba_cidx(wa);
+    const int x0 = tba_lx(wa), y0 = tba_ly(wa);  // relative to the CTB's origin
+    const int zc = tbb_zc(wb);
+    const bool filt = (wa & TBA_FILT) != 0;
+    // component → luma coordinates (6.4.1 takes luma locations; a neighbour's may be -1, so a
+    // product, not a shift of a negative value)
     const int subx = cidx ? chroma_sx(chroma) : 0, suby = cidx ? chroma_sy(chroma) : 0;
-    const int bx0 = w.cx0 << subx, by0 = w.cy0 << suby, csl = w.csx << subx;
+    const int csl = w.csl;
     const int ns = 4 * n + 1;
-    const bool cbf = (tu.flags & TU_CBF) != 0;
+    const bool cbf = (wa & TBA_CBF) != 0;
     // residual of a 4x4 / 8x8 TB (one sample per lane): loaded now, used after
     // the neighbour and filter phases, so the load latency hides behind them
-    // (the TB's first residual, formed only where it is in bounds: a pointer moved
+    // (w.rt is the TB's first residual, formed by the caller only where it is in bounds: a pointer moved
     // before an LDS buffer is out of the object, and its flat address lost the aperture on the GPU)
-    const int16_t *rt = cbf ? w.res + ((ptrdiff_t)(y0 - w.ry0) * w.rp + (x0 - w.rx0)) : w.res;
+    const int16_t *rt = w.rt;
 #if defined(HG_HOST_EMU)
     if (cbf) w.check_res(rt, (size_t)(n - 1) * w.rp + n);
-    w.check_blk(w.cur + ((y0 - w.cy0) * w.csx + (x0 - w.cx0)), ((size_t)(n - 1) * w.csx + n) * sizeof(Pel));
+    w.check_blk(w.cur + ((y0 << w.lsx) + x0), ((size_t)((n - 1) << w.lsx) + n) * sizeof(Pel));
 #endif
     const int r0 = (cbf && n <= 8 && lane < n * n) ? rt[(lane >> log2n) * w.rp + (lane & (n - 1))] : 0;
 #if defined(HG_IABL_TB)  // measurement builds only (wrong pixels): the TB's work dropped
@@ -352,8 +340,9 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
                 xn = x0 + s - 2 * n - 1;
                 yn = y0 - 1;
             }
-            sa[s] = xn >= 0 && yn >= 0 && xn < PW && yn < PH && nb_avail(zc, xn << subx, yn << suby, bx0, by0, csl);
-            sv[s] = sa[s] ? w.fetch(xn, yn) : 0;
+            sa[s] = xn >= w.minx && yn >= w.miny && xn < w.vw && yn < w.vh && nb_avail(zc, xn * (1 << subx), yn * (1 << suby), csl);
+            if (sa[s]) w.check_blk(w.at(xn, yn), sizeof(Pel));
+            sv[s] = sa[s] ? (int)*w.at(xn, yn) : 0;
             any_av |= sa[s];
         }
         int first = -1;
@@ -374,16 +363,14 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
 #else
     if (ns <= 64) {  // 4x4 and 8x8 TBs (most of them): one chunk of 4n + 1 <= 33 samples
         const int s = lane;
-#if !defined(HG_INTRA_GATHER_R04)
         // every step formed for all lanes with selects (the branchy form
         // split the wave into three exec regions per step): the column left
         // of the TB bottom-up, the corner, the row above left to right
         const int xn = s <= 2 * n ? x0 - 1 : x0 + s - 2 * n - 1;
         const int yn = s < 2 * n ? y0 + 2 * n - 1 - s : y0 - 1;
-        const bool av = s < ns && xn >= 0 && yn >= 0 && xn < PW && yn < PH &&
-                        nb_avail(zc, xn << subx, yn << suby, bx0, by0, csl);
-        const int lx = xn - w.cx0, ly = yn - w.cy0;
-        const Pel *src = ly < 0 ? w.above + lx + 1 : (lx < 0 ? w.left + ly : w.cur + ly * w.csx + lx);
+        const bool av = s < ns && xn >= w.minx && yn >= w.miny && xn < w.vw && yn < w.vh &&
+                        nb_avail(zc, xn * (1 << subx), yn * (1 << suby), csl);
+        const Pel *src = w.at(xn, yn);
         const int val = (int)*(av ? src : w.cur);  // (an unavailable lane reads the window's first sample)
         const uint64_t msk = __ballot(av);
         const uint64_t below = msk & ((1ull << lane) - 1ull);
@@ -393,37 +380,6 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
         int16_t *dp = s < 2 * n ? L->left + (2 * n - s) : L->top + (s - 2 * n);
         if (s < ns) *dp = (int16_t)v;
         if (s == 2 * n) L->left[0] = (int16_t)v;
-#else
-        int xn, yn;
-        if (s < 2 * n) {
-            xn = x0 - 1;
-            yn = y0 + 2 * n - 1 - s;
-        } else if (s == 2 * n) {
-            xn = x0 - 1;
-            yn = y0 - 1;
-        } else {
-            xn = x0 + s - 2 * n - 1;
-            yn = y0 - 1;
-        }
-        const bool av = s < ns && xn >= 0 && yn >= 0 && xn < PW && yn < PH &&
-                        nb_avail(zc, xn << subx, yn << suby, bx0, by0, csl);
-        const int val = av ? w.fetch(xn, yn) : 0;
-        const uint64_t msk = __ballot(av);
-        int sl = lane;
-        if (!av && msk) {
-            const uint64_t below = msk & ((1ull << lane) - 1ull);
-            sl = below ? 63 - __clzll(below) : __ffsll((unsigned long long)msk) - 1;
-        }
-        const int sv = __shfl(val, sl, 64);
-        const int v = msk ? sv : (1 << (bd - 1));
-        if (s < 2 * n) L->left[2 * n - s] = (int16_t)v;
-        else if (s == 2 * n) {
-            L->left[0] = (int16_t)v;
-            L->top[0] = (int16_t)v;
-        } else if (s < ns) {
-            L->top[s - 2 * n] = (int16_t)v;
-        }
-#endif
     } else {
     // 16x16 (65 samples) needs two chunks, 32x32 (129) three
     const int nch = ns <= 128 ? 2 : 3;
@@ -434,10 +390,9 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
         const int s = lane + 64 * k;
         const int xn = s <= 2 * n ? x0 - 1 : x0 + s - 2 * n - 1;
         const int yn = s < 2 * n ? y0 + 2 * n - 1 - s : y0 - 1;
-        const bool av = s < ns && xn >= 0 && yn >= 0 && xn < PW && yn < PH &&
-                        nb_avail(zc, xn << subx, yn << suby, bx0, by0, csl);
-        const int lx = xn - w.cx0, ly = yn - w.cy0;
-        const Pel *src = ly < 0 ? w.above + lx + 1 : (lx < 0 ? w.left + ly : w.cur + ly * w.csx + lx);
+        const bool av = s < ns && xn >= w.minx && yn >= w.miny && xn < w.vw && yn < w.vh &&
+                        nb_avail(zc, xn * (1 << subx), yn * (1 << suby), csl);
+        const Pel *src = w.at(xn, yn);
         val[k] = av ? (int)*src : 0;
         msk[k] = __ballot(av);
     }
@@ -481,7 +436,7 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
     // 3. filtering (8.4.4.2.3): luma, and chroma with 4:4:4
     const int16_t *lf = L->left, *tp = L->top;
     {
-        if (filt) {  // (tb_meta: luma or 4:4:4 chroma, not DC, not 4x4, the mode past the threshold)
+        if (filt) {  // (word A: luma or 4:4:4 chroma, not DC, not 4x4, the mode past the threshold)
             const int c = L->left[0];
             const bool bi = strong && cidx == 0 && n == 32 && abs(c + L->top[64] - 2 * L->top[32]) < (1 << (bd - 5)) &&
                             abs(c + L->left[64] - 2 * L->left[32]) < (1 << (bd - 5));
@@ -522,7 +477,8 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
 #endif
         dc = (sum + n) >> (log2n + 1);
     }
-    const int lx0 = x0 - w.cx0, ly0 = y0 - w.cy0;
+    const int ang = tbb_ang(wb), inv = tbb_inv(wb);
+    const bool pcm = (wa & TBA_PCM) != 0;
     auto predict_sample = [&](int o) {
         const int x = o & (n - 1), y = o >> log2n;
         int pv;
@@ -539,7 +495,6 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
                 pv = (x == 0 || y == 0) ? e >> 2 : dc;
             }
         } else {
-            const int ang = (int)(int8_t)(am & 0xffu), inv = (int)(int16_t)(am >> 16);  // (tb_angle)
             const int16_t *main_ = mode >= 18 ? tp : lf, *side = mode >= 18 ? lf : tp;
             const int a = mode >= 18 ? x : y, b = mode >= 18 ? y : x;  // a along the main direction
             const int idx = ((b + 1) * ang) >> 5, fact = ((b + 1) * ang) & 31;
@@ -559,8 +514,8 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
                 }
             }
         }
-        const int li = (ly0 + y) * w.csx + lx0 + x;
-        if (tu.flags & TU_PCM) pv = 0;  // the residual is the PCM sample itself
+        const int li = ((y0 + y) << w.lsx) + x0 + x;
+        if (pcm) pv = 0;  // the residual is the PCM sample itself
         if (cbf) pv += (n <= 8 && o == lane) ? r0 : rt[y * w.rp + x];
         pv = min(max(pv, 0), maxv);
         w.cur[li] = (Pel)pv;
@@ -589,33 +544,31 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
 // reduction, and n * n <= 64 samples in two rounds of 32.  Scratch halves:
 // left / top at + 33 * h.
 template <typename Pel>
-__device__ __attribute__((always_inline)) inline void predict_pair(IntraScratch *L, const TuRec &tb, const TuRec &tr,
-                                                                   const Win<Pel> &wb, const Win<Pel> &wr, int PW,
-                                                                   int PH, int bd, int zc, uint32_t am, int lane) {
+__device__ __attribute__((always_inline)) inline void predict_pair(IntraScratch *L, uint32_t wa, uint32_t wb,
+                                                                   const TbWin<Pel> &wc, uint32_t dwin, uint32_t dres,
+                                                                   int bd, int lane) {
     // lanes 0-31 predict Cb and 32-63 Cr: the pairing needs a full 64-lane wave
     static_assert(kWave == 64, "predict_pair splits a 64-lane wave into two halves");
-    const int log2n = tb.log2, n = 1 << log2n, mode = tb.mode;
-    const int x0 = tb.x, y0 = tb.y;
+    const int log2n = tba_log2(wa), n = 1 << log2n, mode = tba_mode(wa);
+    const int x0 = tba_lx(wa), y0 = tba_ly(wa);  // relative to the CTB's origin
+    const int zc = tbb_zc(wb);
     const int h = lane >> 5, sl = lane & 31;
-    // per-field selects (a lane-dependent reference into the caller's win[] would put it in scratch)
-    Win<Pel> w;
-    w.cur = h ? wr.cur : wb.cur;
-    w.left = h ? wr.left : wb.left;
-    w.above = h ? wr.above : wb.above;
-    w.res = h ? wr.res : wb.res;
-    w.rp = wb.rp;
-    w.csx = wb.csx;
-    w.csy = wb.csy;
-    w.cx0 = wb.cx0;
-    w.cy0 = wb.cy0;
-    const bool cbf = ((h ? tr.flags : tb.flags) & TU_CBF) != 0;
-    const bool pcm = ((h ? tr.flags : tb.flags) & TU_PCM) != 0;
-    const int bx0 = w.cx0 << 1, by0 = w.cy0 << 1, csl = w.csx << 1;
+    // wc is the Cb window; Cr's lies dwin samples behind it, its residual dres elements behind Cb's
+    // (a per-lane offset: a lane-dependent reference into an array of windows would put it in scratch)
+    TbWin<Pel> w = wc;
+    const uint32_t dw = h ? dwin : 0u;
+    w.cur = wc.cur + dw;
+    w.left = wc.left + dw;
+    w.above = wc.above + dw;
+    const int16_t *rt = wc.rt + (h ? dres : 0u);
+    const bool cbf = (wa & (h ? TBA_CBF2 : TBA_CBF)) != 0;
+    const bool pcm = (wa & (h ? TBA_PCM2 : TBA_PCM)) != 0;
+    const int csl = w.csl;
     const int ns = 4 * n + 1, nch = n == 8 ? 2 : 1;
     // residuals (sample sl and sl + 32 of this half), used after the neighbour phase
     int r0 = 0, r1 = 0;
-    if (cbf && sl < n * n) r0 = w.res[(ptrdiff_t)(y0 + (sl >> log2n)) * w.rp + x0 + (sl & (n - 1))];
-    if (cbf && sl + 32 < n * n) r1 = w.res[(ptrdiff_t)(y0 + ((sl + 32) >> log2n)) * w.rp + x0 + ((sl + 32) & (n - 1))];
+    if (cbf && sl < n * n) r0 = rt[(sl >> log2n) * w.rp + (sl & (n - 1))];
+    if (cbf && sl + 32 < n * n) r1 = rt[((sl + 32) >> log2n) * w.rp + ((sl + 32) & (n - 1))];
     int16_t *left = L->left + 33 * h, *top = L->top + 33 * h;
     // 1. neighbours in search order (8.4.4.2.2), chunk k = search positions sl + 32 k
     // (two named registers, not arrays: indexed by a runtime chunk they went to scratch)
@@ -628,10 +581,9 @@ __device__ __attribute__((always_inline)) inline void predict_pair(IntraScratch 
         // (positions and the source by selects, as predict_tb's one-chunk path)
         const int xn = s <= 2 * n ? x0 - 1 : x0 + s - 2 * n - 1;
         const int yn = s < 2 * n ? y0 + 2 * n - 1 - s : y0 - 1;
-        const bool av = s < ns && xn >= 0 && yn >= 0 && xn < PW && yn < PH &&
-                        nb_avail(zc, xn << 1, yn << 1, bx0, by0, csl);
-        const int lx = xn - w.cx0, ly = yn - w.cy0;
-        const Pel *srcp = ly < 0 ? w.above + lx + 1 : (lx < 0 ? w.left + ly : w.cur + ly * w.csx + lx);
+        const bool av = s < ns && xn >= w.minx && yn >= w.miny && xn < w.vw && yn < w.vh &&
+                        nb_avail(zc, xn * 2, yn * 2, csl);
+        const Pel *srcp = w.at(xn, yn);
         const int vk = av ? (int)*srcp : 0;
         const uint32_t hk = (uint32_t)(__ballot(av) >> (32 * h));
         if (k == 0) {
@@ -673,14 +625,13 @@ __device__ __attribute__((always_inline)) inline void predict_pair(IntraScratch 
     const int16_t *lf = left, *tp = top;
     const int maxv = (1 << bd) - 1;
     int dc = 0;
-    const int ang = (int)(int8_t)(am & 0xffu), inv = (int)(int16_t)(am >> 16);  // (tb_angle)
+    const int ang = tbb_ang(wb), inv = tbb_inv(wb);
     const int16_t *main_ = mode >= 18 ? tp : lf, *side = mode >= 18 ? lf : tp;
     if (mode == 1) {  // each half sums its 2n <= 16 references in its lanes 0 .. 2n - 1
         const int sum = group_sum(sl < 2 * n ? (sl < n ? tp[1 + sl] : lf[1 + sl - n]) : 0, 2 * n);
         const int s0 = __builtin_amdgcn_readlane(sum, 0), s1 = __builtin_amdgcn_readlane(sum, 32);
         dc = ((h ? s1 : s0) + n) >> (log2n + 1);
     }
-    const int lx0 = x0 - w.cx0, ly0 = y0 - w.cy0;
     for (int it = 0; it < nch; ++it) {
         const int o = sl + 32 * it;
         if (o < n * n) {
@@ -701,7 +652,7 @@ __device__ __attribute__((always_inline)) inline void predict_pair(IntraScratch 
             if (pcm) pv = 0;  // the residual is the PCM sample itself
             if (cbf) pv += it ? r1 : r0;
             pv = min(max(pv, 0), maxv);
-            w.cur[(ly0 + y) * w.csx + lx0 + x] = (Pel)pv;
+            w.cur[((y0 + y) << w.lsx) + x0 + x] = (Pel)pv;
         }
     }
     wave_sync();
@@ -734,6 +685,41 @@ constexpr size_t kXfDBytes = 32 * kXfDStride32 * sizeof(int16_t), kXfGBytes = 32
 constexpr size_t kXfWaveBytes = kXfDBytes + kXfGBytes + 16;
 static_assert(kXfTablesBytes % 16 == 0 && kXfWaveBytes % 16 == 0, "transform scratch alignment");
 constexpr int kIntraPlanes = 0, kIntraStream = 1;
+
+// One word per record of a wave's 64-record block, lane l holding record
+// base + l's: read back for the TB at hand with one v_readlane (the emulation's
+// single lane holds all 64).
+#if defined(HG_HOST_EMU)
+struct LaneWord {
+    uint32_t v[64];
+    uint32_t at(int l) const { return v[l]; }
+};
+// The block walk's events, counted by the emulation (HEIFGPU_INTRA_STATS=1: emu_intra
+// prints them on an `intra_walk` line): what tests/test_intra_walk.py asserts its pictures reach.
+struct WalkStats {
+    std::atomic<uint64_t> records{0}, ok{0}, pairs{0}, ctus{0}, blocks{0};
+    std::atomic<uint64_t> pair_splits{0};    // a Cb TB in lane 63 whose Cr TB opens the next block
+    std::atomic<uint64_t> ctu_lane0{0};      // a CTU start at lane 0 of a block after the row's first
+    std::atomic<uint64_t> blocks_no_ctu{0};  // a block without a CTU start
+    std::atomic<uint64_t> rows_lt64{0}, rows_gt128{0};
+    std::atomic<uint64_t> second_rows{0};    // a row that is not its wave's first
+    // TBs predicted: 32x32 luma with filtered neighbours under strong smoothing, 4x4 luma, PCM
+    std::atomic<uint64_t> tb32_strong{0}, luma4{0}, pcm{0};
+};
+static WalkStats g_walk;
+static bool walk_stats_on() {
+    static const bool on = [] {
+        const char *e = std::getenv("HEIFGPU_INTRA_STATS");
+        return e && std::atoi(e) != 0;
+    }();
+    return on;
+}
+#else
+struct LaneWord {
+    uint32_t v = 0;
+    __device__ __forceinline__ uint32_t at(int l) const { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+};
+#endif
 constexpr uint32_t kGaveUp = ~0u;                 // a wave's progress word: it gave its rows up
 constexpr uint64_t kRedoPatience = 200000000ull;  // 2 s (10 ns ticks): the parse is over by then
 
@@ -793,6 +779,16 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
     const int prev_wave = split ? ((rw + nrw - 1) % nrw) * 2 + cls : (wave + nw - 1) % nw;
     const bool wpp = (sp.flags & SP_WPP) != 0;
     bool gave_up = false;  // (streaming, first launch: no parse progress for a while)
+    const TbGeom G{log2ctb, chroma, W, H, cw, ch};
+    const WinOffs wo = win_offs(F);  // constants of the picture: a TB's window is a select on cIdx and an add
+    constexpr int SX = chroma_sx(CF), SY = chroma_sy(CF);
+    const uint32_t dwin = F.b1 / (uint32_t)sizeof(Pel);  // from a Cb window part to Cr's, samples
+    const uint32_t dres = (uint32_t)cw * (uint32_t)ch;   // from a Cb residual to Cr's, elements
+#if defined(HG_HOST_EMU)
+    // (split: the records and the walk's events by the luma wave, the pairs by the chroma wave)
+    const bool stats = walk_stats_on() && cls == 0 && !(Poll && a.stream_redo);
+    const bool stats_c = walk_stats_on() && k0 <= 1 && k1 > 1;
+#endif
     for (int r = rw; r < hctb; r += nrw) {
         // streaming: TUs [0, ntu) of the row are known written; `done` once the parse finished the row
         uint32_t ntu = Poll ? 0u : a.row_counts[2 * (pd.row_off + r)];
@@ -800,13 +796,76 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
         const TuRec *tus = a.tus + pd.tu_off + (uint64_t)r * pd.tu_cap_row;
         const CoefSrc<Poll> coefs{a.coefs + pd.coef_off + (uint64_t)r * pd.coef_cap_row};
         int cur = -1;
-#if !defined(HG_HOST_EMU)
-        uint4 tblk = make_uint4(0, 0, 0, 0);  // lane l: TuRec t0 + l (one coalesced load per 64 TBs)
-        uint32_t metav = 0, anglev = 0;       // lane l: tb_meta and tb_angle of that record
-        uint32_t t0 = 0;
+        // finish CTU `cur`: write the window back, keep its last column as `left`
+        auto finish_ctu = [&]() {
+            _Pragma("nounroll") for (int k = 0; k < 3; ++k) {
+                if (k >= ncomp) break;
+                if (k < k0 || k >= k1) continue;
+                const Win<Pel> w = F.win(k, cur, r);
+                Pel *const plane = F.plane(k);
+                const int PW = F.pw(k), PH = F.ph(k);
+                const int vw = min(w.csx, PW - w.cx0), vh = min(w.csy, PH - w.cy0);
+                if (vw == w.csx && !(PW & 3) && !(reinterpret_cast<uintptr_t>(plane) & (4 * sizeof(Pel) - 1))) {
+                    // full-width CTU: four samples per lane, one 4- (8-) byte store
+                    const int lq = __builtin_ctz((unsigned)w.csx) - 2;
+                    for (int o = lane; o < (vh << lq); o += kWave) {
+                        const int x = (o & ((1 << lq) - 1)) << 2, y = o >> lq;
+                        *reinterpret_cast<Quad<Pel> *>(plane + (size_t)(w.cy0 + y) * PW + w.cx0 + x) =
+                            *reinterpret_cast<const Quad<Pel> *>(w.cur + y * w.csx + x);
+                    }
+                } else {
+                    for (int o = lane; o < vw * vh; o += kWave) {
+                        const int x = o % vw, y = o / vw;
+                        plane[(size_t)(w.cy0 + y) * PW + w.cx0 + x] = w.cur[y * w.csx + x];
+                    }
+                }
+                for (int y = lane; y < w.csy; y += kWave) w.left[y] = w.cur[y * w.csx + w.csx - 1];
+            }
+            wave_sync();
+            HG_FENCE_REL();
+            hg_atomic_store(&progress[wave], (uint32_t)r * stride + (uint32_t)cur + 1u);
+        };
+        // start CTU c (after the row above has finished CTU c + 1): the row above, corner .. above-right;
+        // false: the row above was given up
+        auto start_ctu = [&](int c) -> bool {
+            if (r > 0) {
+                const uint32_t need = (uint32_t)(r - 1) * stride + (uint32_t)min(c + 2, wctb);
+                for (uint32_t spin = 0;; ++spin) {
+                    const uint32_t v = (uint32_t)HG_UNI(hg_atomic_load(&progress[prev_wave]));
+                    if (Poll && v == kGaveUp) return false;  // the row above was given up: so is this one
+                    if (v >= need) break;
+                    if (spin > (1u << 24)) {  // bounded: never hang the device
+                        if (lane == 0) atomicOr(&a.status[pic], ST_SUBSTREAM_END);
+                        break;
+                    }
+                    HG_SLEEP();
+                }
+                HG_FENCE_ACQ();
+            }
+            _Pragma("nounroll") for (int k = 0; k < 3; ++k) {
+                if (k >= ncomp) break;
+                if (k < k0 || k >= k1) continue;
+                const Win<Pel> w = F.win(k, c, r);
+                const Pel *const plane = F.plane(k);
+                const int PW = F.pw(k);
+                const int yg = w.cy0 - 1;
+                for (int i = lane; i <= 2 * w.csx; i += kWave) {
+                    const int xg = w.cx0 - 1 + i;
+                    w.above[i] = (yg >= 0 && xg >= 0 && xg < PW) ? plane[(size_t)yg * PW + xg] : (Pel)0;
+                }
+            }
+            wave_sync();
+            return true;
+        };
+#if defined(HG_HOST_EMU)
+        if (stats) {
+            g_walk.rows_lt64 += ntu < 64 && !Poll;
+            g_walk.rows_gt128 += ntu > 128 && !Poll;
+            g_walk.second_rows += r != rw;
+        }
 #endif
-        for (uint32_t t = 0;; ++t) {
-            bool reload = false;
+        bool stop = false;  // a record names a CTU outside the row: the row ends there
+        for (uint32_t t = 0; !stop;) {  // t: the row's first record not consumed yet
             if constexpr (Poll) {
                 if (t >= ntu && !row_done) {
                     // wait until the parse has published TU t of this row or finished the row
@@ -856,168 +915,206 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
                     // the records behind the count / progress word: formally ordered
                     // after the poll (the parse published them with an agent release)
                     HG_ACQ_AGENT();
-                    reload = true;
                 }
             }
-            if (t > ntu || (t == ntu && !row_done)) break;  // (stalled: the status says so)
-            TuRec tu{};
-            int c = wctb;  // sentinel after the last TB: finish the open CTU
-            if (t < ntu) {
+            if (t >= ntu) break;  // the row's last record is consumed (or the parse stalled: the status says so)
+            // ---- the block of up to 64 records that holds record t, one per lane: the packed
+            // words (intra_rec.hpp) and the two masks the walk below follows
+            const uint32_t base = t & ~63u;
+            LaneWord wa, wb, wc, wctu;
+#if !defined(HG_HOST_EMU)
+            uint4 tblk = make_uint4(0, 0, 0, 0);  // (streaming: the record itself, for transform_tb)
+#endif
+            // lane l's words of record base + l (zero where the block has no such record yet)
+            auto form = [&](int l, uint32_t &A, uint32_t &B, uint32_t &C, uint32_t &ctu) {
+                A = B = C = ctu = 0;
+                const uint32_t i = base + (uint32_t)l;
+                if (i < t || i >= ntu) return;
+                TuRec q;
 #if defined(HG_HOST_EMU)
-                tu = tus[t];
-                (void)reload;
+                q = tus[i];
 #else
-                if ((t & 63u) == 0 || reload) {
-                    t0 = t & ~63u;
-                    const uint32_t i = t0 + (uint32_t)lane;
-                    if constexpr (Poll) {
-                        const uint64_t *q = reinterpret_cast<const uint64_t *>(tus + i);
-                        const uint64_t lo = i < ntu ? __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-                        const uint64_t hi = i < ntu ? __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-                        tblk = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
-                    } else {
-                        tblk = i < ntu ? *reinterpret_cast<const uint4 *>(tus + i) : make_uint4(0, 0, 0, 0);
-                    }
-                    TuRec q;
-                    __builtin_memcpy(&q, &tblk, sizeof(q));
-                    metav = i < ntu ? tb_meta(q, F, r, k0, k1) : 0u;
-                    anglev = tb_angle(q);
+                if constexpr (Poll) {
+                    const uint64_t *p = reinterpret_cast<const uint64_t *>(tus + i);
+                    const uint64_t lo = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const uint64_t hi = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    tblk = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+                } else {
+                    tblk = *reinterpret_cast<const uint4 *>(tus + i);
+                }
+                __builtin_memcpy(&q, &tblk, sizeof(q));
+#endif
+                ctu = q.ctu;
+                A = tb_pack_a(q, G, r);
+                bool fits = true;
+                C = tb_pack_c(q, A, G, &fits);
+                if (!fits) A = C = 0;
 #if !defined(HG_INTRA_NO_PAIR)
-                    if constexpr (!XfInline && CF == 1) {
-                        // the next record (lane + 1; none past this block): its Cr TB?
-                        const int nl = min(lane + 1, 63);
-                        const uint4 nb = make_uint4((uint32_t)__shfl((int)tblk.x, nl, 64), (uint32_t)__shfl((int)tblk.y, nl, 64),
-                                                    (uint32_t)__shfl((int)tblk.z, nl, 64), (uint32_t)__shfl((int)tblk.w, nl, 64));
+                if constexpr (!XfInline && CF == 1) {
+                    // a 4x4 / 8x8 Cb TB whose next record is its Cr TB (same TU): both in one pass,
+                    // unless the Cr record opens the next block (a pair never spans two blocks)
+                    if ((A & TBA_OK) && tba_cidx(A) == 1 && tba_log2(A) <= 3 && i + 1 < ntu) {
                         TuRec nq;
+#if defined(HG_HOST_EMU)
+                        nq = tus[i + 1];
+#else
+                        const uint4 nb = *reinterpret_cast<const uint4 *>(tus + i + 1);
                         __builtin_memcpy(&nq, &nb, sizeof(nq));
-                        const bool pair = (metav & TBM_OK) && lane < 63 && i + 1 < ntu && (q.flags & TU_CIDX_MASK) == 1 &&
-                                          q.log2 <= 3 && (nq.flags & TU_CIDX_MASK) == 2 && nq.x == q.x && nq.y == q.y &&
-                                          nq.log2 == q.log2 && nq.mode == q.mode && nq.ctu == q.ctu;
-                        metav |= pair ? TBM_PAIR : 0u;
-                    }
 #endif
-                }
-                const int sel = (int)(t - t0);
-                const uint4 r = make_uint4((uint32_t)__builtin_amdgcn_readlane((int)tblk.x, sel),
-                                           (uint32_t)__builtin_amdgcn_readlane((int)tblk.y, sel),
-                                           (uint32_t)__builtin_amdgcn_readlane((int)tblk.z, sel),
-                                           (uint32_t)__builtin_amdgcn_readlane((int)tblk.w, sel));
-                __builtin_memcpy(&tu, &r, sizeof(tu));
-#endif
-                c = (int)HG_UNI((uint32_t)tu.ctu);
-            }
-            if (c != cur) {
-                if (cur >= 0) {
-                    // finish CTU `cur`: write the window back, keep its last column as `left`
-                    _Pragma("nounroll") for (int k = 0; k < 3; ++k) {
-                        if (k >= ncomp) break;
-                        if (k < k0 || k >= k1) continue;
-                        const Win<Pel> w = F.win(k, cur, r);
-                        Pel *const plane = F.plane(k);
-                        const int PW = F.pw(k), PH = F.ph(k);
-                        const int vw = min(w.csx, PW - w.cx0), vh = min(w.csy, PH - w.cy0);
-                        if (vw == w.csx && !(PW & 3) &&
-                            !(reinterpret_cast<uintptr_t>(plane) & (4 * sizeof(Pel) - 1))) {
-                            // full-width CTU: four samples per lane, one 4- (8-) byte store
-                            const int lq = __builtin_ctz((unsigned)w.csx) - 2;
-                            for (int o = lane; o < (vh << lq); o += kWave) {
-                                const int x = (o & ((1 << lq) - 1)) << 2, y = o >> lq;
-                                *reinterpret_cast<Quad<Pel> *>(plane + (size_t)(w.cy0 + y) * PW + w.cx0 + x) =
-                                    *reinterpret_cast<const Quad<Pel> *>(w.cur + y * w.csx + x);
-                            }
-                        } else {
-                            for (int o = lane; o < vw * vh; o += kWave) {
-                                const int x = o % vw, y = o / vw;
-                                plane[(size_t)(w.cy0 + y) * PW + w.cx0 + x] = w.cur[y * w.csx + x];
-                            }
-                        }
-                        for (int y = lane; y < w.csy; y += kWave) w.left[y] = w.cur[y * w.csx + w.csx - 1];
-                    }
-                    wave_sync();
-                    HG_FENCE_REL();
-                    hg_atomic_store(&progress[wave], (uint32_t)r * stride + (uint32_t)cur + 1u);
-                }
-                if (c >= wctb) break;
-                cur = c;
-                if (r > 0) {
-                    const uint32_t need = (uint32_t)(r - 1) * stride + (uint32_t)min(c + 2, wctb);
-                    for (uint32_t spin = 0;; ++spin) {
-                        const uint32_t v = (uint32_t)HG_UNI(hg_atomic_load(&progress[prev_wave]));
-                        if (Poll && v == kGaveUp) {  // the row above was given up: so is this one
-                            gave_up = true;
-                            break;
-                        }
-                        if (v >= need) break;
-                        if (spin > (1u << 24)) {  // bounded: never hang the device
-                            if (lane == 0) atomicOr(&a.status[pic], ST_SUBSTREAM_END);
-                            break;
-                        }
-                        HG_SLEEP();
-                    }
-                    if (gave_up) break;
-                    HG_FENCE_ACQ();
-                }
-                // start CTU c: the row above (corner .. above-right) and the residuals
-                _Pragma("nounroll") for (int k = 0; k < 3; ++k) {
-                    if (k >= ncomp) break;
-                    if (k < k0 || k >= k1) continue;
-                    const Win<Pel> w = F.win(k, c, r);
-                    const Pel *const plane = F.plane(k);
-                    const int PW = F.pw(k);
-                    const int yg = w.cy0 - 1;
-                    for (int i = lane; i <= 2 * w.csx; i += kWave) {
-                        const int xg = w.cx0 - 1 + i;
-                        w.above[i] = (yg >= 0 && xg >= 0 && xg < PW) ? plane[(size_t)yg * PW + xg] : (Pel)0;
-                    }
-                }
-                wave_sync();
-            }
-            // this wave's component, a valid TB of CTB `cur` (tb_meta): its facts for 64 records
-            // were formed at the block load
+                        const bool cr = (nq.flags & TU_CIDX_MASK) == 2 && nq.x == q.x && nq.y == q.y &&
+                                        nq.log2 == q.log2 && nq.mode == q.mode && nq.ctu == q.ctu;
+                        if (cr && l < 63) A = tb_pack_pair(A, nq.flags);
 #if defined(HG_HOST_EMU)
-            const uint32_t m = tb_meta(tu, F, r, k0, k1);
+                        if (stats_c) g_walk.pairs += cr && l < 63, g_walk.pair_splits += cr && l == 63;
+#endif
+                    }
+                }
+#endif
+                B = tb_word_b(A, G);
+            };
+            // a record is this wave's where it is OK, of the wave's components, and not the Cr TB of a
+            // pair; it opens a CTU where its CTU is not the record's before it (the first one: not `cur`)
+            auto is_mine = [&](uint32_t A, uint32_t prevA) {
+                const int k = tba_cidx(A);
+                return (A & TBA_OK) && k >= k0 && k < k1 && !(prevA & TBA_PAIR);
+            };
+            uint64_t mine_m, nctu_m;
+#if defined(HG_HOST_EMU)
+            mine_m = nctu_m = 0;
+            {
+                uint32_t prevA = 0, prevc = (uint32_t)cur;
+                for (int l = 0; l < 64; ++l) {
+                    form(l, wa.v[l], wb.v[l], wc.v[l], wctu.v[l]);
+                    const uint32_t i = base + (uint32_t)l;
+                    const bool valid = i >= t && i < ntu;
+                    if (valid && is_mine(wa.v[l], prevA)) mine_m |= 1ull << l;
+                    if (valid && wctu.v[l] != prevc) nctu_m |= 1ull << l;
+                    if (valid) prevA = wa.v[l], prevc = wctu.v[l];
+                }
+            }
+            if (stats) {
+                g_walk.blocks += 1;
+                g_walk.blocks_no_ctu += nctu_m == 0;
+                g_walk.ctu_lane0 += base > 0 && (nctu_m & 1ull);
+                g_walk.ctus += (uint64_t)__builtin_popcountll(nctu_m);
+                for (int l = 0; l < 64; ++l) {
+                    const uint32_t i = base + (uint32_t)l;
+                    if (i < t || i >= ntu) continue;
+                    g_walk.records += 1;
+                    g_walk.ok += (wa.v[l] & TBA_OK) != 0;
+                }
+            }
 #else
-            const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)metav, (int)(t - t0));
+            {
+                form(lane, wa.v, wb.v, wc.v, wctu.v);
+                const uint32_t i = base + (uint32_t)lane;
+                const bool valid = i >= t && i < ntu;
+                const int pl = max(lane - 1, 0);
+                const uint32_t pA = (uint32_t)__shfl((int)wa.v, pl, 64), pc = (uint32_t)__shfl((int)wctu.v, pl, 64);
+                const uint32_t prevA = lane == 0 ? 0u : pA;  // (a lane before record t holds zero words)
+                const uint32_t prevc = (i == t) ? (uint32_t)cur : pc;
+                mine_m = __ballot(valid && is_mine(wa.v, prevA));
+                nctu_m = __ballot(valid && wctu.v != prevc);
+            }
 #endif
-            if (!(m & TBM_OK)) continue;
-#if defined(HG_HOST_EMU)
-            const uint32_t am = tb_angle(tu);
-#else
-            const uint32_t am = (uint32_t)__builtin_amdgcn_readlane((int)anglev, (int)(t - t0));
-#endif
-            const int cidx = tu.flags & TU_CIDX_MASK, zc = (int)((m >> 8) & 0xffu);
-            // the TB's component window, formed here from the wave-uniform cidx and CTU
-            Win<Pel> w = F.win(cidx, cur, r);
-            const int PW = cidx ? cw : W, PH = cidx ? ch : H;
-            if constexpr (XfInline) {
-                // the TB's residual, transformed by this wave into LDS (pitch n, origin the TB's)
-                if (tu.flags & TU_CBF) {
-                    const int n = 1 << tu.log2;
-                    transform_tb<Poll>(tu, coefs, sp, a.sf, X, X.d, n, lane);
-                    w.res = X.d;
-                    w.rp = n;
-                    w.rx0 = tu.x;
-                    w.ry0 = tu.y;
-#if defined(HG_HOST_EMU)
-                    w.res_lo = X.d;
-                    w.res_hi = X.d + 32 * 32;  // (the 2 KB residual tile of XfScratch)
-#endif
+            // ---- the walk: TBs at the set bits of mine_m, CTU finish / start at those of nctu_m
+            // (the two masks are the loop's state, their lowest bits cleared as the walk passes them:
+            // a third mask of both would be two more live SGPRs)
+            while (mine_m | nctu_m) {
+                const int l = __builtin_ctzll(mine_m | nctu_m);
+                const uint64_t bit = 1ull << l;
+                const bool tb = (mine_m & bit) != 0;
+                mine_m &= ~bit;
+                if (nctu_m & bit) {
+                    nctu_m &= ~bit;
+                    const int c = (int)wctu.at(l);
+                    if (cur >= 0) finish_ctu();
+                    cur = -1;
+                    if (c >= wctb) {
+                        stop = true;
+                        break;
+                    }
+                    if (!start_ctu(c)) {
+                        gave_up = true;
+                        break;
+                    }
+                    cur = c;
                 }
-            }
-#if !defined(HG_HOST_EMU) && !defined(HG_INTRA_NO_PAIR)
-            // a 4x4 / 8x8 Cb TB followed by its Cr TB (same TU; the next record of this 64-record block):
-            // both in one pass
-            if (!XfInline && (m & TBM_PAIR)) {  // (the next record is its Cr TB: tb_meta)
-                TuRec tr = tu;  // same position, size, mode and CTU; the flags are the Cr TB's
-                tr.flags = (uint8_t)((uint32_t)__builtin_amdgcn_readlane((int)tblk.y, (int)(t + 1 - t0)) >> 8);
-                predict_pair<Pel>(S, tu, tr, F.win(1, cur, r), F.win(2, cur, r), PW, PH, sp.bit_depth_c, zc, am, lane);
-                ++t;
-                continue;
-            }
+                if (!tb) continue;
+                const uint32_t A = wa.at(l), B = wb.at(l);
+                const int cidx = tba_cidx(A), kc = cidx ? 1 : 0;
+#if defined(HG_HOST_EMU)
+                if (walk_stats_on() && !(Poll && a.stream_redo)) {
+                    g_walk.tb32_strong += cidx == 0 && tba_log2(A) == 5 && (A & TBA_FILT) && strong;
+                    g_walk.luma4 += cidx == 0 && tba_log2(A) == 2;
+                    g_walk.pcm += (A & TBA_PCM) != 0;
+                }
 #endif
-            predict_tb<Pel, CF>(S, tu, w, PW, PH, cidx, cidx ? sp.bit_depth_c : sp.bit_depth_y, strong, zc,
-                                (m & TBM_FILT) != 0, am, lane);
+                // the TB's component window: a select on cIdx and an add
+                TbWin<Pel> w;
+                unsigned char *const wbase = F.blk + (cidx == 2 ? F.b1 : 0u);
+                w.cur = reinterpret_cast<Pel *>(wbase + wo.cur[kc]);
+                w.left = reinterpret_cast<Pel *>(wbase + wo.left[kc]);
+                w.above = reinterpret_cast<Pel *>(wbase + wo.above[kc]);
+                w.lsx = log2ctb - (cidx ? SX : 0);
+                // (from the CTU's column and the row: a few scalar operations, no SGPR held across the TB)
+                w.vw = (W - (cur << log2ctb)) >> (cidx ? SX : 0);
+                w.vh = (H - (r << log2ctb)) >> (cidx ? SY : 0);
+                w.minx = cur > 0 ? -1 : 0;
+                w.miny = r > 0 ? -1 : 0;
+                w.csl = 1 << log2ctb;
+                w.rp = cidx ? cw : W;
+#if defined(HG_HOST_EMU)
+                w.blk_lo = F.blk;
+                w.blk_hi = F.blk + F.kS0 + F.b0 + (CF ? 2 * F.b1 : 0u);
+#endif
+                if constexpr (XfInline) {
+                    // the TB's residual, transformed by this wave into LDS (pitch n)
+                    w.rt = X.d;
+                    if (A & TBA_CBF) {
+                        TuRec tu;
+#if defined(HG_HOST_EMU)
+                        tu = tus[base + (uint32_t)l];
+#else
+                        const uint4 rr = make_uint4((uint32_t)__builtin_amdgcn_readlane((int)tblk.x, l),
+                                                    (uint32_t)__builtin_amdgcn_readlane((int)tblk.y, l),
+                                                    (uint32_t)__builtin_amdgcn_readlane((int)tblk.z, l),
+                                                    (uint32_t)__builtin_amdgcn_readlane((int)tblk.w, l));
+                        __builtin_memcpy(&tu, &rr, sizeof(tu));
+#endif
+                        const int n = 1 << tba_log2(A);
+                        transform_tb<Poll>(tu, coefs, sp, a.sf, X, X.d, n, lane);
+                        w.rp = n;
+#if defined(HG_HOST_EMU)
+                        w.res_lo = X.d;
+                        w.res_hi = X.d + 32 * 32;  // (the 2 KB residual tile of XfScratch)
+#endif
+                    }
+                } else {
+                    w.rt = F.resid + wc.at(l);  // (word C: inside the picture's residual planes for an OK record)
+                }
+                if (!XfInline && (A & TBA_PAIR)) {
+#if defined(HG_HOST_EMU)
+                    // (one lane: the Cb TB, then the Cr TB from the pair's bits, each as a TB of its own)
+                    predict_tb<Pel, CF>(S, A, B, w, sp.bit_depth_c, strong, lane);
+                    const uint32_t A2 = (A & ~((3u << TBA_CIDX_SHIFT) | TBA_CBF | TBA_PCM)) | (2u << TBA_CIDX_SHIFT) |
+                                        ((A & TBA_CBF2) ? TBA_CBF : 0u) | ((A & TBA_PCM2) ? TBA_PCM : 0u);
+                    w.cur += dwin;
+                    w.left += dwin;
+                    w.above += dwin;
+                    w.rt += dres;
+                    predict_tb<Pel, CF>(S, A2, B, w, sp.bit_depth_c, strong, lane);
+#else
+                    predict_pair<Pel>(S, A, B, w, dwin, dres, sp.bit_depth_c, lane);
+#endif
+                    continue;
+                }
+                predict_tb<Pel, CF>(S, A, B, w, cidx ? sp.bit_depth_c : sp.bit_depth_y, strong, lane);
+            }
+            if (gave_up) break;
+            t = min(ntu, base + 64u);
         }
+        if (!gave_up && !stop && cur >= 0) finish_ctu();  // after the row's last record: the open CTU
         if (gave_up) {  // (the waves below see it and give up too)
             hg_atomic_store(&progress[wave], kGaveUp);
             break;
@@ -1146,6 +1243,15 @@ void emu_intra(const BatchArgs &a0) {
     case 3: emu_intra_cf<3>(a, nw); break;
     default: emu_intra_cf<1>(a, nw); break;
     }
+    if (walk_stats_on())  // (totals of the process so far)
+        printf("intra_walk records %llu ok %llu pairs %llu ctus %llu blocks %llu pair_splits %llu ctu_lane0 %llu "
+               "blocks_no_ctu %llu rows_lt64 %llu rows_gt128 %llu second_rows %llu tb32_strong %llu luma4 %llu pcm %llu\n",
+               (unsigned long long)g_walk.records, (unsigned long long)g_walk.ok, (unsigned long long)g_walk.pairs,
+               (unsigned long long)g_walk.ctus, (unsigned long long)g_walk.blocks,
+               (unsigned long long)g_walk.pair_splits, (unsigned long long)g_walk.ctu_lane0,
+               (unsigned long long)g_walk.blocks_no_ctu, (unsigned long long)g_walk.rows_lt64,
+               (unsigned long long)g_walk.rows_gt128, (unsigned long long)g_walk.second_rows,
+               (unsigned long long)g_walk.tb32_strong, (unsigned long long)g_walk.luma4, (unsigned long long)g_walk.pcm);
 }
 #else
 template <int CF>
