@@ -10,7 +10,14 @@
 // raw[i+1] <= 3): neither zero can itself be a removed byte (those are 3s),
 // so the sequential rule is a per-position predicate and the removal is a
 // stream compaction.  The two bytes before the payload are the NAL header,
-// whose second byte (nuh_temporal_id_plus1 >= 1) is never zero.
+// whose second byte (nuh_temporal_id_plus1 >= 1) is never zero.  A payload that
+// is a piece of a NAL unit (host/batch.cpp: a substream range, or the slice data
+// of several segments back to back) needs the same of its pieces: the byte
+// before each piece is not zero in the NAL unit it comes from.  It is the last
+// byte of a slice header or of a substream, which both end in an alignment bit
+// equal to one, and batch.cpp drops the cabac_zero_words behind a segment's
+// data.  The kernel never reads before bits_off; tests/test_rbsp.py drives it
+// alone against a model of the clause text.
 //
 // The entry points of the slice header count raw bytes (7.4.7.1); each is
 // remapped to its RBSP offset (raw offset minus the removed bytes before it)

@@ -610,7 +610,11 @@ static void coding_unit(pic_t *p, int x0, int y0, int log2cb, int depth) {
             for (int ci = 0; ci < (P->chroma_format ? 3 : 1); ci++) {
                 const int sw = P->chroma_format == 3 ? 1 : 2, sh = P->chroma_format == 1 ? 2 : 1;
                 const int ns = ci ? (n / sw) * (n / sh) : n * n, bd = ci ? P->pcm_bd_c : P->pcm_bd_y;
-                for (int k = 0; k < ns; k++) bw_bits(c->w, (uint32_t)rnd(&p->rng, 1 << bd), bd);
+                /* pcm_mask: the draw stays, so mask 0 gives the bytes it always gave */
+                for (int k = 0; k < ns; k++) {
+                    const uint32_t v = (uint32_t)rnd(&p->rng, 1 << bd);
+                    bw_bits(c->w, P->pcm_mask ? v & (uint32_t)P->pcm_mask : v, bd);
+                }
             }
             ce_start(c, c->w);
             return;
@@ -950,6 +954,7 @@ int synth_check_params(const synth_params *P) {
                    P->pcm_log2_max > P->log2_ctb || P->pcm_log2_max < P->pcm_log2_min || P->pcm_pct < 0 ||
                    P->pcm_pct > 100))
         return -1;
+    if (P->pcm_mask < 0) return -1;
     if (P->slice_ctus < 0 || P->slice_dependent < 0 || P->slice_dependent > 2 || P->slice_lf_across < 0 ||
         P->slice_lf_across > 2)
         return -1;

@@ -40,6 +40,9 @@ typedef struct {
      * CU sizes log2 [pcm_log2_min, pcm_log2_max] (3..5), pcm_loop_filter_disabled_flag,
      * pcm_flag probability in percent for a CU that may take it */
     int32_t pcm, pcm_bd_y, pcm_bd_c, pcm_log2_min, pcm_log2_max, pcm_lf_disabled, pcm_pct;
+    /* nonzero: every PCM sample is ANDed with it (3: samples 0..3, a stream dense in
+     * emulation-prevention bytes); 0: the samples as drawn */
+    int32_t pcm_mask;
 } synth_params;
 
 /* Each returns the NAL unit length (2-byte header included, emulation

@@ -35,7 +35,7 @@ class _Params(ctypes.Structure):
         ("tile_col_w", ctypes.c_int32 * 8), ("tile_row_h", ctypes.c_int32 * 8)] + [
         (n, ctypes.c_int32) for n in ("slice_ctus", "slice_dependent", "slice_lf_across", "slice_dbk_vary",
                                       "pcm", "pcm_bd_y", "pcm_bd_c", "pcm_log2_min", "pcm_log2_max",
-                                      "pcm_lf_disabled", "pcm_pct")]
+                                      "pcm_lf_disabled", "pcm_pct", "pcm_mask")]
 
 
 @dataclasses.dataclass
@@ -94,6 +94,7 @@ class SynthParams:
     pcm_log2_max: int = 5
     pcm_lf_disabled: int = 0
     pcm_pct: int = 10
+    pcm_mask: int = 0  # nonzero: PCM samples ANDed with it (3: a stream dense in emulation-prevention bytes)
 
     def _c(self) -> _Params:
         c = _Params()

@@ -240,3 +240,55 @@ def split_slices(p, item: bytes) -> List[SubPicture]:
         sp = dataclasses.replace(p, height=h, slice_ctus=0, conf_bottom=p.conf_bottom if last else 0)
         subs.append(SubPicture(0, y0, sp, nal[:2] + _ep(w.bytes()) + nal[2 + hdr_raw:]))
     return subs
+
+
+def slice_header(p, nal: bytes) -> dict:
+    """The slice segment header of one NAL unit hevc_synth.c wrote with p, read in
+    its field order: `entries_pos` is the RBSP bit position of num_entry_point_offsets
+    (the header's end when p has neither WPP nor tiles), `offsets` the entry point
+    offsets, `data_raw` the payload byte (nal[2:]) where slice_segment_data() starts
+    and `starts` the payload bytes where the segment's substreams start."""
+    ctb = 1 << p.log2_ctb
+    nctb = -(-p.width // ctb) * -(-p.height // ctb)
+    rbsp = _unescape(nal[2:])
+    r = _Reader(rbsp)
+    first = r.u(1)
+    r.u(1)
+    assert r.ue() == 0
+    dependent = 0
+    if not first:
+        if p.slice_dependent:
+            dependent = r.u(1)
+        r.u((nctb - 1).bit_length())
+    if not dependent:
+        assert r.ue() == 2
+        sao = 0
+        if p.sao:
+            sao = r.u(1)
+            if p.chroma_format:
+                sao |= r.u(1)
+        r.se()
+        dis = p.deblock_disabled
+        if p.slice_dbk_vary and r.u(1):
+            dis = r.u(1)
+            if not dis:
+                r.se()
+                r.se()
+        if p.slice_lf_across and (sao or not dis):
+            r.u(1)
+    entries_pos, offs = r.pos, []
+    if p.wpp or p.tile_cols * p.tile_rows > 1:
+        n = r.ue()
+        if n:
+            ln = r.ue() + 1
+            offs = [r.u(ln) + 1 for _ in range(n)]
+    assert r.u(1) == 1
+    while r.pos & 7:
+        assert r.u(1) == 0
+    data_raw = len(_ep(rbsp[:r.pos >> 3]))  # the header ends in a nonzero byte: no EP state carries over
+    assert nal[2:2 + data_raw] == _ep(rbsp[:r.pos >> 3])
+    starts = [data_raw]
+    for o in offs:
+        starts.append(starts[-1] + o)
+    assert starts[-1] < len(nal) - 2
+    return dict(rbsp=rbsp, entries_pos=entries_pos, offsets=offs, data_raw=data_raw, starts=starts, dependent=dependent)
