@@ -25,6 +25,7 @@ from ._lib import HeifGpuError, UnsupportedError, lib
 __all__ = [
     "HeicDecoder", "HeifImage", "DecodeContext", "DeviceBatch", "DecodedImage", "RbspReader",
     "HeifGpuError", "UnsupportedError", "ipc_export", "ipc_open", "ipc_close", "chroma_dims", "ColorDescription",
+    "HdrDescription",
 ]
 
 
@@ -120,19 +121,57 @@ class HeifImage:
         _lib.check(lib.heifgpu_image_get_icc(self._h, buf, n.value, ctypes.byref(n)))
         return bytes(buf)
 
-    def color_transform(self, colorspace: str, bits: int = 8) -> _lib.ColorTransform:
+    @property
+    def hdr(self) -> Optional["HdrDescription"]:
+        """What an HDR item carries (heifgpu_image_get_hdr): the transfer (16 PQ,
+        18 HLG), MaxCLL / MaxFALL of its clli box and the mastering luminances of
+        its mdcv box (None without the box), and what a tone transform of it
+        answers.  None for an item whose colour is not defined by a PQ / HLG nclx."""
+        hi = _lib.HdrInfo()
+        _lib.check(lib.heifgpu_image_get_hdr(self._h, ctypes.byref(hi)))
+        if not hi.transfer:
+            return None
+        clli, mdcv = bool(hi.present & _lib.HDR_HAS_CLLI), bool(hi.present & _lib.HDR_HAS_MDCV)
+        return HdrDescription(hi.transfer, hi.max_cll if clli else None, hi.max_fall if clli else None,
+                              hi.mastering_max * 1e-4 if mdcv else None, hi.mastering_min * 1e-4 if mdcv else None,
+                              hi.status)
+
+    # a caller's source peak in cd/m2 for the tone transforms of this image (None: the file's);
+    # color_transform(peak_nits=) overrides it for one call
+    peak_nits: Optional[float] = None
+
+    def color_transform(self, colorspace: str, bits: int = 8, tone_map: Optional[str] = None,
+                        peak_nits: Optional[float] = None):
         """The transform of this image's colour space to "srgb" or "display-p3" at
         the depth a render computes at (heifgpu_color_transform_make): 8 for the
         8-bit formats, the image's bit depth for the 16-bit ones.  UnsupportedError
         for a source outside the supported set (LUT profiles, PQ / HLG, ...),
-        HeifGpuError for a malformed profile.  Cached per (colorspace, bits)."""
+        HeifGpuError for a malformed profile.  tone_map "bt2390" gives an nclx PQ /
+        HLG source a transform with a BT.2390 tone stage instead of the refusal (a
+        _lib.HdrTransform, heifgpu_color_transform_make_hdr; peak_nits replaces the
+        source peak the file states) and every other image the transform it gets
+        without.  Cached per (colorspace, bits, tone_map, peak_nits)."""
         if colorspace not in _lib.COLORSPACES:
             raise ValueError(f"colorspace {colorspace!r}: one of {sorted(_lib.COLORSPACES)}")
+        if tone_map is not None and tone_map not in _lib.TONE_MAPS:
+            raise ValueError(f"tone_map {tone_map!r}: None or one of {sorted(_lib.TONE_MAPS)}")
+        if peak_nits is None:
+            peak_nits = self.peak_nits
+        peak = float(peak_nits) if peak_nits is not None and tone_map is not None else 0.0
         cache = self.__dict__.setdefault("_xf", {})
-        key = (colorspace, int(bits))
+        key = (colorspace, int(bits)) if tone_map is None else (colorspace, int(bits), tone_map, peak)
         if key not in cache:
-            t = _lib.ColorTransform()
-            _lib.check(lib.heifgpu_color_transform_make(self._h, _lib.COLORSPACES[colorspace], int(bits), ctypes.byref(t)))
+            if tone_map is None:
+                t = _lib.ColorTransform()
+                _lib.check(lib.heifgpu_color_transform_make(self._h, _lib.COLORSPACES[colorspace], int(bits), ctypes.byref(t)))
+            else:
+                h = _lib.HdrTransform()
+                _lib.check(lib.heifgpu_color_transform_make_hdr(self._h, _lib.COLORSPACES[colorspace], int(bits),
+                                                                _lib.TONE_MAPS[tone_map], peak, ctypes.byref(h)))
+                t = h
+                if not h.base.tone:  # not an HDR source: the transform it gets without tone_map, as that type
+                    t = _lib.ColorTransform()
+                    ctypes.memmove(ctypes.byref(t), ctypes.byref(h.base), ctypes.sizeof(t))
             cache[key] = t
         return cache[key]
 
@@ -196,6 +235,16 @@ class ColorDescription:
     icc_size: int = 0
     has_nclx: bool = False
     status: int = 0             # HEIFGPU_OK, or the code a transform of this source answers
+
+
+@dataclass
+class HdrDescription:
+    transfer: int                      # 16 (PQ) or 18 (HLG)
+    max_cll: Optional[int]             # clli, cd/m2; None without the box
+    max_fall: Optional[int]
+    mastering_max: Optional[float]     # mdcv, cd/m2; None without the box
+    mastering_min: Optional[float]
+    status: int = 0                    # HEIFGPU_OK, or the code a tone transform of this item answers
 
 
 def chroma_dims(info):
@@ -436,7 +485,7 @@ class DecodeContext:
 
     def render(self, outs: Sequence[DecodedImage], fmt: str = "rgb8",
                alphas: Optional[Sequence[Optional[DecodedImage]]] = None, stream: Optional[int] = None,
-               colorspace: Optional[str] = None):
+               colorspace: Optional[str] = None, tone_map: Optional[str] = None):
         """Display-ready pixels of a batch of decoded images with ONE
         heifgpu_render_batch call (one kernel launch): a list of (H', W', C)
         device tensors, C = 3 or 4, uint8 for "rgb8" / "rgba8" and int16 (like
@@ -448,7 +497,11 @@ class DecodeContext:
         "display-p3" converts every RGB triple from the image's ICC profile or
         nclx description to that space in the same launch (heifgpu_render_batch_color;
         alpha untouched); a source the library cannot transform raises
-        UnsupportedError before anything is launched."""
+        UnsupportedError before anything is launched.  tone_map "bt2390", with a
+        colorspace, tone-maps the nclx PQ / HLG pictures of the batch to SDR in the
+        same launch (BT.2390 on luminance, include/heifgpu.h "HDR render") instead
+        of refusing them; every other picture gets the transform it gets without."""
+        self._check_tone(colorspace, tone_map)
         torch = self._torch
         f = _lib.PIX_FORMATS[fmt]
         ch, wide = (4 if f & 1 else 3), f >= _lib.PIX_RGB16
@@ -458,8 +511,18 @@ class DecodeContext:
         dev = torch.device("cuda", self.device)
         res = [torch.empty((o.image.display.out_height, o.image.display.out_width, ch),
                            dtype=torch.int16 if wide else torch.uint8, device=dev) for o in outs]
-        self._submit("heifgpu_render_batch", outs, alphas, colorspace, wide, stream, (f,), self._surfaces(res))
+        self._submit("heifgpu_render_batch", outs, alphas, colorspace, wide, stream, (f,), self._surfaces(res), tone_map)
         return res
+
+    @staticmethod
+    def _check_tone(colorspace, tone_map):
+        """ValueError for an unknown tone_map, or one without a colorspace to map to."""
+        if tone_map is None:
+            return
+        if tone_map not in _lib.TONE_MAPS:
+            raise ValueError(f"tone_map {tone_map!r}: None or one of {sorted(_lib.TONE_MAPS)}")
+        if colorspace is None:
+            raise ValueError("tone_map needs a colorspace to map to")
 
     @staticmethod
     def _check_images(what, outs, alphas, **more):
@@ -480,14 +543,14 @@ class DecodeContext:
             surf[i].pitch = t.stride(0) * t.element_size()
         return surf
 
-    def _submit(self, name, outs, alphas, colorspace, wide, stream, mid, surf):
+    def _submit(self, name, outs, alphas, colorspace, wide, stream, mid, surf, tone_map=None):
         """The one call of a render: lib.<name>, or lib.<name>_color with the images'
         transforms in front of the surfaces when a colorspace is asked for.  mid: the
         arguments between the alpha planes and the surfaces."""
         imgs, aimgs, aplanes = self._render_args(outs, alphas)
         if stream is None:
             stream = self._torch.cuda.current_stream(self.device).cuda_stream
-        xf, keep = self._transforms(outs, colorspace, wide)
+        xf, keep = self._transforms(outs, colorspace, wide, tone_map)
         if callable(mid):  # a filtered render: one entry point, its transforms (or NULL) where mid puts them
             fn, mid = getattr(lib, name), mid(xf)
         else:
@@ -527,7 +590,7 @@ class DecodeContext:
                       for i in range(n)]
 
     @staticmethod
-    def _transforms(outs, colorspace, wide):
+    def _transforms(outs, colorspace, wide, tone_map=None):
         """(one transform pointer per image, the transforms they point to) for a
         colour-managed render call; (None, None) for colorspace None.  Raises
         before anything is launched (UnsupportedError, HeifGpuError)."""
@@ -535,7 +598,7 @@ class DecodeContext:
             return None, None
         if colorspace not in _lib.COLORSPACES:
             raise ValueError(f"colorspace {colorspace!r}: None or one of {sorted(_lib.COLORSPACES)}")
-        keep = [o.image.color_transform(colorspace, int(o.info.bit_depth) if wide else 8) for o in outs]
+        keep = [o.image.color_transform(colorspace, int(o.info.bit_depth) if wide else 8, tone_map) for o in outs]
         arr = (ctypes.c_void_p * max(len(outs), 1))(*[ctypes.addressof(t) for t in keep])
         return arr, keep
 
@@ -556,7 +619,8 @@ class DecodeContext:
 
     def render_scaled(self, outs: Sequence[DecodedImage], size, mode: str = "cover", fmt: str = "rgb8",
                       alphas: Optional[Sequence[Optional[DecodedImage]]] = None, windows=None,
-                      stream: Optional[int] = None, colorspace: Optional[str] = None, filter: str = "area"):
+                      stream: Optional[int] = None, colorspace: Optional[str] = None, filter: str = "area",
+                      tone_map: Optional[str] = None):
         """render() onto a smaller grid: the exact area average of a window of
         every displayed picture, with ONE heifgpu_render_batch_scaled call (one
         kernel launch).  size = (h, w) is the box; mode "cover" (a centred
@@ -567,13 +631,14 @@ class DecodeContext:
         exactly.  Returns ONE (N, h, w, C) device tensor when every output has
         the same size (cover, stretch, windows), whose slices are the surfaces,
         and a list of (h_i, w_i, C) tensors for "contain".  Dtypes, fmt,
-        alphas and colorspace as in render(): with a colorspace the result is
+        alphas, colorspace and tone_map as in render(): with a colorspace the result is
         the transform of what render_scaled() writes without one (the rounded
         averages are transformed, not the source pixels).  filter "bilinear" or
         "bicubic" resamples with Pillow's antialiased filter of that name
         instead of the area average (heifgpu_render_batch_resampled): per
         channel, for the 8-bit formats, exactly what PIL's
         Image.resize(size, filter, box=window) makes of render()'s picture."""
+        self._check_tone(colorspace, tone_map)
         torch = self._torch
         n = len(outs)
         f = _lib.PIX_FORMATS[fmt]
@@ -587,16 +652,17 @@ class DecodeContext:
                                           lambda h, w: (h, w, ch), torch.int16 if wide else torch.uint8)
         if n and filt == _lib.FILTER_AREA:
             self._submit("heifgpu_render_batch_scaled", outs, alphas, colorspace, wide, stream, (f, scales),
-                         self._surfaces(res))
+                         self._surfaces(res), tone_map)
         elif n:
             self._submit("heifgpu_render_batch_resampled", outs, alphas, colorspace, wide, stream,
-                         lambda xf: (f, scales, filt, xf), self._surfaces(res))
+                         lambda xf: (f, scales, filt, xf), self._surfaces(res), tone_map)
         return whole if whole is not None else res
 
     def render_tensor(self, outs: Sequence[DecodedImage], size, mode: str = "cover", dtype=None, layout: str = "chw",
                       mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), src: str = "rgb8", windows=None,
                       flips=None, alphas: Optional[Sequence[Optional[DecodedImage]]] = None, scale_bias=None,
-                      stream: Optional[int] = None, colorspace: Optional[str] = None, filter: str = "area"):
+                      stream: Optional[int] = None, colorspace: Optional[str] = None, filter: str = "area",
+                      tone_map: Optional[str] = None):
         """render_scaled() as a loader wants it: crop, flip and normalise into
         float elements with ONE heifgpu_render_batch_tensor call (one kernel
         launch).  With R the integers render_scaled(fmt=src) gives, flipped
@@ -610,11 +676,12 @@ class DecodeContext:
         layout "chw" returns ONE (N, C, h, w) tensor, "hwc" ONE (N, h, w, C)
         tensor, for cover, stretch and windows; "contain" returns a list of
         (C, h_i, w_i) or (h_i, w_i, C) tensors.  size, mode, windows, alphas,
-        colorspace and filter as in render_scaled(): R is then what
-        render_scaled(colorspace=, filter=) gives (with "bilinear" or "bicubic"
+        colorspace, tone_map and filter as in render_scaled(): R is then what
+        render_scaled(colorspace=, filter=, tone_map=) gives (with "bilinear" or "bicubic"
         the pixels Pillow's resize gives, which is what most vision models were
         trained on; a flip then acts on R, not on the taps)."""
         filt = _filter_code(filter)
+        self._check_tone(colorspace, tone_map)
         torch = self._torch
         n = len(outs)
         f = _lib.PIX_FORMATS[src]
@@ -660,10 +727,10 @@ class DecodeContext:
         fl = None if flips is None else (ctypes.c_uint32 * n)(*[int(v) for v in flips])
         if filt == _lib.FILTER_AREA:
             self._submit("heifgpu_render_batch_tensor", outs, alphas, colorspace, wide, stream,
-                         (ctypes.byref(tf), scales, fl), surf)
+                         (ctypes.byref(tf), scales, fl), surf, tone_map)
         else:
             self._submit("heifgpu_render_batch_tensor_resampled", outs, alphas, colorspace, wide, stream,
-                         lambda xf: (ctypes.byref(tf), scales, filt, fl, xf), surf)
+                         lambda xf: (ctypes.byref(tf), scales, filt, fl, xf), surf, tone_map)
         return whole if whole is not None else res
 
 
@@ -833,7 +900,7 @@ class HeicDecoder:
     @classmethod
     def decode_display(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, size=None,
                        mode: str = "contain", tiles: str = "all", colorspace: Optional[str] = None,
-                       filter: str = "area"):
+                       filter: str = "area", tone_map: Optional[str] = None, peak_nits: Optional[float] = None):
         """The picture a viewer shows: decodes the primary image and, when it
         has one (display.alpha_item_id), its alpha plane, then renders
         (DecodeContext.render) with clap / irot / imir applied.  fmt None picks
@@ -846,28 +913,37 @@ class HeicDecoder:
         or nclx description to that space (DecodeContext.render); None leaves it
         in its own, unlabelled.  filter, with a size: "area" (the area average,
         right for reduction), "bilinear" or "bicubic" (Pillow's antialiased
-        filters, which also interpolate an enlargement as a viewer expects)."""
+        filters, which also interpolate an enlargement as a viewer expects).
+        tone_map "bt2390", with a colorspace, shows a PQ / HLG picture tone-mapped
+        to SDR (DecodeContext.render); peak_nits replaces the source peak the file
+        states (clli, mdcv)."""
+        DecodeContext._check_tone(colorspace, tone_map)
         ctx = cls.context(device)
         out, alpha = cls._decode_pair(data, device, size, mode, tiles, True, filter)
+        out.image.peak_nits = peak_nits
         if fmt is None:
             fmt = ("rgba" if alpha is not None else "rgb") + ("16" if out.info.bit_depth > 8 else "8")
         alphas = [alpha] if alpha is not None else None
         if size is not None:
-            return ctx.render_scaled([out], size, mode, fmt, alphas, colorspace=colorspace, filter=filter)[0]
-        return ctx.render([out], fmt, alphas, colorspace=colorspace)[0]
+            return ctx.render_scaled([out], size, mode, fmt, alphas, colorspace=colorspace, filter=filter,
+                                     tone_map=tone_map)[0]
+        return ctx.render([out], fmt, alphas, colorspace=colorspace, tone_map=tone_map)[0]
 
     @classmethod
     def decode_tensor(cls, data: bytes, size, mode: str = "cover", device: int = 0, flip: int = 0,
-                      tiles: str = "all", **kw):
+                      tiles: str = "all", peak_nits: Optional[float] = None, **kw):
         """decode_display(size=) as a normalised float tensor: decodes the
         primary image (and its alpha plane when `src` is an RGBA format and the
         file has one), then DecodeContext.render_tensor of that one picture:
         (C, h, w), or (h, w, C) for layout="hwc".  dtype, layout, mean, std, src
-        scale_bias, colorspace and filter go through to render_tensor; tiles as in decode_display."""
+        scale_bias, colorspace, tone_map and filter go through to render_tensor; tiles and
+        peak_nits as in decode_display."""
+        DecodeContext._check_tone(kw.get("colorspace"), kw.get("tone_map"))
         ctx = cls.context(device)
         rgba = kw.get("src", "rgb8").startswith("rgba")
         out, alpha = cls._decode_pair(data, device, size, mode, tiles, rgba, kw.get("filter", "area"))
         alphas = [alpha] if alpha is not None else None
+        out.image.peak_nits = peak_nits
         return ctx.render_tensor([out], size, mode, flips=[flip], alphas=alphas, **kw)[0]
 
     @classmethod

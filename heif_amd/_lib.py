@@ -176,14 +176,40 @@ class ColorInfo(ctypes.Structure):
 class ColorTransform(ctypes.Structure):
     """heifgpu_color_transform: the tables and the Q14 matrix of one source at one depth."""
     _fields_ = [("bits", ctypes.c_uint32), ("identity", ctypes.c_uint32), ("dst", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32), ("m", ctypes.c_int32 * 9), ("m_rounded", ctypes.c_int32 * 9),
+                ("tone", ctypes.c_uint32), ("m", ctypes.c_int32 * 9), ("m_rounded", ctypes.c_int32 * 9),
                 ("in_lut", (ctypes.c_uint16 * 4096) * 3), ("out_lut", ctypes.c_uint16 * 4098)]
+
+
+class HdrInfo(ctypes.Structure):
+    """heifgpu_hdr_info: the transfer of an nclx-defined PQ / HLG item (else 0), which of
+    clli / mdcv it carries (present: HDR_HAS_*), their values, and what a tone transform
+    of the item answers (status)."""
+    _fields_ = [("transfer", ctypes.c_uint32), ("present", ctypes.c_uint32), ("max_cll", ctypes.c_uint32),
+                ("max_fall", ctypes.c_uint32), ("mastering_max", ctypes.c_uint32), ("mastering_min", ctypes.c_uint32),
+                ("status", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+class HdrTransform(ctypes.Structure):
+    """heifgpu_hdr_transform: a colour transform (base; base.tone != 0) and the tables of
+    its tone stage.  A render or heifgpu_color_apply takes the address of `base`."""
+    _fields_ = [("base", ColorTransform), ("in_lut32", (ctypes.c_uint32 * 4096) * 3), ("w", ctypes.c_int32 * 3),
+                ("transfer", ctypes.c_uint32), ("T", ctypes.c_uint32 * 578), ("Lsrc", ctypes.c_double)]
+
+    # what the renders read of a transform, whichever kind it is
+    bits = property(lambda self: self.base.bits)
+    identity = property(lambda self: self.base.identity)
+    dst = property(lambda self: self.base.dst)
+    tone = property(lambda self: self.base.tone)
 
 
 COLOR_NONE, COLOR_ICC, COLOR_NCLX = 0, 1, 2
 COLOR_KINDS = {COLOR_NONE: "none", COLOR_ICC: "icc", COLOR_NCLX: "nclx"}
 CS_SRGB, CS_DISPLAY_P3 = 0, 1
 COLORSPACES = {"srgb": CS_SRGB, "display-p3": CS_DISPLAY_P3}
+TONE_NONE, TONE_BT2390 = 0, 1
+TONE_MAPS = {"bt2390": TONE_BT2390}
+HDR_HAS_CLLI, HDR_HAS_MDCV = 1, 2
+TONE_ENTRIES = 577
 
 ELEM_F32, ELEM_F16, ELEM_BF16 = 0, 1, 2
 LAYOUT_CHW, LAYOUT_HWC = 0, 1
@@ -222,6 +248,7 @@ EXPORTS = (
     "heifgpu_render_batch_color", "heifgpu_render_batch_scaled_color", "heifgpu_render_batch_tensor_color",
     "heifgpu_render_batch_resampled", "heifgpu_render_batch_tensor_resampled", "heifgpu_resample_coeffs",
     "heifgpu_resample_apply", "heifgpu_window_source_rect_resampled",
+    "heifgpu_image_get_hdr", "heifgpu_color_transform_make_hdr",
 )
 
 
@@ -321,6 +348,8 @@ def _load() -> ctypes.CDLL:
         "heifgpu_resample_coeffs": (I32, [U32, U32, U32, U32, U32, U32, P(ctypes.c_int32), P(ctypes.c_int32), SZ, P(U32)]),
         "heifgpu_resample_apply": (I32, [VP, U32, U32, U32, U32, P(Rect), U32, U32, U32, VP]),
         "heifgpu_window_source_rect_resampled": (I32, [VP, P(Scale), U32, P(Rect)]),
+        "heifgpu_image_get_hdr": (I32, [VP, P(HdrInfo)]),
+        "heifgpu_color_transform_make_hdr": (I32, [VP, U32, U32, U32, ctypes.c_double, P(HdrTransform)]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     # (and no window decode: DecodeContext.prepare without windows then goes through prepare_ex)
@@ -331,7 +360,9 @@ def _load() -> ctypes.CDLL:
                 "heifgpu_render_batch_color", "heifgpu_render_batch_scaled_color", "heifgpu_render_batch_tensor_color",
                 # the filtered renders (filter= other than "area" then needs a build that has them)
                 "heifgpu_render_batch_resampled", "heifgpu_render_batch_tensor_resampled", "heifgpu_resample_coeffs",
-                "heifgpu_resample_apply", "heifgpu_window_source_rect_resampled"}
+                "heifgpu_resample_apply", "heifgpu_window_source_rect_resampled",
+                # the HDR render (tone_map= then needs a build that has it)
+                "heifgpu_image_get_hdr", "heifgpu_color_transform_make_hdr"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue

@@ -177,8 +177,51 @@ int heifgpu_color_transform_make(const heifgpu_image *img, uint32_t dst, uint32_
     return HEIFGPU_OK;
 }
 
+int heifgpu_image_get_hdr(const heifgpu_image *img, heifgpu_hdr_info *out) {
+    if (!img || !out) return fail(HEIFGPU_E_INVALID, "null argument");
+    const ColorDesc &c = img->img.color;
+    std::memset(out, 0, sizeof(*out));
+    out->transfer = hdr_transfer(c);
+    out->present = (c.has_clli ? HEIFGPU_HDR_HAS_CLLI : 0u) | (c.has_mdcv ? HEIFGPU_HDR_HAS_MDCV : 0u);
+    HdrMeta m;
+    std::string err;
+    out->status = hdr_read(c, m, err);
+    out->max_cll = m.max_cll, out->max_fall = m.max_fall;
+    out->mastering_max = m.mastering_max, out->mastering_min = m.mastering_min;
+    return HEIFGPU_OK;
+}
+
+int heifgpu_color_transform_make_hdr(const heifgpu_image *img, uint32_t dst, uint32_t bits, uint32_t tone_map,
+                                     double peak_nits, heifgpu_hdr_transform *out) {
+    if (!img || !out) return fail(HEIFGPU_E_INVALID, "null argument");
+    std::string err;
+    if (int rc = hdr_transform_make(img->img.color, dst, bits, tone_map, peak_nits, *out, err)) return fail(rc, err);
+    return HEIFGPU_OK;
+}
+
+// heifgpu_color_apply for a tone transform (t->base.tone != 0)
+static int tone_apply(const heifgpu_hdr_transform *t, const uint16_t *rgb_in, size_t n_pixels, uint16_t *rgb_out) {
+    if (t->base.tone != HEIFGPU_TONE_BT2390 || !hdr_transform_valid(*t))
+        return fail(HEIFGPU_E_INVALID, "tone transform: tag, depth, weights or a level above 2^22 - 1");
+    const int n = 1 << t->base.bits;
+    std::vector<uint32_t> in_lut(size_t(3) * n);
+    for (int c = 0; c < 3; ++c) std::memcpy(in_lut.data() + size_t(c) * n, t->in_lut32[c], size_t(n) * 4);
+    for (size_t i = 0; i < 3 * n_pixels; ++i)
+        if (rgb_in[i] >= n) return fail(HEIFGPU_E_INVALID, "code above maxv");
+    const uint32_t *in = in_lut.data();
+    const XfToneLut<const uint32_t *> tone{t->T};
+    const XfOutLut<const uint16_t *> out{t->base.out_lut};
+    for (size_t i = 0; i < n_pixels; ++i) {
+        uint32_t r = rgb_in[3 * i], g = rgb_in[3 * i + 1], b = rgb_in[3 * i + 2];
+        color_tone_px(in, n, t->w, tone, out, t->base.m, r, g, b);
+        rgb_out[3 * i] = uint16_t(r), rgb_out[3 * i + 1] = uint16_t(g), rgb_out[3 * i + 2] = uint16_t(b);
+    }
+    return HEIFGPU_OK;
+}
+
 int heifgpu_color_apply(const heifgpu_color_transform *t, const uint16_t *rgb_in, size_t n_pixels, uint16_t *rgb_out) {
     if (!t || !rgb_in || !rgb_out) return fail(HEIFGPU_E_INVALID, "null argument");
+    if (t->tone) return tone_apply(reinterpret_cast<const heifgpu_hdr_transform *>(t), rgb_in, n_pixels, rgb_out);
     if (t->bits < 8 || t->bits > 12) return fail(HEIFGPU_E_INVALID, "transform depth outside 8..12");
     const int n = 1 << t->bits;
     // the tables as the device holds them: three of n entries, one after the other

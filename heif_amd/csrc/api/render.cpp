@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../common/desc.hpp"
+#include "../host/icc.hpp"
 #include "../host/resample.hpp"
 #include "../kernels/color_xform.hpp"
 #include "api.hpp"
@@ -34,7 +35,9 @@ struct RenderRing {
 };
 
 // The tables of the transforms on the device, keyed by content: in_lut[3][1 << B] then
-// out_lut as 4096 pairs (xf_out_pair), as ColorRef::lut addresses them.  An entry is written once, by a blocking
+// out_lut as 4096 pairs (xf_out_pair), as ColorRef::lut addresses them; for a tone transform
+// in_lut32[3][1 << B], the same pairs and a ToneBlock (another size: the two kinds never compare
+// equal).  An entry is written once, by a blocking
 // copy before the call that first uses it launches anything, and never again, so no
 // launch in flight can see a table change; a steady-state call finds its tables here.
 // When kColorCacheMax tables are held the cache is emptied after a device synchronise.
@@ -58,11 +61,35 @@ void hg::render_state_free(heifgpu_ctx *ctx) {
     delete ctx->color;
 }
 
+// The device image of a tone transform (t->tone != 0: the first member of a
+// heifgpu_hdr_transform) as 16-bit units, and where its ToneBlock lies in it.
+static void tone_table_image(const heifgpu_color_transform *t, std::vector<uint16_t> &key, int32_t &tone_off) {
+    const heifgpu_hdr_transform &h = *reinterpret_cast<const heifgpu_hdr_transform *>(t);
+    const size_t tn = size_t(1) << t->bits;
+    const size_t off = 4 * (3 * tn + kXfPairEntries);  // bytes: a multiple of 8
+    std::vector<uint8_t> img(off + sizeof(ToneBlock));
+    for (int c = 0; c < 3; ++c) std::memcpy(img.data() + 4 * c * tn, h.in_lut32[c], 4 * tn);
+    for (int k = 0; k < kXfPairEntries; ++k) {
+        const uint32_t w = xf_out_pair(t->out_lut, k);
+        std::memcpy(img.data() + 4 * (3 * tn + k), &w, 4);
+    }
+    ToneBlock tb{};
+    for (int c = 0; c < 3; ++c) tb.w[c] = h.w[c];
+    for (int k = 0; k < kXfTonePairs; ++k) tb.pairs[2 * k] = h.T[k], tb.pairs[2 * k + 1] = h.T[k + 1];
+    std::memcpy(img.data() + off, &tb, sizeof(tb));
+    key.resize(img.size() / 2);
+    std::memcpy(key.data(), img.data(), img.size());
+    tone_off = int32_t(off);
+}
+
 // refs[i] for the images of a render call (empty when no image is to be transformed:
-// the call is then the unmanaged call).  Every check runs before anything is launched.
+// the call is then the unmanaged call); tone: some image has a tone transform.  Every
+// check runs before anything is launched.
 static int color_refs_fill(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, uint32_t format,
-                           const heifgpu_color_transform *const *xf, std::vector<ColorRef> &refs) {
+                           const heifgpu_color_transform *const *xf, std::vector<ColorRef> &refs, bool &tone) {
+    static_assert(sizeof(ToneBlock) == 16 + 8 * kXfTonePairs && sizeof(ToneBlock) % 8 == 0, "ToneBlock: weights, then pairs");
     refs.clear();
+    tone = false;
     if (!xf) return HEIFGPU_OK;
     bool any = false;
     for (size_t i = 0; i < n; ++i) {
@@ -73,6 +100,9 @@ static int color_refs_fill(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, s
         const uint32_t depth = format >= HEIFGPU_PIX_RGB16 ? info.bit_depth : 8;
         if (t->bits != depth || t->bits < 8 || t->bits > 12)
             return fail(HEIFGPU_E_INVALID, "transform made for another depth than the image is rendered at");
+        if (t->tone && (t->tone != HEIFGPU_TONE_BT2390 || t->identity ||
+                        !hdr_transform_valid(*reinterpret_cast<const heifgpu_hdr_transform *>(t))))
+            return fail(HEIFGPU_E_INVALID, "tone transform: tag, weights or a level above 2^22 - 1");
         any = any || !t->identity;
     }
     if (!any) return HEIFGPU_OK;
@@ -89,11 +119,17 @@ static int color_refs_fill(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, s
         const heifgpu_color_transform *t = xf[i];
         if (!t || t->identity) continue;  // lut == 0: untouched
         const size_t tn = size_t(1) << t->bits;
-        key.resize(3 * tn + 2 * kXfPairEntries);
-        for (int c = 0; c < 3; ++c) std::memcpy(key.data() + c * tn, t->in_lut[c], tn * 2);
-        for (int k = 0; k < kXfPairEntries; ++k) {
-            const uint32_t w = xf_out_pair(t->out_lut, k);
-            std::memcpy(key.data() + 3 * tn + 2 * k, &w, 4);
+        int32_t tone_off = 0;
+        if (t->tone) {
+            tone_table_image(t, key, tone_off);
+            tone = true;
+        } else {
+            key.resize(3 * tn + 2 * kXfPairEntries);
+            for (int c = 0; c < 3; ++c) std::memcpy(key.data() + c * tn, t->in_lut[c], tn * 2);
+            for (int k = 0; k < kXfPairEntries; ++k) {
+                const uint32_t w = xf_out_pair(t->out_lut, k);
+                std::memcpy(key.data() + 3 * tn + 2 * k, &w, 4);
+            }
         }
         ColorCache::Entry *hit = nullptr;
         for (ColorCache::Entry &e : cache.entries)
@@ -113,6 +149,8 @@ static int color_refs_fill(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, s
         refs[i].lut = reinterpret_cast<uint64_t>(hit->dev);
         refs[i].n = int32_t(tn);
         for (int k = 0; k < 9; ++k) refs[i].m[k] = t->m[k];
+        refs[i].tone = int32_t(t->tone);
+        refs[i].tone_off = tone_off;
     }
     return HEIFGPU_OK;
 }
@@ -208,7 +246,8 @@ static int render_submit(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, con
     static_assert(sizeof(Desc) % 8 == 0, "the ColorRefs behind the descriptors are 8-byte aligned");
     const size_t n = descs.size();
     std::vector<ColorRef> refs;
-    if (int rc = color_refs_fill(ctx, imgs, n, format, xf, refs)) return rc;
+    bool tone = false;
+    if (int rc = color_refs_fill(ctx, imgs, n, format, xf, refs, tone)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     RenderRing::Slot *slot = nullptr;
     if (int rc = render_ring_slot(ctx, &slot)) return rc;
@@ -219,8 +258,8 @@ static int render_submit(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, con
     std::memcpy(sl.host.p, descs.data(), dbytes);
     if (!refs.empty()) std::memcpy(sl.host.p + dbytes, refs.data(), bytes - dbytes);  // behind the descriptors: one copy
     HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_render(reinterpret_cast<const Desc *>(sl.dev.p), int(n), max_tiles, int(format), bps, !refs.empty(),
-                          s));  // the one launch
+    HIP_TRY(launch_render(reinterpret_cast<const Desc *>(sl.dev.p), int(n), max_tiles, int(format), bps,
+                          refs.empty() ? RENDER_PLAIN : tone ? RENDER_TONE : RENDER_MANAGED, s));  // the one launch
     HIP_TRY(hipEventRecord(sl.done, s));
     sl.pending = true;
     return HEIFGPU_OK;

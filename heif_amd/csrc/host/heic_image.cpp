@@ -206,6 +206,14 @@ ParsedImage parse_heic(const uint8_t *data, size_t len, uint32_t item_id) {
     for (uint32_t idx : pi->properties) {
         if (idx == 0 || idx > heif.properties.size()) continue;
         const Property &p = heif.properties[idx - 1];
+        // the light-level boxes of an HDR item (the first of each): their payloads, unread
+        if (p.type == fourcc('c', 'l', 'l', 'i') && !img.color.has_clli) {
+            img.color.has_clli = true;
+            img.color.clli.assign(data + p.offset, data + p.offset + p.length);
+        } else if (p.type == fourcc('m', 'd', 'c', 'v') && !img.color.has_mdcv) {
+            img.color.has_mdcv = true;
+            img.color.mdcv.assign(data + p.offset, data + p.offset + p.length);
+        }
         if (p.type != fourcc('c', 'o', 'l', 'r') || p.length < 4) continue;
         const uint8_t *q = data + p.offset;
         const uint32_t kind = (uint32_t(q[0]) << 24) | (uint32_t(q[1]) << 16) | (uint32_t(q[2]) << 8) | q[3];

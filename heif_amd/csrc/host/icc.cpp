@@ -156,13 +156,8 @@ int icc_read(const uint8_t *p, size_t len, ColorSource &out, std::string &err) {
     return HEIFGPU_OK;
 }
 
-int nclx_source(uint32_t primaries, uint32_t transfer, ColorSource &out, std::string &err) {
-    out = ColorSource{};
-    out.nclx = true;
-    if (primaries == 2) primaries = 1;  // unspecified: sRGB
-    if (transfer == 2) transfer = 13;
-    // chromaticities x y of R, G, B (H.273 table 2); the white is D65 for all three
-    double xy[6];
+// chromaticities x y of R, G, B (H.273 table 2; primaries 1, 9 or 12); the white is D65 for all three
+static bool nclx_xy(uint32_t primaries, double (&xy)[6]) {
     if (primaries == 1) {
         const double v[6] = {0.640, 0.330, 0.300, 0.600, 0.150, 0.060};
         std::memcpy(xy, v, sizeof(xy));
@@ -173,8 +168,33 @@ int nclx_source(uint32_t primaries, uint32_t transfer, ColorSource &out, std::st
         const double v[6] = {0.680, 0.320, 0.265, 0.690, 0.150, 0.060};
         std::memcpy(xy, v, sizeof(xy));
     } else {
-        return fail(HEIFGPU_E_UNSUPPORTED, err, "nclx: colour_primaries other than 1, 2, 9, 12");
+        return false;
     }
+    return true;
+}
+
+// chromaticities to XYZ: the columns P (x/y, 1, z/y), and the scales S that make R = G = B = 1
+// the D65 white W (the Y row of the RGB -> XYZ matrix is S itself)
+static bool nclx_xyz(const double (&xy)[6], double (&P)[9], double (&S)[3], double (&W)[3]) {
+    const double wx = 0.3127, wy = 0.3290;
+    W[0] = wx / wy, W[1] = 1.0, W[2] = (1.0 - wx - wy) / wy;
+    double Pi[9];
+    for (int c = 0; c < 3; ++c) {
+        const double x = xy[2 * c], y = xy[2 * c + 1];
+        P[c] = x / y, P[3 + c] = 1.0, P[6 + c] = (1.0 - x - y) / y;
+    }
+    if (!invert3(P, Pi)) return false;
+    for (int c = 0; c < 3; ++c) S[c] = Pi[3 * c] * W[0] + Pi[3 * c + 1] * W[1] + Pi[3 * c + 2] * W[2];
+    return true;
+}
+
+int nclx_source(uint32_t primaries, uint32_t transfer, ColorSource &out, std::string &err) {
+    out = ColorSource{};
+    out.nclx = true;
+    if (primaries == 2) primaries = 1;  // unspecified: sRGB
+    if (transfer == 2) transfer = 13;
+    double xy[6];
+    if (!nclx_xy(primaries, xy)) return fail(HEIFGPU_E_UNSUPPORTED, err, "nclx: colour_primaries other than 1, 2, 9, 12");
     out.primaries = primaries;
     switch (transfer) {
     case 1: case 6: case 13: case 14: case 15:
@@ -184,20 +204,13 @@ int nclx_source(uint32_t primaries, uint32_t transfer, ColorSource &out, std::st
     case 4:
         for (Trc &t : out.trc) t.kind = Trc::GAMMA, t.g = 2.2;
         break;
-    case 16: case 18: return fail(HEIFGPU_E_UNSUPPORTED, err, "nclx: PQ / HLG transfer needs tone mapping");
+    case 16: case 18:
+        return fail(HEIFGPU_E_UNSUPPORTED, err,
+                    "nclx: PQ / HLG transfer needs tone mapping (heifgpu_color_transform_make_hdr, tone_map=\"bt2390\")");
     default: return fail(HEIFGPU_E_UNSUPPORTED, err, "nclx: transfer_characteristics not supported");
     }
-    // chromaticities to XYZ: the columns (x/y, 1, z/y) scaled so that R = G = B = 1 is the white
-    const double wx = 0.3127, wy = 0.3290;
-    const double W[3] = {wx / wy, 1.0, (1.0 - wx - wy) / wy};
-    double P[9], Pi[9];
-    for (int c = 0; c < 3; ++c) {
-        const double x = xy[2 * c], y = xy[2 * c + 1];
-        P[c] = x / y, P[3 + c] = 1.0, P[6 + c] = (1.0 - x - y) / y;
-    }
-    if (!invert3(P, Pi)) return fail(HEIFGPU_E_PARSE, err, "nclx: singular primaries");
-    double S[3];
-    for (int c = 0; c < 3; ++c) S[c] = Pi[3 * c] * W[0] + Pi[3 * c + 1] * W[1] + Pi[3 * c + 2] * W[2];
+    double P[9], S[3], W[3];
+    if (!nclx_xyz(xy, P, S, W)) return fail(HEIFGPU_E_PARSE, err, "nclx: singular primaries");
     // Bradford from D65 to the ICC D50 white
     const double B[9] = {0.8951, 0.2664, -0.1614, -0.7502, 1.7135, 0.0367, 0.0389, -0.0685, 1.0296};
     const double D50[3] = {double(0xF6D6) / 65536.0, 1.0, double(0xD32D) / 65536.0};
@@ -281,6 +294,148 @@ int color_transform_build(const ColorSource &src, uint32_t dst, uint32_t bits, h
                                        color_xform_level(int64_t(kXfMatrixOne) * t.in_lut[c][v])) == uint32_t(v);
     t.identity = ident ? 1 : 0;
     return HEIFGPU_OK;
+}
+
+// ---- the tone stage of PQ / HLG sources (include/heifgpu.h, "HDR render") ----
+uint32_t hdr_transfer(const ColorDesc &c) {
+    return !c.has_icc && c.has_nclx && (c.transfer == 16 || c.transfer == 18) ? c.transfer : 0;
+}
+
+int hdr_read(const ColorDesc &c, HdrMeta &out, std::string &err) {
+    out = HdrMeta{};
+    int rc = HEIFGPU_OK;
+    if (c.has_clli) {
+        if (c.clli.size() < 4) {
+            rc = fail(HEIFGPU_E_PARSE, err, "clli: box shorter than its two fields");
+        } else {
+            out.max_cll = be16(c.clli.data());
+            out.max_fall = be16(c.clli.data() + 2);
+        }
+    }
+    if (c.has_mdcv) {
+        if (c.mdcv.size() < 24) {
+            rc = fail(HEIFGPU_E_PARSE, err, "mdcv: box shorter than its fields");
+        } else {
+            out.mastering_max = be32(c.mdcv.data() + 16);
+            out.mastering_min = be32(c.mdcv.data() + 20);
+        }
+    }
+    return rc;
+}
+
+double hdr_source_peak(uint32_t transfer, const HdrMeta &m, double peak_nits) {
+    if (transfer == 18) return 1000.0;  // HLG: the BT.2100 nominal display
+    double l = 1000.0;
+    if (peak_nits > 0.0) l = peak_nits;  // (a NaN is not: the file's then)
+    else if (m.max_cll) l = double(m.max_cll);
+    else if (m.mastering_max) l = double(m.mastering_max) * 1e-4;
+    return l < 203.0 ? 203.0 : l > 10000.0 ? 10000.0 : l;
+}
+
+namespace {
+// SMPTE ST 2084
+constexpr double kPqM1 = 2610.0 / 16384.0, kPqM2 = 2523.0 / 4096.0 * 128.0;
+constexpr double kPqC1 = 3424.0 / 4096.0, kPqC2 = 2413.0 / 4096.0 * 32.0, kPqC3 = 2392.0 / 4096.0 * 32.0;
+double pq_eotf(double e) {  // code value in [0, 1] to cd/m2
+    const double p = std::pow(e > 0.0 ? e : 0.0, 1.0 / kPqM2);
+    const double num = p - kPqC1 > 0.0 ? p - kPqC1 : 0.0;
+    return 10000.0 * std::pow(num / (kPqC2 - kPqC3 * p), 1.0 / kPqM1);
+}
+double pq_inverse(double nits) {
+    const double y = std::pow((nits > 0.0 ? nits : 0.0) / 10000.0, kPqM1);
+    return std::pow((kPqC1 + kPqC2 * y) / (1.0 + kPqC3 * y), kPqM2);
+}
+// BT.2100 HLG inverse OETF: signal in [0, 1] to scene light in [0, 1]
+double hlg_inverse_oetf(double x) {
+    const double a = 0.17883277, b = 1.0 - 4.0 * a, c = 0.5 - a * std::log(4.0 * a);
+    return x <= 0.5 ? x * x / 3.0 : (std::exp((x - c) / a) + b) / 12.0;
+}
+}  // namespace
+
+double hdr_eetf(double x, double lsrc) {
+    if (x > lsrc) x = lsrc;
+    const double n0 = pq_inverse(0.0), span = pq_inverse(lsrc) - n0;
+    const double e1 = (pq_inverse(x) - n0) / span, max_lum = (pq_inverse(203.0) - n0) / span;
+    const double ks = 1.5 * max_lum - 0.5;
+    if (e1 <= ks) return x;
+    const double t = (e1 - ks) / (1.0 - ks), t2 = t * t, t3 = t2 * t;
+    const double e2 = (2.0 * t3 - 3.0 * t2 + 1.0) * ks + (t3 - 2.0 * t2 + t) * (1.0 - ks) + (3.0 * t2 - 2.0 * t3) * max_lum;
+    return pq_eotf(e2 * span + n0);
+}
+
+int hdr_transform_build(uint32_t primaries, uint32_t transfer, double lsrc, uint32_t dst, uint32_t bits,
+                        heifgpu_hdr_transform &out, std::string &err) {
+    if (transfer != 16 && transfer != 18) return fail(HEIFGPU_E_INVALID, err, "tone transform of a transfer other than 16, 18");
+    if (!(lsrc >= 203.0 && lsrc <= 10000.0)) return fail(HEIFGPU_E_INVALID, err, "source peak outside 203..10000 cd/m2");
+    std::memset(&out, 0, sizeof(out));
+    // the matrix and out_lut: those of the same primaries coded linearly
+    ColorSource src;
+    if (int rc = nclx_source(primaries, 8, src, err)) return rc;
+    if (int rc = color_transform_build(src, dst, bits, out.base, err)) return rc;
+    std::memset(out.base.in_lut, 0, sizeof(out.base.in_lut));
+    out.base.identity = 0;
+    out.base.tone = HEIFGPU_TONE_BT2390;
+    out.transfer = transfer;
+    out.Lsrc = transfer == 18 ? 1000.0 : lsrc;
+    auto rhu = [](double v) { return std::floor(v + 0.5); };
+    const int n = 1 << bits, maxv = n - 1;
+    const double U = 65535.0;
+    for (int v = 0; v < n; ++v) {
+        const double x = double(v) / double(maxv);
+        const double nits = transfer == 16 ? pq_eotf(x) : 1000.0 * hlg_inverse_oetf(x);
+        const uint32_t l = uint32_t(rhu(U * nits / 203.0));
+        for (int c = 0; c < 3; ++c) out.in_lut32[c][v] = l < kXfToneMaxLevel ? l : kXfToneMaxLevel;
+    }
+    double xy[6], P[9], S[3], W[3];
+    if (!nclx_xy(src.primaries, xy) || !nclx_xyz(xy, P, S, W)) return fail(HEIFGPU_E_UNSUPPORTED, err, "nclx: primaries");
+    const double ssum = S[0] + S[1] + S[2];
+    int big = 0;
+    for (int c = 0; c < 3; ++c) {
+        out.w[c] = int32_t(rhu(S[c] / ssum * kXfMatrixOne));
+        if (out.w[c] > out.w[big]) big = c;
+    }
+    out.w[big] += kXfMatrixOne - (out.w[0] + out.w[1] + out.w[2]);
+    for (int k = 0; k < kXfToneEntries; ++k) {
+        const double yn = 203.0 * double(xf_tone_node(k)) / U;
+        double g;
+        if (transfer == 16) {
+            g = k == 0 ? 1.0 : hdr_eetf(yn, out.Lsrc) / yn;
+        } else if (k == 0) {
+            g = 0.0;
+        } else {
+            const double ys = yn / 1000.0, yd = 1000.0 * std::pow(ys, 1.2);
+            g = std::pow(ys, 0.2) * hdr_eetf(yd, 1000.0) / yd;
+        }
+        out.T[k] = uint32_t(rhu(double(1u << kXfToneShift) * (g < 1.0 ? g : 1.0)));
+    }
+    return HEIFGPU_OK;
+}
+
+int hdr_transform_make(const ColorDesc &c, uint32_t dst, uint32_t bits, uint32_t tone_map, double peak_nits,
+                       heifgpu_hdr_transform &out, std::string &err) {
+    if (tone_map > HEIFGPU_TONE_BT2390) return fail(HEIFGPU_E_INVALID, err, "tone_map");
+    const uint32_t transfer = tone_map ? hdr_transfer(c) : 0;
+    if (!transfer) {
+        std::memset(&out, 0, sizeof(out));
+        ColorSource src;
+        if (int rc = color_source(c, src, err)) return rc;
+        return color_transform_build(src, dst, bits, out.base, err);
+    }
+    HdrMeta meta;
+    if (int rc = hdr_read(c, meta, err)) return rc;
+    return hdr_transform_build(c.primaries, transfer, hdr_source_peak(transfer, meta, peak_nits), dst, bits, out, err);
+}
+
+bool hdr_transform_valid(const heifgpu_hdr_transform &t) {
+    if (t.base.bits < 8 || t.base.bits > 12) return false;
+    int64_t sum = 0;
+    for (int c = 0; c < 3; ++c) {
+        if (t.w[c] < 0) return false;
+        sum += t.w[c];
+        for (uint32_t v = 0; v < (1u << t.base.bits); ++v)
+            if (t.in_lut32[c][v] > kXfToneMaxLevel) return false;
+    }
+    return sum == kXfMatrixOne;
 }
 
 }  // namespace hg

@@ -16,6 +16,15 @@ struct ColorDesc {
     std::vector<uint8_t> icc;  // the 'prof' / 'rICC' payload (the first one), empty without
     bool has_icc = false, has_nclx = false;
     uint32_t primaries = 2, transfer = 2;  // of the nclx; 2 = unspecified
+    // the payloads of the item's first clli and mdcv boxes, kept unread (hdr_read)
+    std::vector<uint8_t> clli, mdcv;
+    bool has_clli = false, has_mdcv = false;
+};
+
+// what clli and mdcv say (include/heifgpu.h, "HDR render")
+struct HdrMeta {
+    uint32_t max_cll = 0, max_fall = 0;            // cd/m2
+    uint32_t mastering_max = 0, mastering_min = 0;  // 0.0001 cd/m2
 };
 
 // a tone reproduction curve, code value in [0, 1] to linear light
@@ -41,5 +50,26 @@ int color_source(const ColorDesc &c, ColorSource &out, std::string &err);
 // dst: HEIFGPU_CS_*; bits 8..12
 int color_transform_build(const ColorSource &src, uint32_t dst, uint32_t bits, heifgpu_color_transform &out,
                           std::string &err);
+
+
+// ---- the tone stage of PQ / HLG sources (include/heifgpu.h, "HDR render") ----
+// 16 or 18 when c is an nclx-defined PQ or HLG source (no profile), else 0
+uint32_t hdr_transfer(const ColorDesc &c);
+// HEIFGPU_OK, or HEIFGPU_E_PARSE for a box shorter than its fields (out holds what was read)
+int hdr_read(const ColorDesc &c, HdrMeta &out, std::string &err);
+// the source peak in cd/m2 by the rule of the header
+double hdr_source_peak(uint32_t transfer, const HdrMeta &m, double peak_nits);
+// BT.2390's EETF from a source peak lsrc to 203 cd/m2, cd/m2 in and out
+double hdr_eetf(double x, double lsrc);
+// the tone transform of an nclx source (primaries 1, 2, 9, 12; transfer 16, 18) at peak lsrc
+int hdr_transform_build(uint32_t primaries, uint32_t transfer, double lsrc, uint32_t dst, uint32_t bits,
+                        heifgpu_hdr_transform &out, std::string &err);
+// color_transform_build, or for an nclx PQ / HLG source under tone_map hdr_transform_build
+// at the peak the boxes and peak_nits give
+int hdr_transform_make(const ColorDesc &c, uint32_t dst, uint32_t bits, uint32_t tone_map, double peak_nits,
+                       heifgpu_hdr_transform &out, std::string &err);
+// whether a transform handed to heifgpu_color_apply or a render keeps the kernels'
+// reads inside the tables (in_lut32 below 2^22, w not negative and summing to 16384)
+bool hdr_transform_valid(const heifgpu_hdr_transform &t);
 
 }  // namespace hg

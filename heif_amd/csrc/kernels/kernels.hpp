@@ -133,6 +133,7 @@ inline void color_coefs(uint32_t matrix, bool full, ColorArgs &c) {
 // inside the w x h planes.
 enum : int { RENDER_RGB8 = 0, RENDER_RGBA8 = 1, RENDER_RGB16 = 2, RENDER_RGBA16 = 3 };
 constexpr int kRenderXf = 4;  // added to a kernel's format parameter: the colour-managed instantiation
+constexpr int kRenderTone = 8;  // added beside kRenderXf: the instantiation that also knows the tone stage of HDR sources
 constexpr int kRenderTile = 64;                   // axis-swapping images: 64 x 64 output pixels per workgroup
 constexpr int kRenderRowW = 256, kRenderRowH = 16;  // the others: 256 x 16
 struct RenderDesc {
@@ -250,11 +251,20 @@ inline int rs_subtile(const RsAxis &ax) {
 // image, in the same device array behind the call's descriptors.  lut addresses the
 // transform's tables in the context's cache, in_lut[3][n] (uint16) then 4096 words out_lut[i] | out_lut[i + 1] << 16;
 // 0 leaves the image as the unmanaged render writes it.  color_xform.hpp has the arithmetic.
+// A tone transform (tone != 0; read by the kRenderTone instantiations only, which a call
+// launches when one of its images has one) has other tables at lut: in_lut32[3][n]
+// (uint32), the same 4096 out_lut words, and tone_off bytes from lut a ToneBlock.
 struct ColorRef {
     uint64_t lut;
     int32_t n;     // 1 << B
     int32_t m[9];  // Q14
-    int32_t pad[2];
+    int32_t tone;      // HEIFGPU_TONE_*; 0 from every call without a tone transform
+    int32_t tone_off;  // bytes from lut to the ToneBlock (a multiple of 8)
+};
+struct ToneBlock {
+    int32_t w[3];  // Q14 luminance weights
+    int32_t pad;
+    uint32_t pairs[2 * 576];  // T[idx], T[idx + 1] for idx = 0 .. 575 (kXfTonePairs): one 8-byte gather
 };
 static_assert(sizeof(ColorRef) == 56, "ColorRef: a multiple of 8 bytes behind the descriptors");
 
@@ -332,19 +342,32 @@ void emu_sao_out(const BatchArgs &a);
 hipError_t launch_rbsp(const BatchArgs &a, hipStream_t s);
 hipError_t launch_ycbcr_rgb(const ColorArgs &c, int bytes_per_sample, hipStream_t s);
 hipError_t launch_gather_tiles(const GatherArgs &g, hipStream_t s);
-// one launch over (max_tiles, n_images); descs on the device.  color: the colour-managed
-// kernels, with a ColorRef per image behind the n_images descriptors (lut == 0: image i untouched)
+// one launch over (max_tiles, n_images); descs on the device.  color: RENDER_MANAGED, the
+// colour-managed kernels, with a ColorRef per image behind the n_images descriptors (lut == 0:
+// image i untouched), or RENDER_TONE, the kernels that also take ColorRefs with a tone stage
+enum : int { RENDER_PLAIN = 0, RENDER_MANAGED = 1, RENDER_TONE = 2 };
 // Desc: RenderDesc, ScaleDesc or TensorDesc (instantiated in render.hip)
 template <typename Desc>
-hipError_t launch_render(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, bool color,
+hipError_t launch_render(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, int color,
                          hipStream_t s);
 // (the two descriptors of k_render_resampled: specialised in resample.hip)
 template <>
 hipError_t launch_render<ResampleDesc>(const ResampleDesc *descs, int n_images, int max_tiles, int format,
-                                       int bytes_per_sample, bool color, hipStream_t s);
+                                       int bytes_per_sample, int color, hipStream_t s);
 template <>
 hipError_t launch_render<ResampleTensorDesc>(const ResampleTensorDesc *descs, int n_images, int max_tiles, int format,
-                                             int bytes_per_sample, bool color, hipStream_t s);
+                                             int bytes_per_sample, int color, hipStream_t s);
+// launch_render's for RENDER_TONE: the kRenderTone instantiations, code objects of their own
+// (render_tone.hip, resample_tone.hip)
+template <typename Desc>
+hipError_t launch_render_tone(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                              hipStream_t s);
+template <>
+hipError_t launch_render_tone<ResampleDesc>(const ResampleDesc *descs, int n_images, int max_tiles, int format,
+                                            int bytes_per_sample, hipStream_t s);
+template <>
+hipError_t launch_render_tone<ResampleTensorDesc>(const ResampleTensorDesc *descs, int n_images, int max_tiles,
+                                                  int format, int bytes_per_sample, hipStream_t s);
 hipError_t launch_parse(const BatchArgs &a, hipStream_t s);
 // (launch_parse's: the kernels of parse_solo.hip and parse_lean.hip)
 hipError_t launch_parse_solo(const BatchArgs &a, hipStream_t s);

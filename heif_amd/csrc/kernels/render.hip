@@ -45,6 +45,13 @@
 // through LDS: k_render's axis-keeping path has no barrier to stage behind, and
 // the 16-bit formats already sit at the LDS occupancy limit.  The unmanaged
 // kernels are the XF = false instantiations under their old names and arguments.
+//
+// The HDR render adds one more bit, kRenderTone: the instantiations that a call launches
+// when one of its images has a tone transform (ColorRef::tone; include/heifgpu.h "HDR
+// render").  Such an image's RGB triples go through color_tone_px (wide input table,
+// luminance, one 8-byte gather of the gain pair, three 64-bit products, then the same
+// matrix and out_lut); the others of the batch take the managed or unmanaged path by a
+// uniform branch.  Those instantiations are compiled from this file as render_tone.hip.
 #include <type_traits>
 
 #include "color_xform.hpp"
@@ -62,6 +69,7 @@ template <typename Pel, int FMTX>
 __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
     constexpr int FMT = FMTX & 3;
     constexpr bool XF = (FMTX & kRenderXf) != 0;
+    constexpr bool TONE = (FMTX & kRenderTone) != 0;  // (with XF: an image's ColorRef may carry a tone stage)
     constexpr bool WIDE = FMT >= RENDER_RGB16;
     constexpr int T = kRenderTile, LP = kRenderTile + 1;  // LDS pitch in dwords: 65, not 64 (bank conflicts)
     __shared__ uint32_t tile_lds[(WIDE ? 2 : 1) * T * LP];
@@ -83,6 +91,7 @@ __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
         }
     }
 #endif
+    const ToneW tw = tone_weights<TONE>(x);
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int tx = (int)blockIdx.x % d.tiles_x, ty = (int)blockIdx.x / d.tiles_x;
     const Px none = {0, 0};
@@ -95,7 +104,7 @@ __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
             if (oy >= d.out_h) break;
             Px p = valid ? convert<Pel, FMT>(d, ox, oy) : none;
             if constexpr (XF) {
-                if (x.lut) xform_pixel<FMT>(x, p, staged);  // (uniform: the image's transform, or none)
+                if (x.lut) xform_pixel<FMT, TONE>(x, p, staged, tw);  // (uniform: the image's transform, or none)
             }
             store_row<FMT>(d, oy, oxw, lane, p, valid);
         }
@@ -108,7 +117,7 @@ __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
         if (ox < d.out_w && oy < d.out_h) {
             Px p = convert<Pel, FMT>(d, ox, oy);
             if constexpr (XF) {
-                if (x.lut) xform_pixel<FMT>(x, p, staged);
+                if (x.lut) xform_pixel<FMT, TONE>(x, p, staged, tw);
             }
             tile_lds[oxl * LP + lane] = p.lo;
             if (WIDE) tile_lds[T * LP + oxl * LP + lane] = p.hi;
@@ -274,6 +283,7 @@ template <typename Pel, int FMTX, typename Desc>
 __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
     constexpr int FMT = FMTX & 3;
     constexpr bool XF = (FMTX & kRenderXf) != 0;  // (as k_render's)
+    constexpr bool TONE = (FMTX & kRenderTone) != 0;
     constexpr bool TENSOR = std::is_same<Desc, TensorDesc>::value;  // (else ScaleDesc: the integer surfaces)
     constexpr bool WIDE = FMT >= RENDER_RGB16;
     constexpr int NCH = (FMT & 1) ? 4 : 3;
@@ -356,12 +366,13 @@ __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
         // the transform of the tile's rounded averages, in place in the result tile
         const ColorRef x = reinterpret_cast<const ColorRef *>(descs + gridDim.y)[blockIdx.y];
         if (x.lut) {  // (uniform)
+            const ToneW tw = tone_weights<TONE>(x);
             const int nbv = b1 - b0, cnt = (a1 - a0) * nbv;
             for (int idx = t; idx < cnt; idx += 256) {
                 const int al = idx / nbv, at = al * lp + (idx - al * nbv);
                 Px p = {res[at], WIDE ? res[RES + at] : 0u};
                 uint32_t R = px_channel<FMT>(p, 0), G = px_channel<FMT>(p, 1), B = px_channel<FMT>(p, 2);
-                xform_rgb(x, R, G, B);
+                xform_any<TONE>(x, tw, R, G, B);
                 if (WIDE) {
                     res[at] = R | (G << 16);
                     res[RES + at] = B | (p.hi & 0xffff0000u);
@@ -430,23 +441,45 @@ void launch_fmt(const Desc *descs, dim3 grid, int format, hipStream_t s) {
 
 // The kernels lie in the code object in the order of these instantiations: the order the
 // six launchers before this one gave them, so that a build still compares byte for
-// byte with the earlier ones (tools/kernel_text_diff.py).
+// byte with the earlier ones (tools/kernel_text_diff.py).  The tone
+// instantiations are a code object of their own, render_tone.hip, which is this file
+// compiled with HG_RENDER_TONE_UNIT: this unit's kernels stay what they were.
 #define HG_LAUNCH_FMT(XF, Desc)                                                   \
     template void launch_fmt<uint8_t, XF>(const Desc *, dim3, int, hipStream_t); \
     template void launch_fmt<uint16_t, XF>(const Desc *, dim3, int, hipStream_t)
+#if defined(HG_RENDER_TONE_UNIT)
+HG_LAUNCH_FMT(kRenderXf | kRenderTone, RenderDesc);
+HG_LAUNCH_FMT(kRenderXf | kRenderTone, ScaleDesc);
+HG_LAUNCH_FMT(kRenderXf | kRenderTone, TensorDesc);
+#else
 HG_LAUNCH_FMT(0, ScaleDesc);
 HG_LAUNCH_FMT(0, TensorDesc);
 HG_LAUNCH_FMT(kRenderXf, RenderDesc);
 HG_LAUNCH_FMT(kRenderXf, ScaleDesc);
 HG_LAUNCH_FMT(kRenderXf, TensorDesc);
 HG_LAUNCH_FMT(0, RenderDesc);
+#endif
 #undef HG_LAUNCH_FMT
 
 }  // namespace
 
+#if defined(HG_RENDER_TONE_UNIT)
 template <typename Desc>
-hipError_t launch_render(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, bool color,
+hipError_t launch_render_tone(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                              hipStream_t s) {
+    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
+    if (bytes_per_sample == 1) launch_fmt<uint8_t, kRenderXf | kRenderTone>(descs, grid, format, s);
+    else launch_fmt<uint16_t, kRenderXf | kRenderTone>(descs, grid, format, s);
+    return hipGetLastError();
+}
+template hipError_t launch_render_tone(const RenderDesc *, int, int, int, int, hipStream_t);
+template hipError_t launch_render_tone(const ScaleDesc *, int, int, int, int, hipStream_t);
+template hipError_t launch_render_tone(const TensorDesc *, int, int, int, int, hipStream_t);
+#else
+template <typename Desc>
+hipError_t launch_render(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, int color,
                          hipStream_t s) {
+    if (color == RENDER_TONE) return launch_render_tone(descs, n_images, max_tiles, format, bytes_per_sample, s);
     const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
     if (bytes_per_sample == 1) {
         if (color) launch_fmt<uint8_t, kRenderXf>(descs, grid, format, s);
@@ -457,9 +490,10 @@ hipError_t launch_render(const Desc *descs, int n_images, int max_tiles, int for
     }
     return hipGetLastError();
 }
-template hipError_t launch_render(const RenderDesc *, int, int, int, int, bool, hipStream_t);
-template hipError_t launch_render(const ScaleDesc *, int, int, int, int, bool, hipStream_t);
-template hipError_t launch_render(const TensorDesc *, int, int, int, int, bool, hipStream_t);
+template hipError_t launch_render(const RenderDesc *, int, int, int, int, int, hipStream_t);
+template hipError_t launch_render(const ScaleDesc *, int, int, int, int, int, hipStream_t);
+template hipError_t launch_render(const TensorDesc *, int, int, int, int, int, hipStream_t);
+#endif
 #endif
 
 }  // namespace hg

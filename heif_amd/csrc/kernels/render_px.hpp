@@ -4,6 +4,7 @@
 // (interleaved integers) and store_tensor (scaled and biased floats).  render.hip's
 // opening comment describes them.  Device code only; every kernel's unit gets its own copy.
 #pragma once
+#include <cstddef>
 #include <type_traits>
 
 #include "color_xform.hpp"
@@ -40,6 +41,50 @@ __device__ __forceinline__ void xform_rgb(const ColorRef &x, uint32_t &R, uint32
     const XfLut in = (XfLut)x.lut;
     const XfOutPairs<XfWords> out{(XfWords)(x.lut + 6 * (uint64_t)x.n)};
     color_xform_px(in, x.n, out, x.m, R, G, B);
+}
+
+// ---- the tone stage (the kRenderTone instantiations; x.tone != 0) ----
+// what a workgroup keeps of its image's ToneBlock in registers: the luminance weights,
+// read once before the workgroup's first store (scalar loads)
+struct ToneW {
+    int32_t w[3];
+};
+template <bool TONE>
+__device__ __forceinline__ ToneW tone_weights(const ColorRef &x) {
+    ToneW t = {{0, 0, 0}};
+    if constexpr (TONE) {
+        if (x.tone) {  // (uniform)
+            typedef const int32_t __attribute__((address_space(1))) *Words;
+            const Words p = (Words)(x.lut + (uint64_t)x.tone_off);
+            t.w[0] = p[0], t.w[1] = p[1], t.w[2] = p[2];
+        }
+    }
+    return t;
+}
+
+// xform_rgb for an image with a tone stage: in_lut32, the luminance, the gain pair
+// (one 8-byte gather), then the matrix and out_lut as ever: seven gathers per pixel
+__device__ __forceinline__ void tone_rgb(const ColorRef &x, const ToneW &tw, uint32_t &R, uint32_t &G, uint32_t &B) {
+    typedef const uint32_t __attribute__((address_space(1))) *XfWords;
+    typedef uint32_t XfPair __attribute__((ext_vector_type(2)));
+    typedef const XfPair __attribute__((address_space(1))) *XfPairs;
+    const XfWords in = (XfWords)x.lut;
+    const XfOutPairs<XfWords> out{(XfWords)(x.lut + 12 * (uint64_t)x.n)};
+    const XfTonePairs<XfPairs> tone{(XfPairs)(x.lut + (uint64_t)x.tone_off + offsetof(ToneBlock, pairs))};
+    color_tone_px(in, x.n, tw.w, tone, out, x.m, R, G, B);
+}
+
+// the transform of one RGB triple by whichever of the two the image has (a uniform branch)
+template <bool TONE>
+__device__ __forceinline__ void xform_any(const ColorRef &x, const ToneW &tw, uint32_t &R, uint32_t &G, uint32_t &B,
+                                          const uint16_t *staged = nullptr) {
+    if constexpr (TONE) {
+        if (x.tone) {
+            tone_rgb(x, tw, R, G, B);
+            return;
+        }
+    }
+    xform_rgb(x, R, G, B, staged);
 }
 
 template <typename Pel, int FMT>
@@ -133,12 +178,12 @@ __device__ __forceinline__ void store_row(const RenderDesc &d, int oy, int oxw, 
 }
 
 // the transform of a converted pixel, in place (alpha kept)
-template <int FMT>
-__device__ __forceinline__ void xform_pixel(const ColorRef &x, Px &p, const uint16_t *staged) {
+template <int FMT, bool TONE = false>
+__device__ __forceinline__ void xform_pixel(const ColorRef &x, Px &p, const uint16_t *staged, const ToneW &tw = ToneW{}) {
     uint32_t R, G, B;
     if (FMT >= RENDER_RGB16) R = p.lo & 0xffffu, G = p.lo >> 16, B = p.hi & 0xffffu;
     else R = p.lo & 0xffu, G = (p.lo >> 8) & 0xffu, B = (p.lo >> 16) & 0xffu;
-    xform_rgb(x, R, G, B, staged);
+    xform_any<TONE>(x, tw, R, G, B, staged);
     if (FMT >= RENDER_RGB16) p = {R | (G << 16), B | (p.hi & 0xffff0000u)};
     else p = {R | (G << 8) | (B << 16) | (p.lo & 0xff000000u), 0};
 }

@@ -95,6 +95,7 @@ template <typename Pel, int FMTX, typename Desc>
 __global__ void __launch_bounds__(256) k_render_resampled(const Desc *descs) {
     constexpr int FMT = FMTX & 3;
     constexpr bool XF = (FMTX & kRenderXf) != 0;  // (as k_render's)
+    constexpr bool TONE = (FMTX & kRenderTone) != 0;
     constexpr bool TENSOR = std::is_same<Desc, ResampleTensorDesc>::value;
     constexpr bool WIDE = FMT >= RENDER_RGB16;
     constexpr int NCH = (FMT & 1) ? 4 : 3;
@@ -290,11 +291,12 @@ __global__ void __launch_bounds__(256) k_render_resampled(const Desc *descs) {
         // the transform of the tile's rounded results, in place (as k_render_scaled's)
         const ColorRef x = reinterpret_cast<const ColorRef *>(descs + gridDim.y)[blockIdx.y];
         if (x.lut) {  // (uniform)
+            const ToneW tw = tone_weights<TONE>(x);
             for (int idx = t; idx < ny * TW; idx += 256) {
                 if ((idx & (TW - 1)) >= nx) continue;
                 Px v = {res[idx], WIDE ? res[TH * TW + idx] : 0u};
                 uint32_t R = px_channel<FMT>(v, 0), G = px_channel<FMT>(v, 1), B = px_channel<FMT>(v, 2);
-                xform_rgb(x, R, G, B);
+                xform_any<TONE>(x, tw, R, G, B);
                 if (WIDE) {
                     res[idx] = R | (G << 16);
                     res[TH * TW + idx] = B | (v.hi & 0xffff0000u);
@@ -332,9 +334,11 @@ void launch_fmt(const Desc *descs, dim3 grid, int format, hipStream_t s) {
     }
 }
 
+#if !defined(HG_RENDER_TONE_UNIT)
 template <typename Desc>
-hipError_t launch_resampled(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, bool color,
+hipError_t launch_resampled(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, int color,
                             hipStream_t s) {
+    if (color == RENDER_TONE) return launch_render_tone(descs, n_images, max_tiles, format, bytes_per_sample, s);
     const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
     if (bytes_per_sample == 1) {
         if (color) launch_fmt<uint8_t, kRenderXf>(descs, grid, format, s);
@@ -345,19 +349,44 @@ hipError_t launch_resampled(const Desc *descs, int n_images, int max_tiles, int 
     }
     return hipGetLastError();
 }
+#else
+// (resample_tone.hip: this file compiled with HG_RENDER_TONE_UNIT, the tone instantiations
+// as a code object of their own, so that this unit's kernels stay what they were)
+template <typename Desc>
+hipError_t launch_resampled_tone(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                                 hipStream_t s) {
+    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
+    if (bytes_per_sample == 1) launch_fmt<uint8_t, kRenderXf | kRenderTone>(descs, grid, format, s);
+    else launch_fmt<uint16_t, kRenderXf | kRenderTone>(descs, grid, format, s);
+    return hipGetLastError();
+}
+#endif
 
 }  // namespace
 
+#if !defined(HG_RENDER_TONE_UNIT)
 template <>
 hipError_t launch_render<ResampleDesc>(const ResampleDesc *descs, int n_images, int max_tiles, int format,
-                                       int bytes_per_sample, bool color, hipStream_t s) {
+                                       int bytes_per_sample, int color, hipStream_t s) {
     return launch_resampled(descs, n_images, max_tiles, format, bytes_per_sample, color, s);
 }
 template <>
 hipError_t launch_render<ResampleTensorDesc>(const ResampleTensorDesc *descs, int n_images, int max_tiles, int format,
-                                             int bytes_per_sample, bool color, hipStream_t s) {
+                                             int bytes_per_sample, int color, hipStream_t s) {
     return launch_resampled(descs, n_images, max_tiles, format, bytes_per_sample, color, s);
 }
+#else
+template <>
+hipError_t launch_render_tone<ResampleDesc>(const ResampleDesc *descs, int n_images, int max_tiles, int format,
+                                            int bytes_per_sample, hipStream_t s) {
+    return launch_resampled_tone(descs, n_images, max_tiles, format, bytes_per_sample, s);
+}
+template <>
+hipError_t launch_render_tone<ResampleTensorDesc>(const ResampleTensorDesc *descs, int n_images, int max_tiles,
+                                                  int format, int bytes_per_sample, hipStream_t s) {
+    return launch_resampled_tone(descs, n_images, max_tiles, format, bytes_per_sample, s);
+}
+#endif
 #endif
 
 }  // namespace hg

@@ -389,6 +389,23 @@ def icc_box(profile: bytes, kind: bytes = b"prof") -> bytes:
     return _box(b"colr", kind + profile)
 
 
+def clli_box(max_cll: int, max_fall: int, truncate: Optional[int] = None) -> bytes:
+    """ContentLightLevelBox (a plain box): MaxCLL and MaxFALL in cd/m2.  An item
+    property: it rides in `transforms=`.  truncate = n keeps only the first n
+    payload bytes (a box shorter than its fields)."""
+    return _box(b"clli", struct.pack(">HH", max_cll, max_fall)[:truncate])
+
+
+def mdcv_box(primaries=((0.708, 0.292), (0.170, 0.797), (0.131, 0.046)), white=(0.3127, 0.3290),
+             max_nits: float = 1000.0, min_nits: float = 0.005, truncate: Optional[int] = None) -> bytes:
+    """MasteringDisplayColourVolumeBox (a plain box): the primaries and the white
+    point as chromaticities (stored in units of 0.00002), the maximum and minimum
+    luminance in cd/m2 (stored in units of 0.0001).  An item property like clli_box."""
+    xy = [int(round(v / 0.00002)) for p in tuple(primaries) + (white,) for v in p]
+    payload = struct.pack(">8H", *xy) + struct.pack(">II", int(round(max_nits * 10000)), int(round(min_nits * 10000)))
+    return _box(b"mdcv", payload[:truncate])
+
+
 def _colr_boxes(colr) -> List[bytes]:
     """colr= of display_heic / grid_heic: None, one box, or a sequence of boxes."""
     if not colr:

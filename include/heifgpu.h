@@ -431,8 +431,9 @@ int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *im
  *   chromaticities to XYZ, Bradford-adapted to the ICC D50 white (s15.16 F6D6
  *   10000 D32D), in double.  Transfer 1, 6, 13, 14, 15: the sRGB curve (709-coded
  *   stills are shown as sRGB, as browsers and libheif show them); 8: linear; 4:
- *   gamma 2.2; 16 (PQ) and 18 (HLG) need tone mapping and every other code is
- *   HEIFGPU_E_UNSUPPORTED.
+ *   gamma 2.2; 16 (PQ) and 18 (HLG) need tone mapping, which
+ *   heifgpu_color_transform_make_hdr (below, "HDR render") gives on request: here
+ *   they, and every other code, are HEIFGPU_E_UNSUPPORTED.
  * THE DESTINATIONS both encode with the sRGB curve g; colourants (X Y Z, s15.16):
  *   HEIFGPU_CS_SRGB        R 6FA2 38F5 0390      G 6299 B785 18DA   B 24A0 0F84 B6CF
  *   HEIFGPU_CS_DISPLAY_P3  R 83DF 3DBF FFFFFFBB  G 4ABF B137 0AB9   B 2838 110B C8B9
@@ -477,7 +478,7 @@ typedef struct {
     uint32_t bits;                    /* B */
     uint32_t identity;
     uint32_t dst;                     /* HEIFGPU_CS_* */
-    uint32_t reserved;
+    uint32_t tone;                    /* 0 from every call but heifgpu_color_transform_make_hdr: HEIFGPU_TONE_* */
     int32_t m[9];
     int32_t m_rounded[9];             /* m before the row fix-up (informative) */
     uint16_t in_lut[3][4096];         /* the first 1 << B entries of each are used */
@@ -526,6 +527,90 @@ int heifgpu_render_batch_tensor_color(heifgpu_ctx *ctx, const heifgpu_image *con
                                       const uint32_t *flip,
                                       const heifgpu_color_transform *const *xf,
                                       const heifgpu_tensor_surface *out, void *stream);
+
+/* ---- HDR render: opt-in BT.2390 tone mapping of PQ and HLG sources -----------
+ * (added within ABI 6: new entry points only; no struct above changes its layout.)
+ * Without the calls below nothing changes: a PQ / HLG source is refused as above.
+ *
+ * WHAT THE FILE CARRIES.  Two more item properties of the decoded item are kept, the
+ * first of each kind (plain boxes, not FullBoxes):
+ *   clli  u16 max_content_light_level (MaxCLL), u16 max_pic_average_light_level (MaxFALL), cd/m2
+ *   mdcv  3 x (u16 x, u16 y) primaries, u16 x 2 white point, u32 max and u32 min
+ *         display mastering luminance in 0.0001 cd/m2
+ * A box shorter than its fields (4 and 24 bytes) is HEIFGPU_E_PARSE when a tone
+ * transform is asked for, never at parse or decode (the rule of the ICC profiles).
+ * WHEN IT APPLIES.  The item's colour space is defined by an nclx (no ICC profile: a
+ * profile still wins and gets no tone stage) of primaries 1, 2 (taken as 1), 9 or 12
+ * and transfer 16 (PQ, SMPTE ST 2084) or 18 (HLG, ARIB STD-B67 / BT.2100).  For every
+ * other image heifgpu_color_transform_make_hdr gives exactly what
+ * heifgpu_color_transform_make gives (tone == 0), errors included.
+ * THE PEAKS.  Source peak Lsrc in cd/m2: peak_nits if > 0, else MaxCLL if non-zero,
+ * else the mdcv maximum if non-zero, else 1000; clamped to [203, 10000].  HLG always
+ * uses the BT.2100 nominal display, Lw = 1000 cd/m2 and system gamma 1.2: its Lsrc is
+ * 1000 whatever the file or the caller says.  The destination peak is the SDR
+ * reference white of BT.2408, 203 cd/m2; black is 0 on both sides.
+ * THE TONE STAGE sits between in_lut and the matrix; everything from the matrix on
+ * is the transform above, unchanged (m = inv(Dst) * Src of the nclx primaries, rows
+ * normalised, Q14; out_lut).  U = 65535 stands for 203 cd/m2.
+ *   in_lut32[c][v] = round_half_up(U * F(v / maxv) / 203)                      (u32, < 2^22)
+ *       PQ:  F = the ST 2084 EOTF in cd/m2 (at most 10000)
+ *       HLG: F = 1000 * E, E the BT.2100 HLG inverse OETF (scene light, before the OOTF)
+ *   w[3]: the Y row of the source primaries' RGB -> XYZ matrix (D65, from the
+ *       chromaticities) divided by its sum, in Q14 rounded to nearest, the largest
+ *       entry then adjusted so that the three sum to 16384 exactly
+ *   Y = (w0*L0 + w1*L1 + w2*L2 + 8192) >> 14                                   (64-bit sum)
+ *   the gain g(Y), a table on a floating index (32 nodes per octave from 64 on):
+ *       Y < 64:  g = T[Y]
+ *       else     e = bitlength(Y) - 6, idx = 32 + 32 e + ((Y >> e) - 32), frac = Y & ((1 << e) - 1)
+ *                g = (T[idx] * ((1 << e) - frac) + T[idx + 1] * frac + (1 << (e - 1))) >> e   (64 bits)
+ *       T: 577 u32 entries, node k at Y_k = k for k < 64, else (32 + ((k - 32) & 31)) << ((k - 32) >> 5)
+ *       T[k] = round_half_up(2^24 * min(G(Y_k), 1)), with Yn = 203 * Y_k / U (cd/m2)
+ *       (24 fractional bits: G falls to 203 / 12992 = 0.016, where 16 bits left a relative
+ *       step of 5e-4 and more than one 8-bit code of error on a saturated dark channel):
+ *       PQ:  G = EETF(Yn) / Yn, G(0) = 1
+ *       HLG: Ys = Yn / 1000, Yd = 1000 * Ys^1.2, G = Ys^0.2 * EETF(Yd) / Yd, G(0) = 0
+ *            (the BT.2100 OOTF on luminance, then the same tone curve at Lsrc = 1000)
+ *       EETF is BT.2390's (5.4.1), in double.  With N the ST 2084 inverse EOTF of x / 10000:
+ *            E1 = (N(min(x, Lsrc)) - N(0)) / (N(Lsrc) - N(0)),   maxLum = (N(203) - N(0)) / (N(Lsrc) - N(0))
+ *            KS = 1.5 maxLum - 0.5;  E1 <= KS: EETF(x) = min(x, Lsrc) itself;  else with t = (E1 - KS) / (1 - KS)
+ *            E2 = (2t^3 - 3t^2 + 1) KS + (t^3 - 2t^2 + t)(1 - KS) + (3t^2 - 2t^3) maxLum
+ *            EETF(x) = EOTF(E2 (N(Lsrc) - N(0)) + N(0));  no black lift (minLum = 0); inputs above Lsrc clip to it
+ *   L''_c = min((L_c * g + 2^23) >> 24, 65535)                                  (64-bit product)
+ *   then L'_k, i, f and out_k of the transform above, with L'' in the place of L.
+ * Out-of-gamut results clip at the existing clamp (no gamut mapping).  A tone
+ * transform is never an identity.  numpy reproduces this bit for bit
+ * (tests/tone_ref.py); kernels/color_xform.hpp is its one statement in code. */
+enum { HEIFGPU_TONE_NONE = 0, HEIFGPU_TONE_BT2390 = 1 };
+enum { HEIFGPU_HDR_HAS_CLLI = 1, HEIFGPU_HDR_HAS_MDCV = 2 };
+#define HEIFGPU_TONE_ENTRIES 577
+typedef struct {
+    uint32_t transfer;                /* 16 (PQ), 18 (HLG); 0: not an nclx-defined PQ / HLG item */
+    uint32_t present;                 /* HEIFGPU_HDR_HAS_* of the boxes the item carries */
+    uint32_t max_cll, max_fall;       /* clli, cd/m2; 0 without the box (or for a short one) */
+    uint32_t mastering_max, mastering_min;  /* mdcv, 0.0001 cd/m2; 0 without the box (or for a short one) */
+    int32_t status;                   /* HEIFGPU_OK, or what a tone transform of this item answers */
+    uint32_t reserved;
+} heifgpu_hdr_info;
+typedef struct {
+    heifgpu_color_transform base;     /* base.tone != 0; base.in_lut is not used (zeros) */
+    uint32_t in_lut32[3][4096];       /* the first 1 << B entries of each are used */
+    int32_t w[3];
+    uint32_t transfer;                /* 16 or 18 */
+    uint32_t T[HEIFGPU_TONE_ENTRIES + 1];  /* 577 used */
+    double Lsrc;                      /* cd/m2, as used */
+} heifgpu_hdr_transform;
+/* host only, always HEIFGPU_OK for a parsed image */
+int heifgpu_image_get_hdr(const heifgpu_image *img, heifgpu_hdr_info *out);
+/* host only: heifgpu_color_transform_make with a tone stage on request.  tone_map
+ * HEIFGPU_TONE_NONE: out->base is what heifgpu_color_transform_make gives, the rest
+ * zeros.  HEIFGPU_TONE_BT2390: the same for every image but an nclx-defined PQ / HLG
+ * one, whose tone transform is made (peak_nits <= 0: from the file).  A transform
+ * whose base.tone is non-zero is passed on as &out->base: heifgpu_color_apply and
+ * every render that takes heifgpu_color_transform pointers read the whole
+ * heifgpu_hdr_transform behind such a pointer.  Still one descriptor copy and one
+ * launch per render call, whatever the mix of tone, managed and unmanaged images. */
+int heifgpu_color_transform_make_hdr(const heifgpu_image *img, uint32_t dst, uint32_t bits, uint32_t tone_map,
+                                     double peak_nits, heifgpu_hdr_transform *out);
 
 /* ---- window decode: decode only the pictures a window reads ----------------
  * (added within ABI 6: new entry points only; heifgpu_batch_opts keeps its layout.)

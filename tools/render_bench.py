@@ -65,8 +65,17 @@ The condition of 5.27: each filtered cell faster than its box's torch route by
 more than the larger spread (max - min over runs) of the two; the ratios to the
 area render and to `full` are reported, not gated.
 
+--tone measures the tone stage of the HDR render (heifgpu_color_transform_make_hdr,
+DESIGN 5.28): a 10-bit batch labelled BT.2020 PQ, to sRGB with tone_map bt2390,
+against the same planes labelled BT.2020 gamma 2.2 (managed, no tone stage), the
+variants alternated in one process in each of the --runs runs:
+  rgb8            heifgpu_render_batch_color RGB8 at full size
+  rgba16          the same in RGBA16
+  tensor224_f16   heifgpu_render_batch_tensor_color, COVER to 224 x 224, f16 CHW
+each as `managed` and as `tone`; tone / managed is reported.
+
 usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json]
-                                    [--scaled | --tensor | --color | --filter]
+                                    [--scaled | --tensor | --color | --filter | --tone]
 """
 import argparse
 import ctypes
@@ -434,6 +443,98 @@ def color_main(args):
         pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
 
 
+def tone_main(args):
+    n = args.images
+    dev = torch.device("cuda", 0)
+    ctx = H.DecodeContext(0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    g = torch.Generator(device=dev).manual_seed(1)
+    p10 = S.SynthParams(bit_depth=10)
+    pics = [S.picture(p10, 1)] * 48  # (only the host parse is needed: the planes below are random)
+    sources = {"managed": S.nclx_box(9, 4, 9, False), "tone": S.nclx_box(9, 16, 9, False)}
+    imgs = {k: H.HeifImage.parse(S.grid_heic(W, HGT, p10, pictures=pics, colr=c)) for k, c in sources.items()}
+    ys = [torch.randint(0, 1024, (HGT, W), generator=g, device=dev, dtype=torch.int32).to(torch.int16) for _ in range(n)]
+    cs = [[torch.randint(0, 1024, (HGT // 2, W // 2), generator=g, device=dev, dtype=torch.int32).to(torch.int16)
+           for _ in range(n)] for _ in range(2)]
+    planes = (_lib.Planes * n)()
+    for i in range(n):
+        for c, t in enumerate((ys[i], cs[0][i], cs[1][i])):
+            planes[i].plane[c] = t.data_ptr()
+            planes[i].pitch[c] = t.stride(0) * t.element_size()
+    xfs = {}
+    for bits in (8, 10):
+        xfs["managed", bits] = imgs["managed"].color_transform("srgb", bits)
+        xfs["tone", bits] = imgs["tone"].color_transform("srgb", bits, "bt2390")
+        assert not xfs["managed", bits].tone and xfs["tone", bits].tone
+
+    def handles(kind, bits):
+        return ((ctypes.c_void_p * n)(*[imgs[kind]._h.value] * n), (ctypes.c_void_p * n)(*[ctypes.addressof(xfs[kind, bits])] * n))
+
+    px = n * W * HGT
+    result = {"images": n, "width": W, "height": HGT, "reps": args.reps, "runs": args.runs,
+              "device": torch.cuda.get_device_name(0), "hbm_peak_GBps": HBM_PEAK_GBS, "library": _lib.LIB_PATH.name,
+              "managed": "10-bit BT.2020 gamma 2.2 -> sRGB", "tone": "10-bit BT.2020 PQ -> sRGB, bt2390, Lsrc 1000",
+              "cases": {}}
+    out8 = [torch.empty((HGT, W, 3), dtype=torch.uint8, device=dev) for _ in range(n)]
+    out16 = [torch.empty((HGT, W, 4), dtype=torch.int16, device=dev) for _ in range(n)]
+    surf8, surf16 = (_lib.Surface * n)(), (_lib.Surface * n)()
+    for i in range(n):
+        surf8[i].pixels, surf8[i].pitch = out8[i].data_ptr(), out8[i].stride(0)
+        surf16[i].pixels, surf16[i].pitch = out16[i].data_ptr(), out16[i].stride(0) * 2
+    d = imgs["tone"].display
+    sc = (_lib.Scale * n)()
+    for i in range(n):
+        _lib.check(_lib.lib.heifgpu_scale_fit(ctypes.byref(d), 224, 224, _lib.FIT_COVER, ctypes.byref(sc[i])))
+    tout = torch.empty((n, 3, 224, 224), dtype=torch.float16, device=dev)
+    fmt = _lib.TensorFormat(src=_lib.PIX_RGB8, elem=_lib.ELEM_F16, layout=_lib.LAYOUT_CHW)
+    for c, (m_, s_) in enumerate(zip((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))):
+        fmt.a[c], fmt.b[c] = 1.0 / (255.0 * s_), -m_ / s_
+    ts = (_lib.TensorSurface * n)()
+    for i in range(n):
+        ts[i].data, ts[i].stride_c, ts[i].stride_y = tout[i].data_ptr(), 224 * 224 * 2, 224 * 2
+    window_px = (sc[0].width or d.out_width) * (sc[0].height or d.out_height)
+
+    variants, keep = [], []
+    for kind in ("managed", "tone"):
+        h8, h10 = handles(kind, 8), handles(kind, 10)
+        keep += [h8, h10]
+
+        def rgb8(h=h8):
+            _lib.check(_lib.lib.heifgpu_render_batch_color(ctx._h, h[0], n, planes, None, None, _lib.PIX_RGB8, h[1], surf8, stream))
+
+        def rgba16(h=h10):
+            _lib.check(_lib.lib.heifgpu_render_batch_color(ctx._h, h[0], n, planes, None, None, _lib.PIX_RGBA16, h[1], surf16,
+                                                           stream))
+
+        def tensor(h=h8):
+            _lib.check(_lib.lib.heifgpu_render_batch_tensor_color(ctx._h, h[0], n, planes, None, None, ctypes.byref(fmt), sc,
+                                                                  None, h[1], ts, stream))
+        variants += [("rgb8", kind, rgb8, px * 6.0), ("rgba16", kind, rgba16, px * 11.0),
+                     ("tensor224_f16", kind, tensor, n * (window_px * 3.0 + 224 * 224 * 6))]
+    for *_, fn, _ in variants:  # warm-up (and the tables' one upload)
+        fn()
+    torch.cuda.synchronize()
+    ms = {(name, kind): [] for name, kind, _, _ in variants}
+    for _ in range(args.runs):
+        for name, kind, fn, _ in variants:
+            ms[(name, kind)].append(timed(fn, args.reps))
+    for name, kind, _, nbytes in variants:
+        r = summary(ms[(name, kind)], nbytes)
+        r["spread_ms"] = round(r["ms_max"] - r["ms_min"], 4)
+        result["cases"].setdefault(name, {})[kind] = r
+    for name, r in result["cases"].items():
+        r["tone_over_managed"] = round(r["tone"]["ms_per_batch"] / r["managed"]["ms_per_batch"], 4)
+        r["tone_minus_managed_ms"] = round(r["tone"]["ms_per_batch"] - r["managed"]["ms_per_batch"], 4)
+        r["difference_inside_spread"] = bool(abs(r["tone_minus_managed_ms"]) <= max(r["tone"]["spread_ms"], r["managed"]["spread_ms"]))
+        print(f"{name}: " + ", ".join(f"{k} {r[k]['ms_per_batch']:.3f} ms ({r[k]['GBps']:.0f} GB/s, spread "
+                                      f"{r[k]['spread_ms']:.3f})" for k in ("managed", "tone")) +
+              f", tone / managed {r['tone_over_managed']:.4f}", flush=True)
+    print(json.dumps(result))
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def filter_main(args):
     n = args.images
     dev = torch.device("cuda", 0)
@@ -545,9 +646,12 @@ def main():
     ap.add_argument("--tensor", action="store_true", help="measure heifgpu_render_batch_tensor (see above)")
     ap.add_argument("--color", action="store_true", help="measure the colour-managed render (see above)")
     ap.add_argument("--filter", action="store_true", help="measure the bilinear / bicubic render (see above)")
+    ap.add_argument("--tone", action="store_true", help="measure the tone stage of the HDR render (see above)")
     args = ap.parse_args()
     if args.filter:
         return filter_main(args)
+    if args.tone:
+        return tone_main(args)
     if args.color:
         return color_main(args)
     if args.scaled:
