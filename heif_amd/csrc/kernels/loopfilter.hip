@@ -15,9 +15,16 @@
 // picture, EO neighbours outside the picture leave the sample unchanged.
 // The same pass crops the conformance window and writes the picture into
 // its grid position of the caller's output planes (coalesced along rows),
-// clipping to the grid's output size (ISO/IEC 23008-12 ImageGrid).  No
+// clipping to the grid's output size (ISO/IEC 23008-12 ImageGrid).  A thread
+// takes an aligned 16-byte group of a row at a time (sao_group: the CTB's
+// parameters read once as words, the offsets in a byte table in registers,
+// packed 16-bit arithmetic from lf_pack.hpp) and quads or single samples
+// where source, destination or pitch are not aligned (sao_out_quad).  No
 // reference code exists for either stage (src/hevc/slice.rs:249-255).
+// No kernel here uses LDS: beside the next decode's parse, residency decides
+// (luma deblocking through 4-sample words lost there twice).
 #include "kernels.hpp"
+#include "lf_pack.hpp"
 
 #include <algorithm>
 #include <string>
@@ -356,11 +363,170 @@ __device__ __forceinline__ bool sao_quad(const Pel *P, int PW, int PH, int xs0, 
     return true;
 }
 
-// SAO + crop + grid placement: one thread per four consecutive output samples
-// of a row (one 4- or 8-byte store; per sample at a row's ragged end or an
+// One quad of an output row: SAO of the (up to) four samples from picture column xs0 of row ys
+// and their store at dst (one 4- or 8-byte store; per sample at a row's ragged end or an
 // unaligned caller plane)
 template <typename Pel>
-__global__ void __launch_bounds__(256) k_sao_out(BatchArgs a) {
+__device__ __forceinline__ void sao_out_quad(const Pel *P, int PW, int PH, int xs0, int ys, int n, bool on, int cidx,
+                                             int subx, int suby, const SaoParams *sao, int wctb, int log2ctb,
+                                             const uint8_t *flg, int w4, int bd, Pel *dst) {
+    int v[4];
+    if (!(n == 4 && on && sao_quad(P, PW, PH, xs0, ys, cidx, subx, suby, sao, wctb, log2ctb, flg, w4, bd, v))) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] = 0;
+            if (j < n)
+                v[j] = on ? sao_sample(P, PW, PH, xs0 + j, ys, cidx, subx, suby, sao, wctb, log2ctb, flg, w4, bd)
+                          : (int)P[(size_t)ys * PW + xs0 + j];
+        }
+    }
+    if (n == 4 && (reinterpret_cast<uintptr_t>(dst) & (4 * sizeof(Pel) - 1)) == 0) {
+        if (sizeof(Pel) == 1)
+            *reinterpret_cast<uint32_t *>(dst) = (uint32_t)v[0] | (uint32_t)v[1] << 8 | (uint32_t)v[2] << 16 |
+                                                 (uint32_t)v[3] << 24;
+        else
+            *reinterpret_cast<uint64_t *>(dst) = (uint64_t)v[0] | (uint64_t)v[1] << 16 | (uint64_t)v[2] << 32 |
+                                                 (uint64_t)v[3] << 48;
+    } else {
+        for (int j = 0; j < n; ++j) dst[j] = (Pel)v[j];
+    }
+}
+
+// Sixteen bytes of samples: one aligned load or store
+struct alignas(16) Vec16 {
+    uint32_t w[4];
+};
+__device__ __forceinline__ Vec16 load16(const void *p) {
+    Vec16 v;
+    __builtin_memcpy(&v, __builtin_assume_aligned(p, 16), 16);
+    return v;
+}
+__device__ __forceinline__ void store16(void *p, const Vec16 &v) {
+    __builtin_memcpy(__builtin_assume_aligned(p, 16), &v, 16);
+}
+
+// pack p (samples 2p, 2p + 1) of a group
+template <typename Pel>
+__device__ __forceinline__ uint32_t pack_of(const Vec16 &v, int p) {
+    if constexpr (sizeof(Pel) == 1) return lfp::pk_from_bytes(v.w[p >> 1], p & 1);
+    else return v.w[p];
+}
+
+// SAO (8.7.3) of one aligned 16-byte group of row ys from picture column xs0 (G = 16 samples of
+// 8 bits, 8 of 16) into `out`.  The caller has checked that the group is one aligned load in
+// each of the rows ys - 1 .. ys + 1, lies inside the plane and inside one CTB column of its
+// component, and that bd <= 12.  The CTB's parameters (SaoParams is word-aligned) are
+// read once as words and the four offsets kept as a byte table in two registers
+// (lf_pack.hpp); sign of difference, lookup, add and clip run on packs of two samples.
+template <typename Pel>
+__device__ __forceinline__ void sao_group(const Pel *P, int PW, int PH, int xs0, int ys, int cidx, int subx, int suby,
+                                          const SaoParams *sao, int wctb, int log2ctb, const uint8_t *flg, int w4,
+                                          int bd, Vec16 &out) {
+    using namespace lfp;
+    constexpr int G = 16 / (int)sizeof(Pel), BITS = 8 * (int)sizeof(Pel);
+    constexpr int NP = G / 2;  // packs
+    const Pel *row = P + (size_t)ys * PW + xs0;
+    const Vec16 c = load16(row);
+    out = c;
+    const uint32_t *sw =
+        reinterpret_cast<const uint32_t *>(sao + (ys >> (log2ctb - suby)) * wctb + (xs0 >> (log2ctb - subx)));
+    const uint64_t head = (uint64_t)sw[0] | (uint64_t)sw[1] << 32;  // type[3], band_eo[3], off[0][0]
+    const int type = (int)(int8_t)(head >> (8 * cidx));
+    if (!type) return;
+    const int cl = (int)(head >> (24 + 8 * cidx)) & 0xff;
+    uint32_t tlo, thi;
+    sao_tables(sw[1 + 2 * cidx], sw[2 + 2 * cidx], sw[3 + 2 * cidx], type == 2, tlo, thi);
+    const uint32_t maxv2 = (uint32_t)((1 << bd) - 1) * 0x00010001u;
+    // word i of the result from the table indices of its packs
+    auto emit = [&](auto idx_of) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if constexpr (sizeof(Pel) == 1) {
+                const uint32_t r0 = pk_add_clip(pack_of<Pel>(c, 2 * i), sao_lookup(tlo, thi, idx_of(2 * i)), maxv2);
+                const uint32_t r1 = pk_add_clip(pack_of<Pel>(c, 2 * i + 1), sao_lookup(tlo, thi, idx_of(2 * i + 1)), maxv2);
+                out.w[i] = pk_to_bytes(r0, r1);
+            } else {
+                out.w[i] = pk_add_clip(c.w[i], sao_lookup(tlo, thi, idx_of(i)), maxv2);
+            }
+        }
+    };
+    if (type == 2) {
+        // neighbours a at (x - hx, y - vy), b at (x + hx, y + vy): classes 0 .. 3 have
+        // (hx, vy) = (1, 0), (0, 1), (1, 1), (-1, 1).  The edge index is symmetric in a and b, so
+        // a class is the row `rl` whose sample to the left is taken and the row `rr` whose sample
+        // to the right is: class 3 swaps the rows of class 2.
+        const int vy = cl == 0 ? 0 : 1;
+        if (ys - vy < 0 || ys + vy >= PH) return;  // a neighbour row outside the picture: unchanged
+        const ptrdiff_t up = (ptrdiff_t)(cl >= 3 ? -vy : vy) * PW;
+        const Pel *rl = row - up, *rr = row + up;
+        Vec16 na = load16(rl), nb = load16(rr);
+        // the picture's first and last column have a neighbour outside it: index 2, offset 0
+        uint32_t first = 0xffffffffu, last = 0xffffffffu;
+        if (cl != 1) {
+            // the one sample of each row outside the group (clamped into the row)
+            const uint32_t el = rl[xs0 > 0 ? -1 : 0], er = rr[xs0 + G < PW ? G : G - 1];
+            const Vec16 qa = na, qb = nb;
+            na.w[0] = (qa.w[0] << BITS) | el;
+            nb.w[3] = (qb.w[3] >> BITS) | (er << (32 - BITS));
+#pragma unroll
+            for (int i = 1; i < 4; ++i) {
+                na.w[i] = (qa.w[i] << BITS) | (qa.w[i - 1] >> (32 - BITS));
+                nb.w[i - 1] = (qb.w[i - 1] >> BITS) | (qb.w[i] << (32 - BITS));
+            }
+            if (xs0 == 0) first = 0xffff0000u;
+            if (xs0 + G == PW) last = 0x0000ffffu;
+        }
+        emit([&](int p) {
+            const uint32_t cp = pack_of<Pel>(c, p);
+            const uint32_t s = pk_add(pk_sign_diff(cp, pack_of<Pel>(na, p)), pk_sign_diff(cp, pack_of<Pel>(nb, p)));
+            // (a masked lane: sign sum 0)
+            return pk_add(p == 0 ? s & first : (p == NP - 1 ? s & last : s), 0x00020002u);
+        });
+    } else {
+        const uint32_t pos2 = (uint32_t)cl * 0x00010001u;
+        emit([&](int p) {
+            return pk_min_i16(pk_sub(pk_lshr(pack_of<Pel>(c, p), bd - 5), pos2) & 0x001f001fu, 0x00040004u);
+        });
+    }
+    // MF_NOFILT of each sample's 4x4 luma block, from the group's nf flag bytes read as one
+    // word: the samples of a flagged block are put back (both samples of a pack lie in one block)
+    const uint8_t *fr = flg + (size_t)((ys << suby) >> 2) * w4 + ((xs0 << subx) >> 2);
+    const int nf = (G << subx) >> 2;
+    uint64_t fw = 0;
+    if (nf == 8) __builtin_memcpy(&fw, fr, 8);
+    else if (nf == 4) __builtin_memcpy(&fw, fr, 4);
+    else __builtin_memcpy(&fw, fr, 2);
+    fw &= (uint64_t)MF_NOFILT * 0x0101010101010101ull;
+    if (fw) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            if ((fw >> (8 * (((2 * p) << subx) >> 2))) & 0xff) {
+                const int i = sizeof(Pel) == 1 ? p >> 1 : p;
+                const uint32_t m = sizeof(Pel) == 1 ? (p & 1 ? 0xffff0000u : 0x0000ffffu) : 0xffffffffu;
+                out.w[i] = (out.w[i] & ~m) | (c.w[i] & m);
+            }
+        }
+    }
+}
+
+// SAO + crop + grid placement.  Each component's visible rows are cut into groups of 16 bytes
+// (16 samples of 8 bits, 8 of 16); a thread takes one group per iteration, consecutive threads
+// consecutive groups of a row, and steps through (row, group) by the launch's stride, so the
+// divisions are paid once per component and loop.  A group is one 16-byte load per row and one
+// 16-byte store (sao_group) when
+//   - its source is 16-byte aligned in picture coordinates (the conformance offset a multiple
+//     of the group) and in memory, and the plane's row pitch keeps that,
+//   - its destination and the caller's pitch are 16-byte aligned,
+//   - it lies inside the visible width (not the ragged group at a row's end),
+//   - it lies inside one CTB column of its component (not the 8-sample chroma CTBs of
+//     log2_ctb = 4 in 4:2:0 / 4:2:2 at 8 bits: those take the quads),
+// and otherwise the quads and single samples of sao_out_quad.  All but the third condition hold
+// or fail for a whole component of a picture.
+// (The second launch bound keeps 8 waves per SIMD: without it the kernel takes about 106 SGPRs,
+// which bound the occupancy at 7; with it some 36 SGPRs are spilled to lanes of a VGPR, no
+// scratch.  Dropping it costs occupancy, not correctness.)
+template <typename Pel>
+__global__ void __launch_bounds__(256, 8) k_sao_out(BatchArgs a) {
     const int pic = a.pic0 + blockIdx.y;
     const PicDesc pd = a.pics[pic];
     if (pd.flags & PD_CHILD) return;  // output through its assembly
@@ -377,56 +543,60 @@ __global__ void __launch_bounds__(256) k_sao_out(BatchArgs a) {
     // visible region of this picture in the output image (luma)
     const int vw = min(sp.out_w, oi.width - pd.out_x), vh = min(sp.out_h, oi.height - pd.out_y);
     if (vw <= 0 || vh <= 0) return;
-    const int vcw = sp.chroma_format ? (vw + (1 << sx) - 1) >> sx : 0;
-    const int vch = sp.chroma_format ? (vh + (1 << sy) - 1) >> sy : 0;
-    const int qw = (vw + 3) >> 2, qcw = (vcw + 3) >> 2;  // quads per row
-    const int nl = qw * vh, nc = qcw * vch;
-    const int total = nl + 2 * nc;
-    const FastDiv dq(qw), dn(nc), dqc(qcw);
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-        int cidx, q, y;
-        if (t < nl) {
-            cidx = 0;
-            y = dq.div(t, q);
-        } else {
-            const int u = t - nl;
-            int v;
-            cidx = 1 + dn.div(u, v);
-            y = dqc.div(v, q);
-        }
+    const bool on = pd.sao_luma || pd.sao_chroma;  // SaoTypeIdx is 0 for a component whose flag is off
+    constexpr int G = 16 / (int)sizeof(Pel), LOG2G = sizeof(Pel) == 1 ? 4 : 3;
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
+    for (int cidx = 0; cidx < (sp.chroma_format ? 3 : 1); ++cidx) {
         const int subx = cidx ? sx : 0, suby = cidx ? sy : 0;
         const int PW = cidx ? cw : W, PH = cidx ? ch : H;
-        const int vwc = cidx ? vcw : vw;
+        const int vwc = cidx ? (vw + (1 << sx) - 1) >> sx : vw, vhc = cidx ? (vh + (1 << sy) - 1) >> sy : vh;
         const Pel *P = cidx == 0 ? Y : Y + (size_t)W * H + (size_t)(cidx - 1) * cw * ch;
-        const int x0 = q * 4, n = min(4, vwc - x0);
-        const int ys = y + (sp.conf_t >> suby), xs0 = x0 + (sp.conf_l >> subx);  // picture coords
-        const bool on = pd.sao_luma || pd.sao_chroma;  // SaoTypeIdx is 0 for a component whose flag is off
         const int bd = cidx ? sp.bit_depth_c : sp.bit_depth_y;
-        int v[4];
-        if (!(n == 4 && on && sao_quad(P, PW, PH, xs0, ys, cidx, subx, suby, sao, wctb, log2ctb, flg, w4, bd, v))) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v[j] = 0;
-                if (j < n)
-                    v[j] = on ? sao_sample(P, PW, PH, xs0 + j, ys, cidx, subx, suby, sao, wctb, log2ctb, flg, w4, bd)
-                              : (int)P[(size_t)ys * PW + xs0 + j];
-            }
-        }
-        // component fields by select: a lane-varying index into the OutImage copy made
+        const int cx0 = sp.conf_l >> subx, cy0 = sp.conf_t >> suby;  // picture coords of the first visible sample
+        // component fields by select: an index into the OutImage copy that is not a constant made
         // the compiler keep it in LDS (12 KB per workgroup, 519 M bank-conflict cycles per launch)
         const uint64_t plane = cidx == 0 ? oi.plane[0] : (cidx == 1 ? oi.plane[1] : oi.plane[2]);
         const int pitch = cidx == 0 ? oi.pitch[0] : (cidx == 1 ? oi.pitch[1] : oi.pitch[2]);
-        const int ox = (pd.out_x >> subx) + x0, oy = (pd.out_y >> suby) + y;
-        Pel *dst = reinterpret_cast<Pel *>(plane + (size_t)oy * pitch) + ox;
-        if (n == 4 && (reinterpret_cast<uintptr_t>(dst) & (4 * sizeof(Pel) - 1)) == 0) {
-            if (sizeof(Pel) == 1)
-                *reinterpret_cast<uint32_t *>(dst) = (uint32_t)v[0] | (uint32_t)v[1] << 8 | (uint32_t)v[2] << 16 |
-                                                     (uint32_t)v[3] << 24;
-            else
-                *reinterpret_cast<uint64_t *>(dst) = (uint64_t)v[0] | (uint64_t)v[1] << 16 | (uint64_t)v[2] << 32 |
-                                                     (uint64_t)v[3] << 48;
-        } else {
-            for (int j = 0; j < n; ++j) dst[j] = (Pel)v[j];
+        uint8_t *d0 = reinterpret_cast<uint8_t *>(plane) + (size_t)(pd.out_y >> suby) * pitch +
+                      (size_t)(pd.out_x >> subx) * sizeof(Pel);
+        const bool wide = (((PW * (int)sizeof(Pel)) | pitch) & 15) == 0 && (cx0 & (G - 1)) == 0 &&
+                          ((reinterpret_cast<uintptr_t>(P + cx0) | reinterpret_cast<uintptr_t>(d0)) & 15) == 0 &&
+                          log2ctb - subx >= LOG2G && bd <= 12;
+        // the whole groups of every row, then what is left of the rows in quads (all of them
+        // where the component is not eligible): two loops, so neither holds the other's registers
+        const int gw = wide ? vwc >> LOG2G : 0;  // groups per row
+        if (gw > 0) {
+            const FastDiv dg(gw);
+            int g, y = dg.div(tid, g), dgr;
+            const int dy = dg.div(nth, dgr);
+            for (; y < vhc; y += dy) {
+                const int x0 = g << LOG2G, ys = y + cy0, xs0 = x0 + cx0;
+                Vec16 v;
+                if (on) sao_group<Pel>(P, PW, PH, xs0, ys, cidx, subx, suby, sao, wctb, log2ctb, flg, w4, bd, v);
+                else v = load16(P + (size_t)ys * PW + xs0);
+                store16(d0 + (size_t)y * pitch + (size_t)x0 * sizeof(Pel), v);
+                g += dgr;
+                if (g >= gw) {
+                    g -= gw;
+                    ++y;
+                }
+            }
+        }
+        const int xq = gw << LOG2G, qw = (vwc - xq + 3) >> 2;  // first column and quads per row of the rest
+        if (qw > 0) {
+            const FastDiv dq(qw);
+            int q, y = dq.div(tid, q), dqr;
+            const int dy = dq.div(nth, dqr);
+            for (; y < vhc; y += dy) {
+                const int x0 = xq + 4 * q;
+                sao_out_quad<Pel>(P, PW, PH, x0 + cx0, y + cy0, min(4, vwc - x0), on, cidx, subx, suby, sao, wctb, log2ctb,
+                                  flg, w4, bd, reinterpret_cast<Pel *>(d0 + (size_t)y * pitch) + x0);
+                q += dqr;
+                if (q >= qw) {
+                    q -= qw;
+                    ++y;
+                }
+            }
         }
     }
 }
