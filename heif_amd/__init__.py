@@ -25,7 +25,7 @@ from ._lib import HeifGpuError, UnsupportedError, lib
 __all__ = [
     "HeicDecoder", "HeifImage", "DecodeContext", "DeviceBatch", "DecodedImage", "RbspReader",
     "HeifGpuError", "UnsupportedError", "ipc_export", "ipc_open", "ipc_close", "chroma_dims", "ColorDescription",
-    "HdrDescription",
+    "HdrDescription", "ChromaDescription",
 ]
 
 
@@ -59,17 +59,23 @@ class HeifImage:
         self._h = ctypes.c_void_p(handle)
 
     @classmethod
-    def parse(cls, data: bytes, item_id: int = 0) -> "HeifImage":
+    def parse(cls, data: bytes, item_id: int = 0, chroma: Optional[str] = None) -> "HeifImage":
         """The primary image (item_id 0), or any coded image item, e.g. the
-        auxiliary HDR gain map at `HeifImage.parse(d).info.aux_item_id`."""
+        auxiliary HDR gain map at `HeifImage.parse(d).info.aux_item_id`.
+        chroma "bilinear" sets chroma_upsampling on the image returned."""
         h = ctypes.c_void_p()
         _lib.check(lib.heifgpu_image_parse_item(_lib.u8buf(data), len(data), item_id, ctypes.byref(h)))
-        return cls(h.value)
+        img = cls(h.value)
+        if chroma is not None:
+            img.chroma_upsampling = chroma
+        return img
 
     @classmethod
-    def parse_many(cls, files: Sequence[bytes], threads: int = 0) -> List["HeifImage"]:
+    def parse_many(cls, files: Sequence[bytes], threads: int = 0, chroma: Optional[str] = None) -> List["HeifImage"]:
         """Primary images of many files, parsed on `threads` native host threads
-        (heifgpu_image_parse_many; 0 = every hardware thread)."""
+        (heifgpu_image_parse_many; 0 = every hardware thread).  chroma as in parse()."""
+        if chroma is not None and chroma not in _lib.CHROMA_MODES:
+            raise ValueError(f"chroma {chroma!r}: one of {sorted(_lib.CHROMA_MODES)}")
         n = len(files)
         files = [bytes(f) for f in files]  # no copy for bytes; the library copies what it keeps
         # pointers straight into the bytes objects (no Python-side copy of the files)
@@ -80,6 +86,9 @@ class HeifImage:
         rc = lib.heifgpu_image_parse_many(data, lens, n, threads, hs, None)
         imgs = [cls(h) if h else None for h in hs[:n]]
         _lib.check(rc)
+        if chroma is not None:
+            for im in imgs:
+                im.chroma_upsampling = chroma
         return imgs
 
     @property
@@ -135,6 +144,48 @@ class HeifImage:
         return HdrDescription(hi.transfer, hi.max_cll if clli else None, hi.max_fall if clli else None,
                               hi.mastering_max * 1e-4 if mdcv else None, hi.mastering_min * 1e-4 if mdcv else None,
                               hi.status)
+
+    def _chroma_info(self) -> _lib.ChromaInfo:
+        ci = _lib.ChromaInfo()
+        _lib.check(lib.heifgpu_image_get_chroma(self._h, ctypes.byref(ci)))
+        return ci
+
+    @property
+    def chroma(self) -> "ChromaDescription":
+        """Where the stream puts its chroma samples (heifgpu_image_get_chroma): loc,
+        the SPS's chroma_sample_loc_type_top_field (0 when not signalled),
+        signalled, and subsampling = (SubWidthC, SubHeightC)."""
+        ci = self._chroma_info()
+        return ChromaDescription(ci.loc, bool(ci.signalled), (ci.sub_width_c, ci.sub_height_c))
+
+    @property
+    def chroma_upsampling(self) -> str:
+        """How every render of this image turns 4:2:0 / 4:2:2 chroma into the luma
+        grid: "replicate" (the default: a luma sample reads the chroma sample of its
+        cell) or "bilinear" (interpolated at the sample location in force,
+        include/heifgpu.h "chroma upsampling").  4:4:4 and 4:0:0 images accept the
+        setting, which changes nothing for them.  source_rect() follows it.  Not to
+        be set while another thread submits a render of this image."""
+        return "bilinear" if self._chroma_info().mode == _lib.CHROMA_BILINEAR else "replicate"
+
+    @chroma_upsampling.setter
+    def chroma_upsampling(self, mode: str) -> None:
+        if mode not in _lib.CHROMA_MODES:
+            raise ValueError(f"chroma_upsampling {mode!r}: one of {sorted(_lib.CHROMA_MODES)}")
+        _lib.check(lib.heifgpu_image_set_chroma_upsampling(self._h, _lib.CHROMA_MODES[mode], self._chroma_info().loc_override))
+
+    @property
+    def chroma_loc(self) -> int:
+        """The chroma sample location in force for "bilinear" (0..5): the caller's
+        override, else the file's.  Set None to return to the file's."""
+        ci = self._chroma_info()
+        return ci.loc_override if ci.loc_override >= 0 else ci.loc
+
+    @chroma_loc.setter
+    def chroma_loc(self, loc: Optional[int]) -> None:
+        if loc is not None and (isinstance(loc, bool) or int(loc) != loc or not 0 <= int(loc) <= 5):
+            raise ValueError(f"chroma_loc {loc!r}: None or 0..5")
+        _lib.check(lib.heifgpu_image_set_chroma_upsampling(self._h, self._chroma_info().mode, -1 if loc is None else int(loc)))
 
     # a caller's source peak in cd/m2 for the tone transforms of this image (None: the file's);
     # color_transform(peak_nits=) overrides it for one call
@@ -235,6 +286,13 @@ class ColorDescription:
     icc_size: int = 0
     has_nclx: bool = False
     status: int = 0             # HEIFGPU_OK, or the code a transform of this source answers
+
+
+@dataclass
+class ChromaDescription:
+    loc: int               # chroma_sample_loc_type_top_field of the SPS, 0..5 (0 when not signalled)
+    signalled: bool        # the SPS's VUI carries chroma_loc_info
+    subsampling: tuple     # (SubWidthC, SubHeightC)
 
 
 @dataclass
@@ -873,7 +931,7 @@ class HeicDecoder:
 
     @classmethod
     def _decode_pair(cls, data: bytes, device: int, size, mode: str, tiles: str, with_alpha: bool,
-                     filter: str = "area"):
+                     filter: str = "area", chroma: str = "replicate", chroma_loc: Optional[int] = None):
         """The primary image and (with_alpha, when the file has one) its alpha
         image, decoded whole (tiles="all") or for the window that (size, mode)
         reads through `filter` (tiles="window")."""
@@ -881,7 +939,8 @@ class HeicDecoder:
             raise ValueError(f"tiles {tiles!r}: 'all' or 'window'")
         _filter_code(filter)
         ctx = cls.context(device)
-        img = HeifImage.parse(data)
+        img = HeifImage.parse(data, chroma=chroma)
+        img.chroma_loc = chroma_loc
         rect = None
         if tiles == "window":
             rsize = None
@@ -900,7 +959,8 @@ class HeicDecoder:
     @classmethod
     def decode_display(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, size=None,
                        mode: str = "contain", tiles: str = "all", colorspace: Optional[str] = None,
-                       filter: str = "area", tone_map: Optional[str] = None, peak_nits: Optional[float] = None):
+                       filter: str = "area", tone_map: Optional[str] = None, peak_nits: Optional[float] = None,
+                       chroma: str = "replicate", chroma_loc: Optional[int] = None):
         """The picture a viewer shows: decodes the primary image and, when it
         has one (display.alpha_item_id), its alpha plane, then renders
         (DecodeContext.render) with clap / irot / imir applied.  fmt None picks
@@ -916,10 +976,13 @@ class HeicDecoder:
         filters, which also interpolate an enlargement as a viewer expects).
         tone_map "bt2390", with a colorspace, shows a PQ / HLG picture tone-mapped
         to SDR (DecodeContext.render); peak_nits replaces the source peak the file
-        states (clli, mdcv)."""
+        states (clli, mdcv).  chroma "bilinear" interpolates 4:2:0 / 4:2:2 chroma at
+        the sample location the stream signals (chroma_loc 0..5 replaces it) instead
+        of replicating it (HeifImage.chroma_upsampling); with tiles="window" the
+        decoded rectangle then includes the samples the taps read."""
         DecodeContext._check_tone(colorspace, tone_map)
         ctx = cls.context(device)
-        out, alpha = cls._decode_pair(data, device, size, mode, tiles, True, filter)
+        out, alpha = cls._decode_pair(data, device, size, mode, tiles, True, filter, chroma, chroma_loc)
         out.image.peak_nits = peak_nits
         if fmt is None:
             fmt = ("rgba" if alpha is not None else "rgb") + ("16" if out.info.bit_depth > 8 else "8")
@@ -931,17 +994,18 @@ class HeicDecoder:
 
     @classmethod
     def decode_tensor(cls, data: bytes, size, mode: str = "cover", device: int = 0, flip: int = 0,
-                      tiles: str = "all", peak_nits: Optional[float] = None, **kw):
+                      tiles: str = "all", peak_nits: Optional[float] = None, chroma: str = "replicate",
+                      chroma_loc: Optional[int] = None, **kw):
         """decode_display(size=) as a normalised float tensor: decodes the
         primary image (and its alpha plane when `src` is an RGBA format and the
         file has one), then DecodeContext.render_tensor of that one picture:
         (C, h, w), or (h, w, C) for layout="hwc".  dtype, layout, mean, std, src
         scale_bias, colorspace, tone_map and filter go through to render_tensor; tiles and
-        peak_nits as in decode_display."""
+        peak_nits, chroma and chroma_loc as in decode_display."""
         DecodeContext._check_tone(kw.get("colorspace"), kw.get("tone_map"))
         ctx = cls.context(device)
         rgba = kw.get("src", "rgb8").startswith("rgba")
-        out, alpha = cls._decode_pair(data, device, size, mode, tiles, rgba, kw.get("filter", "area"))
+        out, alpha = cls._decode_pair(data, device, size, mode, tiles, rgba, kw.get("filter", "area"), chroma, chroma_loc)
         alphas = [alpha] if alpha is not None else None
         out.image.peak_nits = peak_nits
         return ctx.render_tensor([out], size, mode, flips=[flip], alphas=alphas, **kw)[0]

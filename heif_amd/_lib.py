@@ -224,6 +224,14 @@ FIT_MODES = {"stretch": FIT_STRETCH, "contain": FIT_CONTAIN, "cover": FIT_COVER}
 PIX_RGB8, PIX_RGBA8, PIX_RGB16, PIX_RGBA16 = 0, 1, 2, 3
 PIX_FORMATS = {"rgb8": PIX_RGB8, "rgba8": PIX_RGBA8, "rgb16": PIX_RGB16, "rgba16": PIX_RGBA16}
 
+class ChromaInfo(ctypes.Structure):  # heifgpu_chroma_info
+    _fields_ = [("loc", ctypes.c_uint32), ("signalled", ctypes.c_uint32), ("loc_override", ctypes.c_int32),
+                ("mode", ctypes.c_uint32), ("sub_width_c", ctypes.c_uint32), ("sub_height_c", ctypes.c_uint32)]
+
+
+CHROMA_REPLICATE, CHROMA_BILINEAR = 0, 1
+CHROMA_MODES = {"replicate": CHROMA_REPLICATE, "bilinear": CHROMA_BILINEAR}
+
 PARSE_AUTO, PARSE_LANES, PARSE_SOLO, PARSE_SPREAD = 0, 1, 2, 3
 PARSE_ROWS = 4  # ABI 5 only; removed in ABI 6 (prepare answers HEIFGPU_E_UNSUPPORTED)
 PARSE_MODES = {"auto": PARSE_AUTO, "lanes": PARSE_LANES, "solo": PARSE_SOLO, "spread": PARSE_SPREAD}
@@ -249,6 +257,7 @@ EXPORTS = (
     "heifgpu_render_batch_resampled", "heifgpu_render_batch_tensor_resampled", "heifgpu_resample_coeffs",
     "heifgpu_resample_apply", "heifgpu_window_source_rect_resampled",
     "heifgpu_image_get_hdr", "heifgpu_color_transform_make_hdr",
+    "heifgpu_image_get_chroma", "heifgpu_image_set_chroma_upsampling", "heifgpu_chroma_upsample",
 )
 
 
@@ -350,6 +359,10 @@ def _load() -> ctypes.CDLL:
         "heifgpu_window_source_rect_resampled": (I32, [VP, P(Scale), U32, P(Rect)]),
         "heifgpu_image_get_hdr": (I32, [VP, P(HdrInfo)]),
         "heifgpu_color_transform_make_hdr": (I32, [VP, U32, U32, U32, ctypes.c_double, P(HdrTransform)]),
+        "heifgpu_image_get_chroma": (I32, [VP, P(ChromaInfo)]),
+        "heifgpu_image_set_chroma_upsampling": (I32, [VP, U32, ctypes.c_int32]),
+        "heifgpu_chroma_upsample": (I32, [VP, U32, U32, ctypes.c_int32, U32, U32, U32, U32, U32, U32, U32, VP,
+                                          ctypes.c_int32]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     # (and no window decode: DecodeContext.prepare without windows then goes through prepare_ex)
@@ -362,7 +375,9 @@ def _load() -> ctypes.CDLL:
                 "heifgpu_render_batch_resampled", "heifgpu_render_batch_tensor_resampled", "heifgpu_resample_coeffs",
                 "heifgpu_resample_apply", "heifgpu_window_source_rect_resampled",
                 # the HDR render (tone_map= then needs a build that has it)
-                "heifgpu_image_get_hdr", "heifgpu_color_transform_make_hdr"}
+                "heifgpu_image_get_hdr", "heifgpu_color_transform_make_hdr",
+                # bilinear chroma upsampling (chroma= other than "replicate" then needs a build that has it)
+                "heifgpu_image_get_chroma", "heifgpu_image_set_chroma_upsampling", "heifgpu_chroma_upsample"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue

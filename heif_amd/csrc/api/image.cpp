@@ -239,6 +239,38 @@ int heifgpu_color_apply(const heifgpu_color_transform *t, const uint16_t *rgb_in
     return HEIFGPU_OK;
 }
 
+// ---- chroma upsampling (include/heifgpu.h): the signalled location, the setting, the rule ----
+int heifgpu_image_get_chroma(const heifgpu_image *img, heifgpu_chroma_info *out) {
+    if (!img || !out) return fail(HEIFGPU_E_INVALID, "null argument");
+    const ParsedImage &p = img->img;
+    const SequenceParameterSet &s = p.params[0].sps;
+    std::memset(out, 0, sizeof(*out));
+    out->loc = uint32_t(s.chroma_loc_top);
+    out->signalled = s.chroma_loc_present ? 1 : 0;
+    out->loc_override = p.chroma_loc_override;
+    out->mode = p.chroma_mode;
+    out->sub_width_c = 1u << chroma_sx(s.chroma_array_type());
+    out->sub_height_c = 1u << chroma_sy(s.chroma_array_type());
+    return HEIFGPU_OK;
+}
+
+int heifgpu_image_set_chroma_upsampling(heifgpu_image *img, uint32_t mode, int32_t loc) {
+    if (!img) return fail(HEIFGPU_E_INVALID, "null argument");
+    if (mode > HEIFGPU_CHROMA_BILINEAR) return fail(HEIFGPU_E_INVALID, "chroma upsampling mode");
+    if (loc < -1 || loc > 5) return fail(HEIFGPU_E_INVALID, "chroma sample location outside -1..5");
+    img->img.chroma_mode = mode;
+    img->img.chroma_loc_override = loc;
+    return HEIFGPU_OK;
+}
+
+int heifgpu_chroma_upsample(const void *in, uint32_t w_c, uint32_t h_c, int32_t pitch, uint32_t bits,
+                            uint32_t chroma_format_idc, uint32_t loc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                            void *out, int32_t out_pitch) {
+    if (const char *err = chroma_upsample_rect(in, w_c, h_c, pitch, bits, chroma_format_idc, loc, x0, y0, w, h, out, out_pitch))
+        return fail(HEIFGPU_E_INVALID, err);
+    return HEIFGPU_OK;
+}
+
 void heifgpu_image_free(heifgpu_image *img) { delete img; }
 
 // ---- window decode: geometry (host only) ----

@@ -23,7 +23,7 @@ constexpr int kRenderSlots = 4;
 struct RenderRing {
     struct Slot {
         PinnedBuf host;
-        DevBuf<uint8_t> dev;  // n descriptors of the call's type, then its ColorRefs
+        DevBuf<uint8_t> dev;  // n descriptors of the call's type, then its ColorRefs, then its ChromaRefs
         hipEvent_t done = nullptr;
         bool pending = false;
     } slot[kRenderSlots];
@@ -238,7 +238,10 @@ static int render_ring_slot(heifgpu_ctx *ctx, RenderRing::Slot **out) {
 
 // What every render call ends in, for Desc = RenderDesc, ScaleDesc or TensorDesc: the
 // colour refs, a ring slot, the descriptors then the refs in one staging image, one
-// copy, the one launch and the slot's event.
+// copy, the one launch and the slot's event.  When an image of the call is set to
+// bilinear chroma upsampling (image_chroma_up: the setting window_source_rect reads too)
+// the call goes to the kernels that know it: a ChromaRef per image follows the ColorRefs,
+// which are then always there (lut == 0 for an image without a transform).
 template <class Desc>
 static int render_submit(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, const std::vector<Desc> &descs,
                          int max_tiles, uint32_t format, int bps, const heifgpu_color_transform *const *xf,
@@ -248,18 +251,30 @@ static int render_submit(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, con
     std::vector<ColorRef> refs;
     bool tone = false;
     if (int rc = color_refs_fill(ctx, imgs, n, format, xf, refs, tone)) return rc;
+    static_assert(sizeof(ChromaUp) == sizeof(ChromaRef) && sizeof(ColorRef) % 8 == 0, "ChromaUp is ChromaRef's image");
+    std::vector<ChromaUp> ups;
+    bool any_up = false;
+    for (size_t i = 0; i < n; ++i) any_up = any_up || image_chroma_up(imgs[i]->img).mode != 0;
+    if (any_up) {
+        if (refs.empty()) refs.assign(n, ColorRef{});
+        ups.resize(n);
+        for (size_t i = 0; i < n; ++i) ups[i] = image_chroma_up(imgs[i]->img);
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     RenderRing::Slot *slot = nullptr;
     if (int rc = render_ring_slot(ctx, &slot)) return rc;
     RenderRing::Slot &sl = *slot;
-    const size_t dbytes = n * sizeof(Desc), bytes = dbytes + refs.size() * sizeof(ColorRef);
+    const size_t dbytes = n * sizeof(Desc), rbytes = refs.size() * sizeof(ColorRef);
+    const size_t bytes = dbytes + rbytes + ups.size() * sizeof(ChromaUp);
     HIP_TRY(sl.host.reserve(bytes));
     HIP_TRY(sl.dev.alloc(bytes));
     std::memcpy(sl.host.p, descs.data(), dbytes);
-    if (!refs.empty()) std::memcpy(sl.host.p + dbytes, refs.data(), bytes - dbytes);  // behind the descriptors: one copy
+    if (!refs.empty()) std::memcpy(sl.host.p + dbytes, refs.data(), rbytes);  // behind the descriptors: one copy
+    if (!ups.empty()) std::memcpy(sl.host.p + dbytes + rbytes, ups.data(), ups.size() * sizeof(ChromaUp));
     HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(launch_render(reinterpret_cast<const Desc *>(sl.dev.p), int(n), max_tiles, int(format), bps,
-                          refs.empty() ? RENDER_PLAIN : tone ? RENDER_TONE : RENDER_MANAGED, s));  // the one launch
+                          any_up ? RENDER_CHROMA : refs.empty() ? RENDER_PLAIN : tone ? RENDER_TONE : RENDER_MANAGED,
+                          s));  // the one launch
     HIP_TRY(hipEventRecord(sl.done, s));
     sl.pending = true;
     return HEIFGPU_OK;

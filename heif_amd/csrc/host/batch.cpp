@@ -88,6 +88,13 @@ bool rect_inside(const Rect &r, uint32_t W, uint32_t H) {
     return r.w && r.h && r.x < W && r.y < H && r.w <= W - r.x && r.h <= H - r.y;
 }
 
+ChromaUp image_chroma_up(const ParsedImage &im) {
+    if (im.params.empty()) return ChromaUp{};
+    const SequenceParameterSet &s = im.params[0].sps;
+    const int loc = im.chroma_loc_override >= 0 ? im.chroma_loc_override : s.chroma_loc_top;
+    return chroma_up_for(im.chroma_mode, loc, s.chroma_array_type(), im.out_width, im.out_height);
+}
+
 bool window_source_rect(const ParsedImage &im, const Rect &window, Rect &src) {
     const DisplayMap &d = im.display;
     Rect w = window;
@@ -107,10 +114,22 @@ bool window_source_rect(const ParsedImage &im, const Rect &window, Rect &src) {
     if (x0 < 0 || y0 < 0 || x1 >= W || y1 >= H) return false;  // (parse_heic keeps the map inside)
     const int cf = im.params.empty() ? 0 : im.params[0].sps.chroma_array_type();
     const int64_t mx = cf ? (int64_t(1) << chroma_sx(cf)) - 1 : 0, my = cf ? (int64_t(1) << chroma_sy(cf)) - 1 : 0;
+    const int64_t lx0 = x0, lx1 = x1, ly0 = y0, ly1 = y1;  // the luma box
     x0 &= ~mx;
     y0 &= ~my;
     x1 = std::min(x1 | mx, W - 1);
     y1 = std::min(y1 | my, H - 1);
+    // a bilinear image: the cells of every chroma sample the luma box taps as well
+    const ChromaUp cu = image_chroma_up(im);
+    if (cu.mode) {
+        int c0, c1;
+        chroma_tap_span(int(lx0), int(lx1), cu.px, cu.wc, c0, c1);
+        x0 = std::min(x0, int64_t(c0) << chroma_sx(cf));
+        x1 = std::max(x1, std::min((int64_t(c1) << chroma_sx(cf)) | mx, W - 1));
+        chroma_tap_span(int(ly0), int(ly1), cu.py, cu.hc, c0, c1);
+        y0 = std::min(y0, int64_t(c0) << chroma_sy(cf));
+        y1 = std::max(y1, std::min((int64_t(c1) << chroma_sy(cf)) | my, H - 1));
+    }
     src = Rect{uint32_t(x0), uint32_t(y0), uint32_t(x1 - x0 + 1), uint32_t(y1 - y0 + 1)};
     return true;
 }

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../common/desc.hpp"
+#include "chroma.hpp"
 #include "heic_image.hpp"
 
 namespace hg {
@@ -44,10 +45,17 @@ struct Rect {
 bool rect_inside(const Rect &r, uint32_t W, uint32_t H);
 // The decoded samples of `im` that a render of `window` (displayed coordinates;
 // "everything": the whole displayed picture) reads: the bounding box of the display
-// map over the window's opposite corners, grown to the chroma sample grid (the
-// render replicates chroma, so a luma sample reads its chroma sample's whole cell)
-// and clipped to the image.  False if the window is not inside the displayed picture.
+// map over the window's opposite corners, grown to the chroma sample grid and clipped
+// to the image.  An image set to replicate chroma (the default) reads, for a luma
+// sample, its own chroma sample: the box grows to whole chroma cells.  An image set to
+// bilinear upsampling reads the two chroma columns floor((2x - px) / 4) and the next
+// (clamped to the plane) and the two such rows: the box also covers the cells of the
+// taps of its first and last luma column and row.  False if the window is not inside
+// the displayed picture.
 bool window_source_rect(const ParsedImage &im, const Rect &window, Rect &src);
+// the chroma upsampling in force for an image: its setting, the caller's sample location
+// or else its first SPS's (what the render calls and window_source_rect both read)
+ChromaUp image_chroma_up(const ParsedImage &im);
 // The grid tiles whose visible part meets src (rect_inside the image): columns
 // [col0, col0 + cols), rows [row0, row0 + rows).
 void tiles_for_rect(const ParsedImage &im, const Rect &src, uint32_t &col0, uint32_t &row0, uint32_t &cols,

@@ -330,6 +330,8 @@ ParsedImage parse_heic(const uint8_t *data, size_t len, uint32_t item_id) {
             throw UnsupportedError("grid tiles of different sizes");
         if (ps.sps.bit_depth_luma_minus8 != s0.bit_depth_luma_minus8 || ps.sps.chroma_format_idc != s0.chroma_format_idc)
             throw UnsupportedError("grid tiles with different formats");
+        if (ps.sps.chroma_loc_present != s0.chroma_loc_present || ps.sps.chroma_loc_top != s0.chroma_loc_top)
+            throw UnsupportedError("grid tiles with different formats");
     }
     if (pi->type != fourcc('g', 'r', 'i', 'd')) {
         img.out_width = img.tile_width;

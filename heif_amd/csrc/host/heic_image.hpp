@@ -77,6 +77,11 @@ struct ParsedImage {
     // first 'auxl' image of the decoded item whose auxC names an alpha plane (0: none);
     // a 'prem' reference from the item to it is reported, nothing is un-premultiplied
     uint32_t alpha_item_id = 0, alpha_premultiplied = 0;
+    // how the renders turn subsampled chroma into the luma grid (host/chroma.hpp): replicate
+    // (0) or bilinear (1), and the caller's sample location in place of the SPS's (-1: the file's).
+    // Set by heifgpu_image_set_chroma_upsampling; read by the render calls and by window_source_rect.
+    uint32_t chroma_mode = 0;
+    int32_t chroma_loc_override = -1;
 };
 
 // Throws HeifError (parse) or UnsupportedError (valid stream, tool outside this path).

@@ -179,9 +179,10 @@ void vui_parameters(RbspReader &r, SequenceParameterSet &s) {
             s.matrix_coeffs = int(r.read_bits(8));
         }
     }
-    if (r.read_flag()) {
-        r.read_ue();
-        r.read_ue();
+    if (r.read_flag()) {  // chroma_loc_info_present_flag
+        s.chroma_loc_present = true;
+        s.chroma_loc_top = r.read_ue_max(5, "chroma_sample_loc_type_top_field");
+        r.read_ue();  // chroma_sample_loc_type_bottom_field: stills are frames
     }
     r.read_bits(3);
     if (r.read_flag())

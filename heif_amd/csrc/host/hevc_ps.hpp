@@ -62,6 +62,9 @@ struct SequenceParameterSet {
     bool video_full_range_flag = false;
     int colour_primaries = 2, transfer_characteristics = 2, matrix_coeffs = 2;
     bool range_extension_tools = false;
+    // VUI chroma_loc_info: chroma_sample_loc_type_top_field (0 when not signalled)
+    bool chroma_loc_present = false;
+    int chroma_loc_top = 0;
 
     int chroma_array_type() const { return separate_colour_plane_flag ? 0 : chroma_format_idc; }
     int pic_width_in_ctbs_y() const { return (pic_width_in_luma_samples + (1 << log2_ctb_size) - 1) >> log2_ctb_size; }

@@ -134,6 +134,8 @@ inline void color_coefs(uint32_t matrix, bool full, ColorArgs &c) {
 enum : int { RENDER_RGB8 = 0, RENDER_RGBA8 = 1, RENDER_RGB16 = 2, RENDER_RGBA16 = 3 };
 constexpr int kRenderXf = 4;  // added to a kernel's format parameter: the colour-managed instantiation
 constexpr int kRenderTone = 8;  // added beside kRenderXf: the instantiation that also knows the tone stage of HDR sources
+// added beside both: the instantiations that also know bilinear chroma upsampling (ChromaRef)
+constexpr int kRenderChromaUp = 16;
 constexpr int kRenderTile = 64;                   // axis-swapping images: 64 x 64 output pixels per workgroup
 constexpr int kRenderRowW = 256, kRenderRowH = 16;  // the others: 256 x 16
 struct RenderDesc {
@@ -268,6 +270,20 @@ struct ToneBlock {
 };
 static_assert(sizeof(ColorRef) == 56, "ColorRef: a multiple of 8 bytes behind the descriptors");
 
+// Bilinear chroma upsampling (chroma_up.hpp; include/heifgpu.h "chroma upsampling"): one
+// ChromaRef per image behind the call's ColorRefs, read by the kRenderChromaUp
+// instantiations only, which a call launches when one of its images is set to bilinear
+// (such a call always carries ColorRefs, with lut == 0 for its unmanaged images).  The
+// fields live here and not in RenderDesc so that the descriptors, and with them the
+// machine code of every other instantiation, stay what they were.
+struct ChromaRef {
+    int32_t mode;    // 0: replicate (also every 4:4:4 / 4:0:0 image), 1: bilinear
+    int32_t px, py;  // chroma_phase(); py < 0: no vertical filter (4:2:2)
+    int32_t wc, hc;  // the chroma planes' size in samples: where the taps clamp
+    int32_t pad;
+};
+static_assert(sizeof(ChromaRef) == 24, "ChromaRef: a multiple of 8 bytes behind the ColorRefs");
+
 // parse modes (BatchArgs::parse_mode; heifgpu_batch_opts::parse_mode)
 // (4 was r05's row waves, HEIFGPU_PARSE_ROWS: removed in ABI 6, prepare answers HEIFGPU_E_UNSUPPORTED)
 enum : int { PARSE_AUTO = 0, PARSE_LANES = 1, PARSE_SOLO = 2, PARSE_SPREAD = 3 };
@@ -345,7 +361,8 @@ hipError_t launch_gather_tiles(const GatherArgs &g, hipStream_t s);
 // one launch over (max_tiles, n_images); descs on the device.  color: RENDER_MANAGED, the
 // colour-managed kernels, with a ColorRef per image behind the n_images descriptors (lut == 0:
 // image i untouched), or RENDER_TONE, the kernels that also take ColorRefs with a tone stage
-enum : int { RENDER_PLAIN = 0, RENDER_MANAGED = 1, RENDER_TONE = 2 };
+// RENDER_CHROMA: the kernels that take everything, with a ChromaRef per image behind the ColorRefs
+enum : int { RENDER_PLAIN = 0, RENDER_MANAGED = 1, RENDER_TONE = 2, RENDER_CHROMA = 3 };
 // Desc: RenderDesc, ScaleDesc or TensorDesc (instantiated in render.hip)
 template <typename Desc>
 hipError_t launch_render(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, int color,
@@ -368,6 +385,17 @@ hipError_t launch_render_tone<ResampleDesc>(const ResampleDesc *descs, int n_ima
 template <>
 hipError_t launch_render_tone<ResampleTensorDesc>(const ResampleTensorDesc *descs, int n_images, int max_tiles,
                                                   int format, int bytes_per_sample, hipStream_t s);
+// launch_render's for RENDER_CHROMA: the kRenderChromaUp instantiations, code objects of their own
+// (render_chroma.hip, resample_chroma.hip)
+template <typename Desc>
+hipError_t launch_render_chroma(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                                hipStream_t s);
+template <>
+hipError_t launch_render_chroma<ResampleDesc>(const ResampleDesc *descs, int n_images, int max_tiles, int format,
+                                              int bytes_per_sample, hipStream_t s);
+template <>
+hipError_t launch_render_chroma<ResampleTensorDesc>(const ResampleTensorDesc *descs, int n_images, int max_tiles,
+                                                    int format, int bytes_per_sample, hipStream_t s);
 hipError_t launch_parse(const BatchArgs &a, hipStream_t s);
 // (launch_parse's: the kernels of parse_solo.hip and parse_lean.hip)
 hipError_t launch_parse_solo(const BatchArgs &a, hipStream_t s);

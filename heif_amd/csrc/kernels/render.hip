@@ -52,6 +52,13 @@
 // luminance, one 8-byte gather of the gain pair, three 64-bit products, then the same
 // matrix and out_lut); the others of the batch take the managed or unmanaged path by a
 // uniform branch.  Those instantiations are compiled from this file as render_tone.hip.
+//
+// Bilinear chroma upsampling adds a third bit, kRenderChromaUp: the instantiations (with
+// all three bits, render_chroma.hip) that a call launches when one of its images is set to
+// it.  A ChromaRef per image follows the ColorRefs; for such an image (a uniform branch)
+// convert() forms C' from the clamped 2 x 2 neighbourhood of Cb and of Cr (chroma_up.hpp)
+// in place of the one replicated sample, and k_render_scaled walks its columns with
+// scale_columns_up; everything behind that is unchanged.
 #include <type_traits>
 
 #include "color_xform.hpp"
@@ -70,6 +77,7 @@ __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
     constexpr int FMT = FMTX & 3;
     constexpr bool XF = (FMTX & kRenderXf) != 0;
     constexpr bool TONE = (FMTX & kRenderTone) != 0;  // (with XF: an image's ColorRef may carry a tone stage)
+    constexpr bool CUP = (FMTX & kRenderChromaUp) != 0;  // (with XF: a ChromaRef per image behind the ColorRefs)
     constexpr bool WIDE = FMT >= RENDER_RGB16;
     constexpr int T = kRenderTile, LP = kRenderTile + 1;  // LDS pitch in dwords: 65, not 64 (bank conflicts)
     __shared__ uint32_t tile_lds[(WIDE ? 2 : 1) * T * LP];
@@ -92,6 +100,7 @@ __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
     }
 #endif
     const ToneW tw = tone_weights<TONE>(x);
+    const ChromaRef cu = chroma_ref_of<CUP>(descs);
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
     const int tx = (int)blockIdx.x % d.tiles_x, ty = (int)blockIdx.x / d.tiles_x;
     const Px none = {0, 0};
@@ -102,7 +111,7 @@ __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
         for (int r = 0; r < kRenderRowH; ++r) {
             const int oy = ty * kRenderRowH + r;
             if (oy >= d.out_h) break;
-            Px p = valid ? convert<Pel, FMT>(d, ox, oy) : none;
+            Px p = valid ? convert<Pel, FMT, CUP>(d, ox, oy, cu) : none;
             if constexpr (XF) {
                 if (x.lut) xform_pixel<FMT, TONE>(x, p, staged, tw);  // (uniform: the image's transform, or none)
             }
@@ -115,7 +124,7 @@ __global__ void __launch_bounds__(256) k_render(const RenderDesc *descs) {
     for (int i = 0; i < T / 4; ++i) {
         const int oxl = wave * (T / 4) + i, ox = ox0 + oxl, oy = oy0 + lane;
         if (ox < d.out_w && oy < d.out_h) {
-            Px p = convert<Pel, FMT>(d, ox, oy);
+            Px p = convert<Pel, FMT, CUP>(d, ox, oy, cu);
             if constexpr (XF) {
                 if (x.lut) xform_pixel<FMT, TONE>(x, p, staged, tw);
             }
@@ -186,12 +195,13 @@ struct ScaleChroma {
 
 // convert()'s arithmetic for the two columns of one source row (samples as loaded),
 // weighted into the column sums; every product has factors below 2^23
-template <int FMT>
+// (UP: cc holds C' of either column, chroma_up.hpp: two sets of products whatever the format)
+template <int FMT, bool UP = false>
 __device__ __forceinline__ void scale_acc(const RenderDesc &d, const int (&ys)[2], const ScaleChroma &cc,
                                           const int (&al)[2], uint32_t w, uint32_t (&acc)[2][4]) {
     int tr[2] = {0, 0}, tg[2] = {0, 0}, tb[2] = {0, 0};  // the chroma terms of R, G, B
     if (d.chroma) {
-        const int n = chroma_sx(d.chroma) ? 1 : 2;  // a subsampled pair shares its sample: one set of products
+        const int n = !UP && chroma_sx(d.chroma) ? 1 : 2;  // a subsampled pair shares its sample: one set of products
         for (int c = 0; c < n; ++c) {
             const int cb = (cc.cb[c] >> d.shift) - d.cmid, cr = (cc.cr[c] >> d.shift) - d.cmid;
             tr[c] = __mul24(d.cr_r, cr);
@@ -276,6 +286,90 @@ __device__ __forceinline__ void scale_columns(const ScaleDesc &s, int x0, int x1
     }
 }
 
+// scale_columns for an image with bilinear chroma upsampling (cu.mode != 0).  A chroma row
+// in use holds, per plane, the two taps of either luma column (neighbouring columns share
+// samples: up to three different ones); row r waits in slot r & 1, and the two rows a
+// luma row taps are equal or consecutive, so they never share a slot.  A row is loaded
+// when the walk first needs it, with its group's luma loads; C' is formed and rounded per
+// luma sample in front of scale_acc's products.
+struct ScaleChromaRow {
+    int cb[2][2], cr[2][2];  // [column][tap], as loaded
+};
+
+template <typename Pel, int FMT>
+__device__ __forceinline__ void scale_columns_up(const ScaleDesc &s, const ChromaRef &cu, int x0, int x1, int ka0, int ka1,
+                                                 uint32_t alo, uint32_t ahi, uint32_t (&sum)[2][4]) {
+    constexpr int G = kScaleRowGroup;
+    const RenderDesc &d = s.r;
+    const uint32_t oa = (uint32_t)s.oa;
+    const ChromaTap tx[2] = {chroma_tap(x0, cu.px, cu.wc), chroma_tap(x1, cu.px, cu.wc)};
+    ScaleChromaRow cur[2] = {};     // the chroma rows in use, by parity
+    int in_row[2] = {-1, -1};       // their numbers
+    auto load_row = [&](int yc) {
+        ScaleChromaRow r;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            r.cb[c][0] = sample_g<Pel>(d.plane[1], d.pitch[1], tx[c].i0, yc);
+            r.cb[c][1] = sample_g<Pel>(d.plane[1], d.pitch[1], tx[c].i1, yc);
+            r.cr[c][0] = sample_g<Pel>(d.plane[2], d.pitch[2], tx[c].i0, yc);
+            r.cr[c][1] = sample_g<Pel>(d.plane[2], d.pitch[2], tx[c].i1, yc);
+        }
+        return r;
+    };
+    for (int k0 = ka0; k0 < ka1; k0 += G) {
+        int ly[G][2], la[G][2];
+        ScaleChromaRow lc[G][2];
+        bool enter[G][2];
+        ChromaTap ty[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int y = s.ma * min(k0 + g, ka1 - 1) + s.ta;
+            ly[g][0] = sample_g<Pel>(d.plane[0], d.pitch[0], x0, y);
+            ly[g][1] = sample_g<Pel>(d.plane[0], d.pitch[0], x1, y);
+            ty[g] = chroma_tap(y, cu.py, cu.hc);
+            enter[g][0] = enter[g][1] = false;
+            lc[g][0] = lc[g][1] = ScaleChromaRow{};
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int yc = e ? ty[g].i1 : ty[g].i0;
+#pragma unroll
+                for (int slot = 0; slot < 2; ++slot)  // (constant indices: nothing goes to scratch)
+                    if ((yc & 1) == slot && yc != in_row[slot]) {  // (uniform)
+                        in_row[slot] = yc;
+                        enter[g][slot] = true;
+                        lc[g][slot] = load_row(yc);
+                    }
+            }
+            la[g][0] = la[g][1] = 0;
+            if ((FMT & 1) && d.alpha) {
+                if (d.alpha_bps == 2) {
+                    la[g][0] = sample_g<uint16_t>(d.alpha, d.alpha_pitch, x0, y);
+                    la[g][1] = sample_g<uint16_t>(d.alpha, d.alpha_pitch, x1, y);
+                } else {
+                    la[g][0] = sample_g<uint8_t>(d.alpha, d.alpha_pitch, x0, y);
+                    la[g][1] = sample_g<uint8_t>(d.alpha, d.alpha_pitch, x1, y);
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int k = k0 + g;
+            if (k >= ka1) break;  // (uniform; the repeated rows past the end were loaded for nothing)
+            if (enter[g][0]) cur[0] = lc[g][0];
+            if (enter[g][1]) cur[1] = lc[g][1];
+            const ScaleChromaRow r0 = (ty[g].i0 & 1) ? cur[1] : cur[0], r1 = (ty[g].i1 & 1) ? cur[1] : cur[0];
+            ScaleChroma cc;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                cc.cb[c] = chroma_value(r0.cb[c][0], r0.cb[c][1], r1.cb[c][0], r1.cb[c][1], tx[c], ty[g]);
+                cc.cr[c] = chroma_value(r0.cr[c][0], r0.cr[c][1], r1.cr[c][0], r1.cr[c][1], tx[c], ty[g]);
+            }
+            const uint32_t w = min((uint32_t)(k + 1) * oa, ahi) - max((uint32_t)k * oa, alo);
+            scale_acc<FMT, true>(d, ly[g], cc, la[g], w, sum);
+        }
+    }
+}
+
 __device__ __forceinline__ const ScaleDesc &scale_of(const ScaleDesc &s) { return s; }
 __device__ __forceinline__ const ScaleDesc &scale_of(const TensorDesc &t) { return t.s; }
 
@@ -284,6 +378,7 @@ __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
     constexpr int FMT = FMTX & 3;
     constexpr bool XF = (FMTX & kRenderXf) != 0;  // (as k_render's)
     constexpr bool TONE = (FMTX & kRenderTone) != 0;
+    constexpr bool CUP = (FMTX & kRenderChromaUp) != 0;
     constexpr bool TENSOR = std::is_same<Desc, TensorDesc>::value;  // (else ScaleDesc: the integer surfaces)
     constexpr bool WIDE = FMT >= RENDER_RGB16;
     constexpr int NCH = (FMT & 1) ? 4 : 3;
@@ -294,6 +389,7 @@ __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
     const ScaleDesc &s = scale_of(dd);
     const RenderDesc &d = s.r;
     if ((int)blockIdx.x >= d.tiles) return;  // (a smaller image of the batch: the whole workgroup leaves)
+    const ChromaRef cu = chroma_ref_of<CUP>(descs);
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
     const int a0 = ((int)blockIdx.x / d.tiles_x) * s.na, b0 = ((int)blockIdx.x % d.tiles_x) * s.nb;
     const int a1 = min(a0 + s.na, s.oa), b1 = min(b0 + s.nb, s.ob);
@@ -320,7 +416,10 @@ __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
                 // a column outside the footprint repeats its neighbour and is never read back
                 const int x0c = max(x0, xmin), x1c = min(x0 + 1, xmax - 1);
                 uint32_t sum[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-                scale_columns<Pel, FMT>(s, x0c, x1c, ka0, ka1, alo, ahi, sum);
+                bool up = false;
+                if constexpr (CUP) up = cu.mode != 0;  // (uniform)
+                if (up) scale_columns_up<Pel, FMT>(s, cu, x0c, x1c, ka0, ka1, alo, ahi, sum);
+                else scale_columns<Pel, FMT>(s, x0c, x1c, ka0, ka1, alo, ahi, sum);
 #pragma unroll
                 for (int c = 0; c < NCH; ++c)
                     reinterpret_cast<uint2 *>(colsum + c * kScaleCols)[t] = make_uint2(sum[0][c], sum[1][c]);
@@ -447,7 +546,11 @@ void launch_fmt(const Desc *descs, dim3 grid, int format, hipStream_t s) {
 #define HG_LAUNCH_FMT(XF, Desc)                                                   \
     template void launch_fmt<uint8_t, XF>(const Desc *, dim3, int, hipStream_t); \
     template void launch_fmt<uint16_t, XF>(const Desc *, dim3, int, hipStream_t)
-#if defined(HG_RENDER_TONE_UNIT)
+#if defined(HG_RENDER_CHROMA_UNIT)
+HG_LAUNCH_FMT(kRenderXf | kRenderTone | kRenderChromaUp, RenderDesc);
+HG_LAUNCH_FMT(kRenderXf | kRenderTone | kRenderChromaUp, ScaleDesc);
+HG_LAUNCH_FMT(kRenderXf | kRenderTone | kRenderChromaUp, TensorDesc);
+#elif defined(HG_RENDER_TONE_UNIT)
 HG_LAUNCH_FMT(kRenderXf | kRenderTone, RenderDesc);
 HG_LAUNCH_FMT(kRenderXf | kRenderTone, ScaleDesc);
 HG_LAUNCH_FMT(kRenderXf | kRenderTone, TensorDesc);
@@ -463,7 +566,21 @@ HG_LAUNCH_FMT(0, RenderDesc);
 
 }  // namespace
 
-#if defined(HG_RENDER_TONE_UNIT)
+#if defined(HG_RENDER_CHROMA_UNIT)
+// (render_chroma.hip: the instantiations that know everything, bilinear chroma upsampling included)
+template <typename Desc>
+hipError_t launch_render_chroma(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                                hipStream_t s) {
+    constexpr int ALL = kRenderXf | kRenderTone | kRenderChromaUp;
+    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
+    if (bytes_per_sample == 1) launch_fmt<uint8_t, ALL>(descs, grid, format, s);
+    else launch_fmt<uint16_t, ALL>(descs, grid, format, s);
+    return hipGetLastError();
+}
+template hipError_t launch_render_chroma(const RenderDesc *, int, int, int, int, hipStream_t);
+template hipError_t launch_render_chroma(const ScaleDesc *, int, int, int, int, hipStream_t);
+template hipError_t launch_render_chroma(const TensorDesc *, int, int, int, int, hipStream_t);
+#elif defined(HG_RENDER_TONE_UNIT)
 template <typename Desc>
 hipError_t launch_render_tone(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
                               hipStream_t s) {
@@ -479,6 +596,7 @@ template hipError_t launch_render_tone(const TensorDesc *, int, int, int, int, h
 template <typename Desc>
 hipError_t launch_render(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, int color,
                          hipStream_t s) {
+    if (color == RENDER_CHROMA) return launch_render_chroma(descs, n_images, max_tiles, format, bytes_per_sample, s);
     if (color == RENDER_TONE) return launch_render_tone(descs, n_images, max_tiles, format, bytes_per_sample, s);
     const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
     if (bytes_per_sample == 1) {

@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <type_traits>
 
+#include "chroma_up.hpp"
 #include "color_xform.hpp"
 #include "kernels.hpp"
 
@@ -87,12 +88,51 @@ __device__ __forceinline__ void xform_any(const ColorRef &x, const ToneW &tw, ui
     xform_rgb(x, R, G, B, staged);
 }
 
-template <typename Pel, int FMT>
-__device__ __forceinline__ Px convert(const RenderDesc &d, int ox, int oy) {
+// ---- bilinear chroma upsampling (the kRenderChromaUp instantiations; cu.mode != 0) ----
+// a call's ChromaRefs lie behind its gridDim.y descriptors and as many ColorRefs
+template <bool CUP, typename Desc>
+__device__ __forceinline__ ChromaRef chroma_ref_of(const Desc *descs) {
+    ChromaRef cu{};
+    if constexpr (CUP)
+        cu = reinterpret_cast<const ChromaRef *>(reinterpret_cast<const ColorRef *>(descs + gridDim.y) + gridDim.y)[blockIdx.y];
+    return cu;
+}
+
+// C' of Cb and Cr at decoded luma position (x, y), samples as decoded (chroma_up.hpp): the
+// clamped 2 x 2 neighbourhood of each plane, 1 x 2 without a vertical filter (uniform).
+// Load: sample<Pel> or sample_g<Pel>.
+template <typename Load>
+__device__ __forceinline__ void chroma_up_pair(const RenderDesc &d, const ChromaRef &cu, int x, int y, Load load, int &cb,
+                                               int &cr) {
+    const ChromaTap tx = chroma_tap(x, cu.px, cu.wc), ty = chroma_tap(y, cu.py, cu.hc);
+    const int b00 = load(d.plane[1], d.pitch[1], tx.i0, ty.i0), b01 = load(d.plane[1], d.pitch[1], tx.i1, ty.i0);
+    const int r00 = load(d.plane[2], d.pitch[2], tx.i0, ty.i0), r01 = load(d.plane[2], d.pitch[2], tx.i1, ty.i0);
+    int b10 = b00, b11 = b01, r10 = r00, r11 = r01;
+    if (cu.py >= 0) {
+        b10 = load(d.plane[1], d.pitch[1], tx.i0, ty.i1), b11 = load(d.plane[1], d.pitch[1], tx.i1, ty.i1);
+        r10 = load(d.plane[2], d.pitch[2], tx.i0, ty.i1), r11 = load(d.plane[2], d.pitch[2], tx.i1, ty.i1);
+    }
+    cb = chroma_value(b00, b01, b10, b11, tx, ty);
+    cr = chroma_value(r00, r01, r10, r11, tx, ty);
+}
+
+template <typename Pel, int FMT, bool CUP = false>
+__device__ __forceinline__ Px convert(const RenderDesc &d, int ox, int oy, const ChromaRef &cu = ChromaRef{}) {
     const int x = d.m[0] * ox + d.m[1] * oy + d.t[0], y = d.m[2] * ox + d.m[3] * oy + d.t[1];
     const int ys = sample<Pel>(d.plane[0], d.pitch[0], x, y) >> d.shift;
     int cb = 0, cr = 0;
-    if (d.chroma) {
+    if constexpr (CUP) {
+        if (d.chroma && cu.mode) {  // (uniform)
+            chroma_up_pair(d, cu, x, y, [](uint64_t p, int32_t pitch, int cx, int cy) { return sample<Pel>(p, pitch, cx, cy); },
+                           cb, cr);
+            cb = (cb >> d.shift) - d.cmid;
+            cr = (cr >> d.shift) - d.cmid;
+        } else if (d.chroma) {
+            const int xc = x >> chroma_sx(d.chroma), yc = y >> chroma_sy(d.chroma);
+            cb = (sample<Pel>(d.plane[1], d.pitch[1], xc, yc) >> d.shift) - d.cmid;
+            cr = (sample<Pel>(d.plane[2], d.pitch[2], xc, yc) >> d.shift) - d.cmid;
+        }
+    } else if (d.chroma) {
         const int xc = x >> chroma_sx(d.chroma), yc = y >> chroma_sy(d.chroma);
         cb = (sample<Pel>(d.plane[1], d.pitch[1], xc, yc) >> d.shift) - d.cmid;
         cr = (sample<Pel>(d.plane[2], d.pitch[2], xc, yc) >> d.shift) - d.cmid;

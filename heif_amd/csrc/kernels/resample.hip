@@ -54,11 +54,21 @@ struct RawPx {
     int y, cb, cr, a;
 };
 
-template <typename Pel, int FMT>
-__device__ __forceinline__ RawPx load_raw(const RenderDesc &d, int ox, int oy) {
+// (CUP, cu.mode != 0: cb and cr are C' of the pixel's position, chroma_up.hpp, as convert()'s)
+template <typename Pel, int FMT, bool CUP = false>
+__device__ __forceinline__ RawPx load_raw(const RenderDesc &d, int ox, int oy, const ChromaRef &cu = ChromaRef{}) {
     const int x = d.m[0] * ox + d.m[1] * oy + d.t[0], y = d.m[2] * ox + d.m[3] * oy + d.t[1];
     RawPx r = {sample_g<Pel>(d.plane[0], d.pitch[0], x, y), 0, 0, 0};
-    if (d.chroma) {
+    if constexpr (CUP) {
+        if (d.chroma && cu.mode) {  // (uniform)
+            chroma_up_pair(d, cu, x, y, [](uint64_t p, int32_t pitch, int cx, int cy) { return sample_g<Pel>(p, pitch, cx, cy); },
+                           r.cb, r.cr);
+        } else if (d.chroma) {
+            const int xc = x >> chroma_sx(d.chroma), yc = y >> chroma_sy(d.chroma);
+            r.cb = sample_g<Pel>(d.plane[1], d.pitch[1], xc, yc);
+            r.cr = sample_g<Pel>(d.plane[2], d.pitch[2], xc, yc);
+        }
+    } else if (d.chroma) {
         const int xc = x >> chroma_sx(d.chroma), yc = y >> chroma_sy(d.chroma);
         r.cb = sample_g<Pel>(d.plane[1], d.pitch[1], xc, yc);
         r.cr = sample_g<Pel>(d.plane[2], d.pitch[2], xc, yc);
@@ -96,6 +106,7 @@ __global__ void __launch_bounds__(256) k_render_resampled(const Desc *descs) {
     constexpr int FMT = FMTX & 3;
     constexpr bool XF = (FMTX & kRenderXf) != 0;  // (as k_render's)
     constexpr bool TONE = (FMTX & kRenderTone) != 0;
+    constexpr bool CUP = (FMTX & kRenderChromaUp) != 0;
     constexpr bool TENSOR = std::is_same<Desc, ResampleTensorDesc>::value;
     constexpr bool WIDE = FMT >= RENDER_RGB16;
     constexpr int NCH = (FMT & 1) ? 4 : 3;
@@ -113,6 +124,7 @@ __global__ void __launch_bounds__(256) k_render_resampled(const Desc *descs) {
     const RenderDesc &d = render_of(dd);
     const RsParams &p = dd.p;
     if ((int)blockIdx.x >= d.tiles) return;  // (a smaller image of the batch: the whole workgroup leaves)
+    const ChromaRef cu = chroma_ref_of<CUP>(descs);
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
     const int sx0 = ((int)blockIdx.x % d.tiles_x) * TW, sy0 = ((int)blockIdx.x / d.tiles_x) * TH;
     const int nx = min(TW, d.out_w - sx0), ny = min(TH, d.out_h - sy0);
@@ -179,7 +191,7 @@ __global__ void __launch_bounds__(256) k_render_resampled(const Desc *descs) {
                         for (int r0 = 0; r0 < nr; r0 += G) {
                             RawPx raw[G];
 #pragma unroll
-                            for (int g = 0; g < G; ++g) raw[g] = load_raw<Pel, FMT>(d, cx + t, ry + min(r0 + g, nr - 1));
+                            for (int g = 0; g < G; ++g) raw[g] = load_raw<Pel, FMT, CUP>(d, cx + t, ry + min(r0 + g, nr - 1), cu);
 #pragma unroll
                             for (int g = 0; g < G; ++g) {
                                 const int r = r0 + g;
@@ -196,7 +208,7 @@ __global__ void __launch_bounds__(256) k_render_resampled(const Desc *descs) {
                             RawPx raw[G];
 #pragma unroll
                             for (int g = 0; g < G; ++g)
-                                raw[g] = load_raw<Pel, FMT>(d, cx + min(c0 + g * (256 / RC), nc - 1), ry + r);
+                                raw[g] = load_raw<Pel, FMT, CUP>(d, cx + min(c0 + g * (256 / RC), nc - 1), ry + r, cu);
 #pragma unroll
                             for (int g = 0; g < G; ++g) {
                                 const int c = c0 + g * (256 / RC);
@@ -334,10 +346,23 @@ void launch_fmt(const Desc *descs, dim3 grid, int format, hipStream_t s) {
     }
 }
 
-#if !defined(HG_RENDER_TONE_UNIT)
+#if defined(HG_RENDER_CHROMA_UNIT)
+// (resample_chroma.hip: this file compiled with HG_RENDER_CHROMA_UNIT, the instantiations that
+// know everything, bilinear chroma upsampling included, as a code object of their own)
+template <typename Desc>
+hipError_t launch_resampled_chroma(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                                   hipStream_t s) {
+    constexpr int ALL = kRenderXf | kRenderTone | kRenderChromaUp;
+    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
+    if (bytes_per_sample == 1) launch_fmt<uint8_t, ALL>(descs, grid, format, s);
+    else launch_fmt<uint16_t, ALL>(descs, grid, format, s);
+    return hipGetLastError();
+}
+#elif !defined(HG_RENDER_TONE_UNIT)
 template <typename Desc>
 hipError_t launch_resampled(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample, int color,
                             hipStream_t s) {
+    if (color == RENDER_CHROMA) return launch_render_chroma(descs, n_images, max_tiles, format, bytes_per_sample, s);
     if (color == RENDER_TONE) return launch_render_tone(descs, n_images, max_tiles, format, bytes_per_sample, s);
     const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
     if (bytes_per_sample == 1) {
@@ -364,7 +389,18 @@ hipError_t launch_resampled_tone(const Desc *descs, int n_images, int max_tiles,
 
 }  // namespace
 
-#if !defined(HG_RENDER_TONE_UNIT)
+#if defined(HG_RENDER_CHROMA_UNIT)
+template <>
+hipError_t launch_render_chroma<ResampleDesc>(const ResampleDesc *descs, int n_images, int max_tiles, int format,
+                                              int bytes_per_sample, hipStream_t s) {
+    return launch_resampled_chroma(descs, n_images, max_tiles, format, bytes_per_sample, s);
+}
+template <>
+hipError_t launch_render_chroma<ResampleTensorDesc>(const ResampleTensorDesc *descs, int n_images, int max_tiles,
+                                                    int format, int bytes_per_sample, hipStream_t s) {
+    return launch_resampled_chroma(descs, n_images, max_tiles, format, bytes_per_sample, s);
+}
+#elif !defined(HG_RENDER_TONE_UNIT)
 template <>
 hipError_t launch_render<ResampleDesc>(const ResampleDesc *descs, int n_images, int max_tiles, int format,
                                        int bytes_per_sample, int color, hipStream_t s) {

@@ -875,7 +875,17 @@ long synth_sps(const synth_params *P, uint8_t *out, size_t cap) {
     bw_bits(&w, 0, 1);
     bw_bits(&w, 0, 1);
     bw_bits(&w, P->strong_intra ? 1 : 0, 1);
-    bw_bits(&w, 0, 1); /* vui */
+    if (P->chroma_loc < 0) {
+        bw_bits(&w, 0, 1); /* vui */
+    } else {
+        bw_bits(&w, 1, 1); /* vui_parameters_present_flag */
+        bw_bits(&w, 0, 3); /* aspect_ratio_info, overscan_info, video_signal_type: absent */
+        bw_bits(&w, 1, 1); /* chroma_loc_info_present_flag */
+        bw_ue(&w, (uint32_t)P->chroma_loc);
+        bw_ue(&w, (uint32_t)P->chroma_loc);
+        bw_bits(&w, 0, 3); /* neutral_chroma_indication, field_seq, frame_field_info_present */
+        bw_bits(&w, 0, 3); /* default_display_window, vui_timing_info, bitstream_restriction: absent */
+    }
     bw_bits(&w, 0, 1); /* extensions */
     bw_align1(&w);
     return finish_nal(&w, out, cap);
@@ -935,6 +945,7 @@ long synth_pps(const synth_params *P, uint8_t *out, size_t cap) {
 
 int synth_check_params(const synth_params *P) {
     if (P->chroma_format < 0 || P->chroma_format > 3) return -1;
+    if (P->chroma_loc < -1 || P->chroma_loc > 5) return -1;
     if (P->bit_depth < 8 || P->bit_depth > 12) return -1;
     if (P->log2_min_cb < 3 || P->log2_ctb < 4 || P->log2_ctb > 6 || P->log2_min_cb > P->log2_ctb) return -1;
     if (P->log2_min_tb != 2 || P->log2_max_tb < P->log2_min_tb || P->log2_max_tb > 5 ||

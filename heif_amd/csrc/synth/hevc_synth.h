@@ -43,6 +43,9 @@ typedef struct {
     /* nonzero: every PCM sample is ANDed with it (3: samples 0..3, a stream dense in
      * emulation-prevention bytes); 0: the samples as drawn */
     int32_t pcm_mask;
+    /* -1: no VUI (vui_parameters_present_flag 0); 0..5: a VUI whose only present part is
+     * chroma_loc_info, chroma_sample_loc_type_top_field = _bottom_field = this value */
+    int32_t chroma_loc;
 } synth_params;
 
 /* Each returns the NAL unit length (2-byte header included, emulation

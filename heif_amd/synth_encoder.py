@@ -35,7 +35,7 @@ class _Params(ctypes.Structure):
         ("tile_col_w", ctypes.c_int32 * 8), ("tile_row_h", ctypes.c_int32 * 8)] + [
         (n, ctypes.c_int32) for n in ("slice_ctus", "slice_dependent", "slice_lf_across", "slice_dbk_vary",
                                       "pcm", "pcm_bd_y", "pcm_bd_c", "pcm_log2_min", "pcm_log2_max",
-                                      "pcm_lf_disabled", "pcm_pct", "pcm_mask")]
+                                      "pcm_lf_disabled", "pcm_pct", "pcm_mask", "chroma_loc")]
 
 
 @dataclasses.dataclass
@@ -95,6 +95,9 @@ class SynthParams:
     pcm_lf_disabled: int = 0
     pcm_pct: int = 10
     pcm_mask: int = 0  # nonzero: PCM samples ANDed with it (3: a stream dense in emulation-prevention bytes)
+    # -1: no VUI, as ever; 0..5: a VUI whose only present part is chroma_loc_info with this
+    # chroma_sample_loc_type in both fields
+    chroma_loc: int = -1
 
     def _c(self) -> _Params:
         c = _Params()
@@ -295,7 +298,7 @@ def _len_prefixed(nal: bytes) -> bytes:
 
 def grid_heic(out_w: int, out_h: int, p: SynthParams, seed: int = 0, pictures: Optional[List[bytes]] = None,
               layout: Optional[BoxLayout] = None, transforms: Tuple[bytes, ...] = (), colr=None,
-              aux: Tuple["AuxImage", ...] = ()) -> bytes:
+              aux: Tuple["AuxImage", ...] = (), tile_params: Optional[List[SynthParams]] = None) -> bytes:
     """A grid HEIC of ceil(out_w/W) x ceil(out_h/H) synthetic tiles of p's
     size, tile k drawn with seed (seed << 16) + k.  `colr` (nclx_box) and then
     `transforms` (clap_box / irot_box / imir_box, applied in the order given) are
@@ -303,13 +306,14 @@ def grid_heic(out_w: int, out_h: int, p: SynthParams, seed: int = 0, pictures: O
     `aux` entry (an AuxImage) becomes a grid item of its own over the same
     out_w x out_h, cut into tiles of ITS params' size (tile k drawn with seed
     (a.seed << 16) + k), with auxC and an 'auxl' reference to the primary grid
-    ('prem' from the primary when premultiplied).  With the defaults the file is
-    byte for byte what it was before these arguments existed."""
+    ('prem' from the primary when premultiplied).  tile_params[k] gives tile k
+    parameter sets (an hvcC) of its own, of p's geometry, in place of p's.  With
+    the defaults the file is byte for byte what it was before these arguments existed."""
     cols = -(-out_w // (p.width - p.conf_right))
     rows = -(-out_h // (p.height - p.conf_bottom))
     n = rows * cols
     if pictures is None:
-        items_data = [picture_item(p, (seed << 16) + k) for k in range(n)]
+        items_data = [picture_item(tile_params[k] if tile_params else p, (seed << 16) + k) for k in range(n)]
     else:
         items_data = [_len_prefixed(pic) for pic in pictures]
     vps, sps, pps = parameter_sets(p)
@@ -323,6 +327,10 @@ def grid_heic(out_w: int, out_h: int, p: SynthParams, seed: int = 0, pictures: O
         props.append(box)
         grid_idx.append(len(props))
     assoc = [(grid_id, grid_idx)] + [(k + 2, [1, 2]) for k in range(n)]
+    if tile_params is not None:
+        for k in range(n):
+            props.append(hvcc(tile_params[k], *parameter_sets(tile_params[k])))
+            assoc[1 + k] = (k + 2, [len(props), 2])
     refs = _box(b"dimg", struct.pack(">HH", grid_id, n) + b"".join(struct.pack(">H", k + 2) for k in range(n)))
     idat = items[0][2]
     next_id = n + 2

@@ -235,7 +235,9 @@ int heifgpu_ipc_close(void *dev_ptr);
  * and 3.  Matrix from info->matrix_coeffs (H.273: 1 BT.709, 9 BT.2020 NCL,
  * anything else BT.601), range from info->full_range, 4:2:0 / 4:2:2 chroma by
  * sample replication, samples above 8 bits rounded down to 8.  Fixed point: 16
- * fractional bits, round half up, clip to 0..255.  Asynchronous on `stream`. */
+ * fractional bits, round half up, clip to 0..255.  Asynchronous on `stream`.
+ * The call takes no image handle, so heifgpu_image_set_chroma_upsampling does not
+ * reach it: chroma here is always replicated. */
 int heifgpu_ycbcr_to_rgb(heifgpu_ctx *ctx, const heifgpu_image_info *info, const heifgpu_planes *in, void *rgb,
                          int32_t rgb_pitch, void *stream);
 
@@ -612,6 +614,51 @@ int heifgpu_image_get_hdr(const heifgpu_image *img, heifgpu_hdr_info *out);
 int heifgpu_color_transform_make_hdr(const heifgpu_image *img, uint32_t dst, uint32_t bits, uint32_t tone_map,
                                      double peak_nits, heifgpu_hdr_transform *out);
 
+/* ---- chroma upsampling: replicate (default) or bilinear at the signalled location ----
+ * (added within ABI 6: new entry points only; no existing struct changes layout.)
+ * By default every render turns 4:2:0 / 4:2:2 chroma into RGB by replication: a luma
+ * sample reads the one chroma sample of its cell.  An image set to
+ * HEIFGPU_CHROMA_BILINEAR renders as if Cb and Cr had first been upsampled to the luma
+ * grid by the filter below and the unchanged pipeline (>> shift, the matrix, the clip,
+ * then area average / filter / colour transform / tone map / tensor epilogue) ran on that
+ * 4:4:4 picture.  Integers only:
+ *   t  = the SPS VUI's chroma_sample_loc_type_top_field (0 without a VUI or with
+ *        chroma_loc_info_present_flag 0; above 5 fails the parse), or the caller's override;
+ *   4:2:0: px = t & 1 (0: co-sited with even luma columns, 1: midway);
+ *          py = 1 (midway) for t >> 1 == 0, 0 (top) for 1, 2 (bottom) for 2;
+ *   4:2:2: px = 0, no vertical filter; 4:4:4 and 4:0:0: the setting has no effect;
+ *   luma column x: u = 2x - px, i0 = floor(u / 4), f = u & 3: chroma columns i0 and i0 + 1,
+ *        each clamped to [0, Wc - 1], weights 4 - f and f; rows likewise with v = 2y - py
+ *        (4:2:2: row y, weights 4 and 0);
+ *   C'(x, y) = (sum wy * wx * C + 8) >> 4 on the decoded samples at the image's depth.
+ * x, y, Wc, Hc are those of the decoded planes: a clap crop interpolates across its own
+ * edge from real samples, only the edge of the coded picture clamps.
+ * The setting lives on the image handle, where every render call and
+ * heifgpu_window_source_rect* read it, so the two cannot disagree about the samples read.
+ * heifgpu_image_set_chroma_upsampling is host only; loc is -1 (the file's location) or
+ * 0..5, anything else HEIFGPU_E_INVALID.  It must not be called while a render of that
+ * image is being submitted from another thread (a submitted render is not affected).
+ * A call with one bilinear image runs kernels of its own (one launch, as ever); a
+ * call without one runs what it ran before, bit for bit.
+ * heifgpu_chroma_upsample is the rule on the host for one plane: `in` holds w_c x h_c
+ * samples (uint8 for bits == 8, else uint16; pitch bytes a row), the luma-grid rectangle
+ * [x0, x0 + w) x [y0, y0 + h) of C' goes to `out` (same type, out_pitch bytes a row).
+ * chroma_format_idc 1 or 2, loc 0..5, the rectangle inside 2 * w_c columns and 2 * h_c
+ * (4:2:2: h_c) rows, else HEIFGPU_E_INVALID. */
+enum { HEIFGPU_CHROMA_REPLICATE = 0, HEIFGPU_CHROMA_BILINEAR = 1 };
+typedef struct {
+    uint32_t loc;           /* chroma_sample_loc_type_top_field of the first coded picture's SPS, 0..5 */
+    uint32_t signalled;     /* 1 if the SPS carries chroma_loc_info */
+    int32_t  loc_override;  /* the caller's location, -1: none */
+    uint32_t mode;          /* HEIFGPU_CHROMA_* */
+    uint32_t sub_width_c, sub_height_c;
+} heifgpu_chroma_info;
+int heifgpu_image_get_chroma(const heifgpu_image *img, heifgpu_chroma_info *out);
+int heifgpu_image_set_chroma_upsampling(heifgpu_image *img, uint32_t mode, int32_t loc);
+int heifgpu_chroma_upsample(const void *in, uint32_t w_c, uint32_t h_c, int32_t pitch, uint32_t bits,
+                            uint32_t chroma_format_idc, uint32_t loc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                            void *out, int32_t out_pitch);
+
 /* ---- window decode: decode only the pictures a window reads ----------------
  * (added within ABI 6: new entry points only; heifgpu_batch_opts keeps its layout.)
  * A render of a window of the displayed picture (heifgpu_scale's x, y, width,
@@ -623,9 +670,14 @@ int heifgpu_color_transform_make_hdr(const heifgpu_image *img, uint32_t dst, uin
  *     heifgpu_display_info); their bounding box is the box of the whole window,
  *     m being a signed permutation;
  *   - the box is grown to the chroma sample grid (x0 down and x1 up to multiples
- *     of SubWidthC, y likewise with SubHeightC; 4:0:0 and 4:4:4 grow nothing),
- *     because the render replicates chroma: a luma sample reads the chroma sample
- *     of its cell;
+ *     of SubWidthC, y likewise with SubHeightC; 4:0:0 and 4:4:4 grow nothing).
+ *     For an image that replicates chroma (the default) that is all: a luma sample
+ *     reads the chroma sample of its cell.  For an image set to bilinear chroma
+ *     upsampling ("chroma upsampling" below) a luma column x reads the chroma
+ *     columns floor((2x - px) / 4) and the next one, so the box then also covers the
+ *     cells of chroma columns floor((2*x0 - px) / 4) to floor((2*(x1 - 1) - px) / 4) + 1
+ *     ([x0, x1) the luma box), clamped to the plane and scaled back by SubWidthC; rows
+ *     likewise with py and SubHeightC (4:2:2 has no vertical filter and grows no rows);
  *   - and clipped to width x height (heifgpu_image_info).
  * That is exactly the set of decoded samples heifgpu_render_batch (whole
  * picture), heifgpu_render_batch_scaled and heifgpu_render_batch_tensor read for
@@ -655,7 +707,8 @@ int heifgpu_color_transform_make_hdr(const heifgpu_image *img, uint32_t dst, uin
  * mode chosen by picture count, heifgpu_batch_parse_geometry and
  * heifgpu_batch_lanes_variant all speak of the pictures selected. */
 typedef struct { uint32_t x, y, width, height; } heifgpu_rect;  /* width == 0 && height == 0: everything */
-/* host only: the source rectangle of `window` (NULL: the whole displayed picture) */
+/* host only: the source rectangle of `window` (NULL: the whole displayed picture),
+ * for the image's chroma upsampling as it is set at the time of the call */
 int heifgpu_window_source_rect(const heifgpu_image *img, const heifgpu_rect *window, heifgpu_rect *src);
 /* host only: the grid tiles a source rectangle selects (src NULL: everything):
  * columns [col0, col0 + cols), rows [row0, row0 + rows); cols * rows tiles.  Any

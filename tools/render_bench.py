@@ -74,12 +74,20 @@ variants alternated in one process in each of the --runs runs:
   tensor224_f16   heifgpu_render_batch_tensor_color, COVER to 224 x 224, f16 CHW
 each as `managed` and as `tone`; tone / managed is reported.
 
+--chroma bilinear measures bilinear chroma upsampling: `full`, and
+COVER to 224 x 224 and 512 x 384 through the area, BILINEAR and BICUBIC filters, each
+with images that replicate chroma and with the same planes under images set to
+bilinear, alternated in one process.  bilinear / replicate is reported, nothing is
+gated.  With HEIFGPU_LIBRARY naming the parent commit's build (no setter) the replicate
+columns alone are measured: the figures to hold this build's replicate launch against.
+
 usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json]
-                                    [--scaled | --tensor | --color | --filter | --tone]
+                                    [--scaled | --tensor | --color | --filter | --tone | --chroma bilinear]
 """
 import argparse
 import ctypes
 import json
+import os
 import pathlib
 import statistics
 import sys
@@ -636,6 +644,91 @@ def filter_main(args):
         pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
 
 
+def chroma_main(args):
+    """--chroma bilinear: the full-size render, the area-scaled render and the filtered render
+    (cover 224 x 224 and 512 x 384, rotation 0 and 3, RGB8) of a batch whose images replicate
+    chroma and of the same planes under images set to bilinear upsampling, interleaved in the
+    same run.  The replicate figures are this library's launch of the kernels it had before:
+    run the tool again with HEIFGPU_LIBRARY naming the parent commit's build (which has no
+    setter: the replicate columns alone are then measured) to set them beside the parent's."""
+    n = args.images
+    dev = torch.device("cuda", 0)
+    ctx = H.DecodeContext(0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    golden = (ROOT / "tests" / "golden" / "halfmoonbay.heic").read_bytes()
+    g = torch.Generator(device=dev).manual_seed(1)
+    ys = [torch.randint(0, 256, (HGT, W), generator=g, device=dev, dtype=torch.int32).to(torch.uint8) for _ in range(n)]
+    cs = [[torch.randint(0, 256, (HGT // 2, W // 2), generator=g, device=dev, dtype=torch.int32).to(torch.uint8)
+           for _ in range(n)] for _ in range(2)]
+    planes = (_lib.Planes * n)()
+    for i in range(n):
+        for c, t in enumerate((ys[i], cs[0][i], cs[1][i])):
+            planes[i].plane[c] = t.data_ptr()
+            planes[i].pitch[c] = t.stride(0) * t.element_size()
+    has_setter = hasattr(_lib.lib, "heifgpu_image_set_chroma_upsampling")
+    modes = ("replicate", args.chroma) if has_setter and args.chroma != "replicate" else ("replicate",)
+    result = {"images": n, "width": W, "height": HGT, "reps": args.reps, "runs": args.runs, "modes": list(modes),
+              "library": os.environ.get("HEIFGPU_LIBRARY", "default"), "device": torch.cuda.get_device_name(0), "rgb8": {}}
+    for rot in (0, 3):
+        variants, keep = [], []
+        for mode in modes:
+            img = H.HeifImage.parse(forced_rotation(golden, rot))
+            if mode != "replicate":
+                img.chroma_upsampling = mode
+            keep.append(img)
+            d = img.display
+            imgs = (ctypes.c_void_p * n)(*[img._h.value] * n)
+            full_out = torch.empty((n, d.out_height, d.out_width, 3), dtype=torch.uint8, device=dev)
+            keep.append(full_out)
+
+            def surfaces(out):
+                surf = (_lib.Surface * n)()
+                for i in range(n):
+                    surf[i].pixels, surf[i].pitch = out[i].data_ptr(), out[i].stride(0)
+                return surf
+
+            def full(imgs=imgs, surf=surfaces(full_out)):
+                _lib.check(_lib.lib.heifgpu_render_batch(ctx._h, imgs, n, planes, None, None, _lib.PIX_RGB8, surf, stream))
+            variants.append((f"full_{mode}", full))
+            for box, bw, bh in (("cover224", 224, 224), ("cover512", 512, 384)):
+                sc = (_lib.Scale * n)()
+                for i in range(n):
+                    _lib.check(_lib.lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, _lib.FIT_COVER, ctypes.byref(sc[i])))
+                for fname, code in (("area", _lib.FILTER_AREA), ("bilinear", _lib.FILTER_BILINEAR), ("bicubic", _lib.FILTER_BICUBIC)):
+                    out = torch.empty((n, bh, bw, 3), dtype=torch.uint8, device=dev)
+                    keep.append(out)
+
+                    def scaled(imgs=imgs, sc=sc, surf=surfaces(out), code=code):
+                        _lib.check(_lib.lib.heifgpu_render_batch_resampled(ctx._h, imgs, n, planes, None, None, _lib.PIX_RGB8,
+                                                                           sc, code, None, surf, stream))
+                    variants.append((f"{box}_{fname}_{mode}", scaled))
+        for _, fn in variants:  # warm-up
+            fn()
+        torch.cuda.synchronize()
+        ms = {name: [] for name, _ in variants}
+        for _ in range(args.runs):
+            for name, fn in variants:
+                ms[name].append(timed(fn, args.reps))
+        r = {}
+        for name, _ in variants:
+            v = ms[name]
+            r[name] = {"ms_per_batch": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
+                       "ms_runs": [round(x, 4) for x in v], "spread_ms": round(max(v) - min(v), 4)}
+        if len(modes) == 2:
+            for name in [k for k in r if k.endswith("_replicate")]:
+                b = r[name[:-len("replicate")] + modes[1]]
+                b["of_replicate"] = round(b["ms_per_batch"] / r[name]["ms_per_batch"], 3)
+                b["minus_replicate_ms"] = round(b["ms_per_batch"] - r[name]["ms_per_batch"], 4)
+        result["rgb8"][f"rotation_{rot}"] = r
+        print(f"rotation {rot}: " + ", ".join(f"{name} {r[name]['ms_per_batch']:.3f} ms (spread {r[name]['spread_ms']:.3f})"
+                                              for name, _ in variants), flush=True)
+        del variants, keep
+    print(json.dumps(result))
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=128)
@@ -647,7 +740,11 @@ def main():
     ap.add_argument("--color", action="store_true", help="measure the colour-managed render (see above)")
     ap.add_argument("--filter", action="store_true", help="measure the bilinear / bicubic render (see above)")
     ap.add_argument("--tone", action="store_true", help="measure the tone stage of the HDR render (see above)")
+    ap.add_argument("--chroma", choices=("replicate", "bilinear"), default=None,
+                    help="measure the render, scaled and filtered calls with chroma upsampling set, beside replicate")
     args = ap.parse_args()
+    if args.chroma:
+        return chroma_main(args)
     if args.filter:
         return filter_main(args)
     if args.tone:
