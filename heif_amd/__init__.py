@@ -24,7 +24,7 @@ from ._lib import HeifGpuError, UnsupportedError, lib
 
 __all__ = [
     "HeicDecoder", "HeifImage", "DecodeContext", "DeviceBatch", "DecodedImage", "RbspReader",
-    "HeifGpuError", "UnsupportedError", "ipc_export", "ipc_open", "ipc_close", "chroma_dims", "ColorDescription",
+    "HeifGpuError", "UnsupportedError", "ipc_export", "ipc_open", "ipc_close", "chroma_dims", "ColorDescription", "GainMapDescription",
     "HdrDescription", "ChromaDescription",
 ]
 
@@ -144,6 +144,41 @@ class HeifImage:
         return HdrDescription(hi.transfer, hi.max_cll if clli else None, hi.max_fall if clli else None,
                               hi.mastering_max * 1e-4 if mdcv else None, hi.mastering_min * 1e-4 if mdcv else None,
                               hi.status)
+
+    @property
+    def gain_map(self) -> Optional["GainMapDescription"]:
+        """The image's HDR gain map (heifgpu_image_get_gain), None without one: kind
+        "iso" (an ISO 21496-1 'tmap' item names this image as its base; the payload's
+        fields are reported, log2 values for the headrooms, min and max) or "apple"
+        (an auxiliary image with Apple's URN; its headroom is the caller's to give),
+        item_id of the gain-map image, and what a transform of it answers (status)."""
+        gi = _lib.GainInfo()
+        _lib.check(lib.heifgpu_image_get_gain(self._h, ctypes.byref(gi)))
+        if gi.kind == _lib.GAIN_NONE:
+            return None
+        return GainMapDescription(_lib.GAIN_KINDS[gi.kind], gi.gain_item_id, gi.status, gi.version, gi.minimum_version,
+                                  gi.writer_version, bool(gi.multichannel), bool(gi.use_base_colour_space),
+                                  gi.base_headroom, gi.alternate_headroom, gi.gain_min, gi.gain_max, gi.gamma,
+                                  gi.base_offset, gi.alternate_offset)
+
+    def gain_transform(self, gain: "HeifImage", colorspace: str = "display-p3", encoding: str = "linear",
+                       pq_bits: int = 10, headroom: Optional[float] = None, display_headroom: Optional[float] = None,
+                       sdr_white: float = 203.0):
+        """The gain-map HDR transform of this base image with its parsed gain-map image
+        `gain` (heifgpu_gain_transform_make) to "srgb", "display-p3" or "bt2020", for the
+        "linear" or the "pq" encoding: a _lib.GainTransform.  headroom is the Apple
+        rule's (required there); display_headroom None means the full HDR rendition."""
+        if colorspace not in _lib.HDR_COLORSPACES:
+            raise ValueError(f"colorspace {colorspace!r}: one of {sorted(_lib.HDR_COLORSPACES)}")
+        if encoding not in ("linear", "pq"):
+            raise ValueError(f"encoding {encoding!r}: 'linear' or 'pq'")
+        t = _lib.GainTransform()
+        _lib.check(lib.heifgpu_gain_transform_make(
+            self._h, gain._h, _lib.HDR_COLORSPACES[colorspace], int(self.info.bit_depth),
+            _lib.GAIN_PQ if encoding == "pq" else _lib.GAIN_LINEAR, int(pq_bits),
+            0.0 if headroom is None else float(headroom), 0.0 if display_headroom is None else float(display_headroom),
+            float(sdr_white), ctypes.byref(t)))
+        return t
 
     def _chroma_info(self) -> _lib.ChromaInfo:
         ci = _lib.ChromaInfo()
@@ -293,6 +328,25 @@ class ChromaDescription:
     loc: int               # chroma_sample_loc_type_top_field of the SPS, 0..5 (0 when not signalled)
     signalled: bool        # the SPS's VUI carries chroma_loc_info
     subsampling: tuple     # (SubWidthC, SubHeightC)
+
+
+@dataclass
+class GainMapDescription:
+    kind: str                 # "apple" or "iso"
+    item_id: int              # the gain-map image item
+    status: int               # HEIFGPU_OK, or what a transform answers
+    version: int = 0          # the rest: the ISO 21496-1 payload ("iso"; zeros otherwise)
+    minimum_version: int = 0
+    writer_version: int = 0
+    multichannel: bool = False
+    use_base_colour_space: bool = False
+    base_headroom: float = 0.0
+    alternate_headroom: float = 0.0
+    gain_min: float = 0.0
+    gain_max: float = 0.0
+    gamma: float = 0.0
+    base_offset: float = 0.0
+    alternate_offset: float = 0.0
 
 
 @dataclass
@@ -570,6 +624,54 @@ class DecodeContext:
         res = [torch.empty((o.image.display.out_height, o.image.display.out_width, ch),
                            dtype=torch.int16 if wide else torch.uint8, device=dev) for o in outs]
         self._submit("heifgpu_render_batch", outs, alphas, colorspace, wide, stream, (f,), self._surfaces(res), tone_map)
+        return res
+
+    def render_hdr(self, outs: Sequence[DecodedImage], gains: Sequence[DecodedImage], fmt: str = "rgba16f",
+                   colorspace: str = "display-p3", headroom: Optional[float] = None,
+                   display_headroom: Optional[float] = None, sdr_white: float = 203.0, pq_bits: int = 10,
+                   alphas: Optional[Sequence[Optional[DecodedImage]]] = None, stream: Optional[int] = None,
+                   transforms=None, out=None):
+        """The HDR rendition of a batch of SDR base pictures with their decoded gain
+        maps, with ONE heifgpu_render_batch_gain call (one kernel launch): a list of
+        (H', W', C) device tensors with clap / irot / imir applied, float16 in linear
+        light with 1.0 at SDR white for "rgb16f" / "rgba16f", uint16 PQ codes of depth
+        pq_bits (10, 12, 16; sdr_white cd/m2 at SDR white) for "rgb16pq" / "rgba16pq",
+        in "srgb", "display-p3" or "bt2020" primaries (out of gamut clips).  gains[i] is
+        the decoded gain-map image of outs[i] (HeifImage.gain_map.item_id), of any size.
+        headroom is required for Apple maps (theirs lies in the Exif maker note, which
+        is not read); display_headroom limits the rendition to a display's headroom
+        (None: full).  alphas as in render().  transforms: one _lib.GainTransform per
+        image in place of those made here; out: the tensors to write into.  Images
+        decoded for a window, or set to bilinear chroma, are refused (UnsupportedError)
+        before anything is launched."""
+        torch = self._torch
+        if fmt not in _lib.HDR_FORMATS:
+            raise ValueError(f"fmt {fmt!r}: one of {sorted(_lib.HDR_FORMATS)}")
+        f = _lib.HDR_FORMATS[fmt]
+        ch, pq = (4 if f & 1 else 3), f >= _lib.PIX_HDR_RGB16PQ
+        self._check_images("render_hdr", outs, alphas, gains=gains, transforms=transforms, out=out)
+        if any(g is None or g.image is None for g in gains):
+            raise ValueError("render_hdr needs gain images that carry their HeifImage (alloc_outputs)")
+        for i, o in enumerate(outs):
+            for name, im in (("image", o), ("gain image", gains[i]), ("alpha image", alphas[i] if alphas is not None else None)):
+                if im is not None and im.valid is not None:
+                    raise UnsupportedError(_lib.HEIFGPU_E_UNSUPPORTED,
+                                           f"render_hdr: {name} {i} was decoded for a window ({im.valid}) only")
+        if transforms is None:
+            transforms = [o.image.gain_transform(g.image, colorspace, "pq" if pq else "linear", pq_bits, headroom,
+                                                 display_headroom, sdr_white) for o, g in zip(outs, gains)]
+        dev = torch.device("cuda", self.device)
+        dtype = torch.uint16 if pq else torch.float16
+        res = out if out is not None else [
+            torch.empty((o.image.display.out_height, o.image.display.out_width, ch), dtype=dtype, device=dev) for o in outs]
+        imgs, aimgs, aplanes = self._render_args(outs, alphas)
+        gimgs, _, _ = self._render_args(gains, None)
+        xf = (ctypes.c_void_p * max(len(outs), 1))(*[ctypes.addressof(t) for t in transforms])
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(lib.heifgpu_render_batch_gain(self._h, imgs, len(outs), DecodeContext.planes_of(outs), gimgs,
+                                                 DecodeContext.planes_of(gains), aimgs, aplanes, f, xf,
+                                                 self._surfaces(res), ctypes.c_void_p(stream)))
         return res
 
     @staticmethod
@@ -991,6 +1093,26 @@ class HeicDecoder:
             return ctx.render_scaled([out], size, mode, fmt, alphas, colorspace=colorspace, filter=filter,
                                      tone_map=tone_map)[0]
         return ctx.render([out], fmt, alphas, colorspace=colorspace, tone_map=tone_map)[0]
+
+    @classmethod
+    def decode_hdr(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, colorspace: str = "display-p3",
+                   headroom: Optional[float] = None, display_headroom: Optional[float] = None,
+                   sdr_white: float = 203.0, pq_bits: int = 10):
+        """The HDR rendition of a file whose primary image has a gain map
+        (HeifImage.gain_map): decodes the primary image, its gain-map image and, when
+        it has one, its alpha plane, then DecodeContext.render_hdr of that one picture.
+        fmt None picks "rgba16f" when there is alpha, else "rgb16f".  ValueError for a
+        file without a gain map; an Apple map needs the caller's headroom."""
+        ctx = cls.context(device)
+        out, alpha = cls._decode_pair(data, device, None, "contain", "all", True)
+        gm = out.image.gain_map
+        if gm is None:
+            raise ValueError("decode_hdr: the file's primary image has no gain map")
+        gain = cls._decode_image(ctx, HeifImage.parse(data, gm.item_id), None)
+        if fmt is None:
+            fmt = "rgba16f" if alpha is not None else "rgb16f"
+        alphas = [alpha] if alpha is not None and fmt.startswith("rgba") else None
+        return ctx.render_hdr([out], [gain], fmt, colorspace, headroom, display_headroom, sdr_white, pq_bits, alphas)[0]
 
     @classmethod
     def decode_tensor(cls, data: bytes, size, mode: str = "cover", device: int = 0, flip: int = 0,

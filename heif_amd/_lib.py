@@ -232,6 +232,41 @@ class ChromaInfo(ctypes.Structure):  # heifgpu_chroma_info
 CHROMA_REPLICATE, CHROMA_BILINEAR = 0, 1
 CHROMA_MODES = {"replicate": CHROMA_REPLICATE, "bilinear": CHROMA_BILINEAR}
 
+
+class GainInfo(ctypes.Structure):
+    """heifgpu_gain_info: the kind of an image's gain map (GAIN_*), the gain-map image item,
+    what a transform answers (status) and the fields of an ISO 21496-1 'tmap' payload."""
+    _fields_ = [("kind", ctypes.c_uint32), ("gain_item_id", ctypes.c_uint32), ("status", ctypes.c_int32),
+                ("version", ctypes.c_uint32), ("minimum_version", ctypes.c_uint32), ("writer_version", ctypes.c_uint32),
+                ("multichannel", ctypes.c_uint32), ("use_base_colour_space", ctypes.c_uint32),
+                ("base_headroom", ctypes.c_double), ("alternate_headroom", ctypes.c_double),
+                ("gain_min", ctypes.c_double), ("gain_max", ctypes.c_double), ("gamma", ctypes.c_double),
+                ("base_offset", ctypes.c_double), ("alternate_offset", ctypes.c_double)]
+
+
+GAIN_T_ENTRIES, GAIN_E_ENTRIES = 4097, 641
+
+
+class GainTransform(ctypes.Structure):
+    """heifgpu_gain_transform: the tables, the Q14 matrix and the offsets of one base image
+    with its gain map, for one destination and one encoding."""
+    _fields_ = [("bits", ctypes.c_uint32), ("gain_bits", ctypes.c_uint32), ("dst", ctypes.c_uint32),
+                ("encoding", ctypes.c_uint32), ("pq_bits", ctypes.c_uint32), ("kind", ctypes.c_uint32),
+                ("m", ctypes.c_int32 * 9), ("k_b", ctypes.c_int32), ("k_a", ctypes.c_int32),
+                ("weight", ctypes.c_double), ("headroom", ctypes.c_double), ("sdr_white", ctypes.c_double),
+                ("in_lut", (ctypes.c_uint16 * 4096) * 3), ("T", ctypes.c_uint32 * (GAIN_T_ENTRIES + 1)),
+                ("E", ctypes.c_uint32 * (GAIN_E_ENTRIES + 1))]
+
+
+GAIN_NONE, GAIN_APPLE, GAIN_ISO = 0, 1, 2
+GAIN_KINDS = {GAIN_NONE: "none", GAIN_APPLE: "apple", GAIN_ISO: "iso"}
+CS_BT2020 = 2  # a destination of the gain-map HDR render only
+HDR_COLORSPACES = {"srgb": 0, "display-p3": 1, "bt2020": CS_BT2020}
+GAIN_LINEAR, GAIN_PQ = 0, 1
+PIX_HDR_RGB16F, PIX_HDR_RGBA16F, PIX_HDR_RGB16PQ, PIX_HDR_RGBA16PQ = 4, 5, 6, 7
+HDR_FORMATS = {"rgb16f": PIX_HDR_RGB16F, "rgba16f": PIX_HDR_RGBA16F, "rgb16pq": PIX_HDR_RGB16PQ,
+               "rgba16pq": PIX_HDR_RGBA16PQ}
+
 PARSE_AUTO, PARSE_LANES, PARSE_SOLO, PARSE_SPREAD = 0, 1, 2, 3
 PARSE_ROWS = 4  # ABI 5 only; removed in ABI 6 (prepare answers HEIFGPU_E_UNSUPPORTED)
 PARSE_MODES = {"auto": PARSE_AUTO, "lanes": PARSE_LANES, "solo": PARSE_SOLO, "spread": PARSE_SPREAD}
@@ -258,6 +293,8 @@ EXPORTS = (
     "heifgpu_resample_apply", "heifgpu_window_source_rect_resampled",
     "heifgpu_image_get_hdr", "heifgpu_color_transform_make_hdr",
     "heifgpu_image_get_chroma", "heifgpu_image_set_chroma_upsampling", "heifgpu_chroma_upsample",
+    "heifgpu_image_get_gain", "heifgpu_gain_transform_make", "heifgpu_gain_apply", "heifgpu_gain_sample",
+    "heifgpu_render_batch_gain",
 )
 
 
@@ -363,6 +400,13 @@ def _load() -> ctypes.CDLL:
         "heifgpu_image_set_chroma_upsampling": (I32, [VP, U32, ctypes.c_int32]),
         "heifgpu_chroma_upsample": (I32, [VP, U32, U32, ctypes.c_int32, U32, U32, U32, U32, U32, U32, U32, VP,
                                           ctypes.c_int32]),
+        "heifgpu_image_get_gain": (I32, [VP, P(GainInfo)]),
+        "heifgpu_gain_transform_make": (I32, [VP, VP, U32, U32, U32, U32, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_double, P(GainTransform)]),
+        "heifgpu_gain_apply": (I32, [P(GainTransform), P(ctypes.c_uint16), P(U32), SZ, P(ctypes.c_uint16)]),
+        "heifgpu_gain_sample": (I32, [VP, U32, U32, ctypes.c_int32, U32, U32, U32, P(U32)]),
+        "heifgpu_render_batch_gain": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), P(VP), P(Planes), U32, P(VP),
+                                            P(Surface), VP]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     # (and no window decode: DecodeContext.prepare without windows then goes through prepare_ex)
@@ -377,7 +421,10 @@ def _load() -> ctypes.CDLL:
                 # the HDR render (tone_map= then needs a build that has it)
                 "heifgpu_image_get_hdr", "heifgpu_color_transform_make_hdr",
                 # bilinear chroma upsampling (chroma= other than "replicate" then needs a build that has it)
-                "heifgpu_image_get_chroma", "heifgpu_image_set_chroma_upsampling", "heifgpu_chroma_upsample"}
+                "heifgpu_image_get_chroma", "heifgpu_image_set_chroma_upsampling", "heifgpu_chroma_upsample",
+                # the gain-map HDR render (render_hdr / decode_hdr then need a build that has it)
+                "heifgpu_image_get_gain", "heifgpu_gain_transform_make", "heifgpu_gain_apply", "heifgpu_gain_sample",
+                "heifgpu_render_batch_gain"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue

@@ -1,6 +1,6 @@
 // api.hpp — what the units of the C ABI layer (include/heifgpu.h) share: the two
 // opaque handles every unit looks into, the error message, and the device and
-// pinned buffers.  image.cpp, context.cpp, render.cpp and batch.cpp hold the calls.
+// pinned buffers.  image.cpp, gain.cpp, context.cpp, render.cpp and batch.cpp hold the calls.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -11,6 +11,7 @@
 #include "../host/icc.hpp"
 #include "../host/resample.hpp"
 #include "../kernels/color_xform.hpp"
+#include "../kernels/gain_xform.hpp"
 #include "api.hpp"
 
 using namespace hg;
@@ -670,4 +671,159 @@ int heifgpu_render_batch_tensor_color(heifgpu_ctx *ctx, const heifgpu_image *con
                                       const heifgpu_color_transform *const *xf, const heifgpu_tensor_surface *out,
                                       void *stream) {
     return render_tensor_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, fmt, scale, flip, xf, out, stream);
+}
+
+// ---- the gain-map HDR render (k_render_gain; include/heifgpu.h "Gain-map HDR render") ----
+// The device image of a gain transform as 16-bit units (the cache's key): in_lut[3][n], the
+// pairs T[i], T[i + 1] for i = 0 .. maxg, for PQ the pairs E[i], E[i + 1] for i = 0 .. 639, and a
+// tag that no colour table ends in.
+static void gain_table_image(const heifgpu_gain_transform &t, std::vector<uint16_t> &key, int32_t &t_off, int32_t &e_off) {
+    const size_t tn = size_t(1) << t.bits, ng = size_t(1) << t.gain_bits;  // ng = maxg + 1 pairs
+    const size_t ne = t.encoding == HEIFGPU_GAIN_PQ ? size_t(kGainEPairs) : 0;
+    const size_t toff = 6 * tn, eoff = toff + 8 * ng, end = eoff + 8 * ne;  // bytes: multiples of 8
+    std::vector<uint8_t> img(end + 8);
+    for (int c = 0; c < 3; ++c) std::memcpy(img.data() + 2 * c * tn, t.in_lut[c], 2 * tn);
+    for (size_t i = 0; i < ng; ++i) std::memcpy(img.data() + toff + 8 * i, &t.T[i], 8);  // T[i], T[i + 1]
+    for (size_t i = 0; i < ne; ++i) std::memcpy(img.data() + eoff + 8 * i, &t.E[i], 8);
+    std::memcpy(img.data() + end, "gain map", 8);
+    key.resize(img.size() / 2);
+    std::memcpy(key.data(), img.data(), img.size());
+    t_off = int32_t(toff);
+    e_off = ne ? int32_t(eoff) : 0;
+}
+
+int heifgpu_render_batch_gain(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                              const heifgpu_image *const *gain_imgs, const heifgpu_planes *gain_in,
+                              const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                              const heifgpu_gain_transform *const *xf, const heifgpu_surface *out, void *stream) {
+    static_assert(sizeof(RenderDesc) % 8 == 0, "the GainRefs behind the descriptors are 8-byte aligned");
+    static_assert(HEIFGPU_PIX_HDR_RGB16F - 4 == GAIN_RGB16F && HEIFGPU_PIX_HDR_RGBA16PQ - 4 == GAIN_RGBA16PQ, "HDR formats");
+    if (!ctx || !imgs || !in || !gain_imgs || !gain_in || !xf || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (format < HEIFGPU_PIX_HDR_RGB16F || format > HEIFGPU_PIX_HDR_RGBA16PQ) return fail(HEIFGPU_E_INVALID, "format");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    const int hf = int(format) - 4;
+    const bool pq = (hf & 2) != 0, with_alpha = (hf & 1) != 0;
+    const uint32_t wide = with_alpha ? HEIFGPU_PIX_RGBA16 : HEIFGPU_PIX_RGB16;  // what the descriptors are filled for
+    std::vector<RenderDesc> descs(n);
+    std::vector<GainRef> refs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!imgs[i] || !gain_imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
+        if (!xf[i]) return fail(HEIFGPU_E_INVALID, "null gain transform");
+        const heifgpu_gain_transform &t = *xf[i];
+        if (const char *why = gain_transform_invalid(t)) return fail(HEIFGPU_E_INVALID, why);
+        if (t.encoding != (pq ? HEIFGPU_GAIN_PQ : HEIFGPU_GAIN_LINEAR))
+            return fail(HEIFGPU_E_INVALID, "gain transform made for the other encoding than the format's");
+        const ParsedImage &bi = imgs[i]->img, &gi = gain_imgs[i]->img;
+        if (image_chroma_up(bi).mode != 0 || image_chroma_up(gi).mode != 0 ||
+            (with_alpha && alpha_imgs && alpha_imgs[i] && image_chroma_up(alpha_imgs[i]->img).mode != 0))
+            return fail(HEIFGPU_E_UNSUPPORTED, "gain-map render of an image set to bilinear chroma upsampling");
+        heifgpu_image_info info, ginfo;
+        heifgpu_image_get_info(imgs[i], &info);
+        heifgpu_image_get_info(gain_imgs[i], &ginfo);
+        if (t.bits != info.bit_depth) return fail(HEIFGPU_E_INVALID, "gain transform made for another depth than the base image's");
+        if (t.gain_bits != ginfo.bit_depth) return fail(HEIFGPU_E_INVALID, "gain transform made for another depth than the gain map's");
+        const uint32_t lim = uint32_t(kGainMaxSide);
+        if (info.width > lim || info.height > lim || ginfo.width > lim || ginfo.height > lim)
+            return fail(HEIFGPU_E_UNSUPPORTED, "gain-map render of a side above 65535");
+        // the map is sampled at decoded base positions: its own display map must say nothing, or the same
+        const DisplayMap &dm = bi.display, &gm = gi.display;
+        const bool ident = gm.m[0] == 1 && gm.m[1] == 0 && gm.m[2] == 0 && gm.m[3] == 1 && gm.t[0] == 0 && gm.t[1] == 0 &&
+                           gm.out_width == gi.out_width && gm.out_height == gi.out_height;
+        const bool same = std::memcmp(gm.m, dm.m, sizeof(dm.m)) == 0 && gm.t[0] == dm.t[0] && gm.t[1] == dm.t[1] &&
+                          gm.out_width == dm.out_width && gm.out_height == dm.out_height;
+        // (the base's irot / imir over the map's own whole picture, as Apple's files carry them, is the base's map at the map's size)
+        const bool turned = std::memcmp(gm.m, dm.m, sizeof(dm.m)) == 0 &&
+                            uint64_t(gm.out_width) * gm.out_height == uint64_t(gi.out_width) * gi.out_height;
+        if (!ident && !same && !turned)
+            return fail(HEIFGPU_E_UNSUPPORTED, "gain image with a display map that is neither the identity nor the base's");
+        if (!gain_in[i].plane[0]) return fail(HEIFGPU_E_INVALID, "missing gain plane");
+        if (int64_t(gain_in[i].pitch[0]) < int64_t(ginfo.width) * ginfo.bytes_per_sample)
+            return fail(HEIFGPU_E_INVALID, "gain plane pitch smaller than its row");
+        RenderDesc &d = descs[i];
+        // (the alpha image may be of another sample width here: convert() reads it by alpha_bps)
+        const heifgpu_image *const *am = with_alpha ? alpha_imgs : nullptr;
+        uint32_t abits = 0;
+        if (am && am[i]) {
+            heifgpu_image_info ai;
+            heifgpu_image_get_info(am[i], &ai);
+            abits = ai.bit_depth;
+            if (!alpha_in || !alpha_in[i].plane[0]) return fail(HEIFGPU_E_INVALID, "missing alpha plane");
+            if (ai.width != info.width || ai.height != info.height)
+                return fail(HEIFGPU_E_UNSUPPORTED, "alpha image of another size than its colour image");
+            if (abits > 12) return fail(HEIFGPU_E_UNSUPPORTED, "alpha image deeper than 12 bits");
+            if (int64_t(alpha_in[i].pitch[0]) < int64_t(ai.width) * ai.bytes_per_sample)
+                return fail(HEIFGPU_E_INVALID, "alpha plane pitch smaller than its row");
+        }
+        if (int rc = render_desc_fill(i, imgs, in, nullptr, nullptr, wide, out, dm, dm.out_width, dm.out_height, bps, d))
+            return rc;
+        if (abits) {
+            heifgpu_image_info ai;
+            heifgpu_image_get_info(am[i], &ai);
+            d.alpha = reinterpret_cast<uint64_t>(alpha_in[i].plane[0]);
+            d.alpha_pitch = alpha_in[i].pitch[0];
+            d.alpha_bps = int32_t(ai.bytes_per_sample);
+            d.alpha_shift = 0;  // the sample as decoded: the GainRef says where it goes
+        }
+        const int tw = d.swap ? kRenderTile : kRenderRowW, th = d.swap ? kRenderTile : kRenderRowH;
+        d.tiles_x = (d.out_w + tw - 1) / tw;
+        d.tiles = d.tiles_x * ((d.out_h + th - 1) / th);
+        max_tiles = std::max(max_tiles, d.tiles);
+        GainRef &g = refs[i];
+        g = GainRef{};
+        g.gain = reinterpret_cast<uint64_t>(gain_in[i].plane[0]);
+        g.gain_pitch = gain_in[i].pitch[0];
+        g.gain_bps = int32_t(ginfo.bytes_per_sample);
+        g.w = int32_t(info.width), g.h = int32_t(info.height), g.wg = int32_t(ginfo.width), g.hg = int32_t(ginfo.height);
+        g.inv_w = 1.0 / double(info.width), g.inv_h = 1.0 / double(info.height);
+        g.n = 1 << t.bits;
+        for (int k = 0; k < 9; ++k) g.m[k] = t.m[k];
+        g.k_b = t.k_b, g.k_a = t.k_a;
+        g.gmax = 256u * ((1u << t.gain_bits) - 1);
+        g.maxp = pq ? int32_t((1u << t.pq_bits) - 1) : 0;
+        g.alpha_shift = pq && abits ? int32_t(abits) - int32_t(t.pq_bits) : 0;
+        g.alpha_scale = abits ? 1.0f / float((1u << abits) - 1) : 1.0f;
+    }
+    // the tables: the context's content cache (color_refs_fill's rules)
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->color) ctx->color = new ColorCache;
+    ColorCache &cache = *ctx->color;
+    if (cache.entries.size() >= kColorCacheMax) {
+        HIP_TRY(hipDeviceSynchronize());  // nothing in flight reads a table that is freed
+        cache.clear();
+    }
+    std::vector<uint16_t> key;
+    for (size_t i = 0; i < n; ++i) {
+        gain_table_image(*xf[i], key, refs[i].t_off, refs[i].e_off);
+        ColorCache::Entry *hit = nullptr;
+        for (ColorCache::Entry &e : cache.entries)
+            if (e.key == key) hit = &e;
+        if (!hit) {
+            ColorCache::Entry e;
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e.dev), key.size() * 2));
+            const hipError_t up = hipMemcpy(e.dev, key.data(), key.size() * 2, hipMemcpyHostToDevice);  // blocking
+            if (up != hipSuccess) {
+                (void)hipFree(e.dev);
+                return fail(HEIFGPU_E_DEVICE, std::string("gain table upload: ") + hipGetErrorString(up));
+            }
+            e.key = key;
+            cache.entries.push_back(std::move(e));
+            hit = &cache.entries.back();
+        }
+        refs[i].lut = reinterpret_cast<uint64_t>(hit->dev);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RenderRing::Slot *slot = nullptr;
+    if (int rc = render_ring_slot(ctx, &slot)) return rc;
+    RenderRing::Slot &sl = *slot;
+    const size_t dbytes = n * sizeof(RenderDesc), rbytes = n * sizeof(GainRef);
+    HIP_TRY(sl.host.reserve(dbytes + rbytes));
+    HIP_TRY(sl.dev.alloc(dbytes + rbytes));
+    std::memcpy(sl.host.p, descs.data(), dbytes);
+    std::memcpy(sl.host.p + dbytes, refs.data(), rbytes);  // behind the descriptors: one copy
+    HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host.p, dbytes + rbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_render_gain(reinterpret_cast<const RenderDesc *>(sl.dev.p), int(n), max_tiles, hf, bps, s));  // the one launch
+    HIP_TRY(hipEventRecord(sl.done, s));
+    sl.pending = true;
+    return HEIFGPU_OK;
 }

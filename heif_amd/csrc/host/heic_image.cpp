@@ -352,8 +352,8 @@ ParsedImage parse_heic(const uint8_t *data, size_t len, uint32_t item_id) {
         else if (p.type == fourcc('i', 'm', 'i', 'r') && p.length >= 1) display_imir(img.display, data[p.offset] & 1u);
     }
     // alpha: the first auxiliary image of this item whose auxC (FullBox, then the
-    // zero-terminated aux_type URN) names an alpha plane; other auxiliaries (a gain
-    // map, depth) are passed over
+    // zero-terminated aux_type URN) names an alpha plane; other auxiliaries are not alpha
+    // (depth is passed over; a gain map is found further down)
     static const char *const kAlphaUrn[2] = {"urn:mpeg:hevc:2015:auxid:1", "urn:mpeg:mpegB:cicp:systems:auxiliary:alpha"};
     for (const auto &r : heif.references) {
         if (r.type != fourcc('a', 'u', 'x', 'l') || img.alpha_item_id) continue;
@@ -371,6 +371,36 @@ ParsedImage parse_heic(const uint8_t *data, size_t len, uint32_t item_id) {
             if (r.type == fourcc('p', 'r', 'e', 'm') && r.from == img.item_id &&
                 std::find(r.to.begin(), r.to.end(), img.alpha_item_id) != r.to.end())
                 img.alpha_premultiplied = 1;
+    // gain map: a 'tmap' item whose dimg lists [this item, the map] (its data kept unread; data
+    // that cannot be fetched stays empty and is a parse error when a transform is asked for) ...
+    for (const ItemInfo &it : heif.items) {
+        if (it.type != fourcc('t', 'm', 'a', 'p') || img.gain.kind) continue;
+        const std::vector<uint32_t> to = heif.references_from(fourcc('d', 'i', 'm', 'g'), it.id);
+        if (to.size() < 2 || to[0] != img.item_id) continue;
+        img.gain.kind = HEIFGPU_GAIN_ISO;
+        img.gain.item_id = to[1];
+        try {
+            // (its fields are 62 or 142 bytes: an item above 64 KiB is not copied and reads as damaged)
+            if (heif.item_data(it, nullptr) <= 65536) heif.item_data(it, &img.gain.tmap);
+        } catch (const std::exception &) {
+            img.gain.tmap.clear();
+        }
+    }
+    // ... else the first auxiliary image of this item that Apple's URN names
+    static const char kGainUrn[] = "urn:com:apple:photo:2020:aux:hdrgainmap";
+    for (const auto &r : heif.references) {
+        if (r.type != fourcc('a', 'u', 'x', 'l') || img.gain.kind) continue;
+        if (std::find(r.to.begin(), r.to.end(), img.item_id) == r.to.end()) continue;
+        const ItemInfo *ai = heif.item_info_by_item_id(r.from);
+        const Property *ac = ai ? heif.item_property(*ai, fourcc('a', 'u', 'x', 'C')) : nullptr;
+        if (!ac || ac->length < 4) continue;
+        const char *urn = reinterpret_cast<const char *>(data + ac->offset + 4);
+        const size_t ulen = strnlen(urn, ac->length - 4);
+        if (ulen == sizeof(kGainUrn) - 1 && std::memcmp(urn, kGainUrn, ulen) == 0) {
+            img.gain.kind = HEIFGPU_GAIN_APPLE;
+            img.gain.item_id = r.from;
+        }
+    }
     return img;
 }
 

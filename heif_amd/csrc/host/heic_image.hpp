@@ -3,6 +3,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "gain.hpp"
 #include "heif_reader.hpp"
 #include "hevc_ps.hpp"
 #include "icc.hpp"
@@ -82,6 +83,9 @@ struct ParsedImage {
     // Set by heifgpu_image_set_chroma_upsampling; read by the render calls and by window_source_rect.
     uint32_t chroma_mode = 0;
     int32_t chroma_loc_override = -1;
+    // the item's gain map (gain.hpp): the 'tmap' item that names it as its base, its data kept
+    // unread, else the first 'auxl' image whose auxC is Apple's gain-map URN
+    GainDesc gain;
 };
 
 // Throws HeifError (parse) or UnsupportedError (valid stream, tool outside this path).

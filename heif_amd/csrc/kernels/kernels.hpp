@@ -284,6 +284,31 @@ struct ChromaRef {
 };
 static_assert(sizeof(ChromaRef) == 24, "ChromaRef: a multiple of 8 bytes behind the ColorRefs");
 
+// The gain-map HDR render (k_render_gain, render_gain.hip; gain_xform.hpp has the arithmetic;
+// include/heifgpu.h "Gain-map HDR render"): one GainRef per image behind the call's RenderDescs,
+// which are heifgpu_render_batch's at the 16-bit formats with alpha_shift 0 (convert() then
+// hands the alpha sample on as decoded).  lut addresses the transform's tables in the
+// context's cache: in_lut[3][n] (uint16), at t_off the (maxg + 1) pairs T[i], T[i + 1] and at
+// e_off the 640 pairs E[i], E[i + 1] (uint32 each: one 8-byte gather per pair).
+struct GainRef {
+    uint64_t lut;
+    uint64_t gain;         // the gain map's luma plane
+    int32_t gain_pitch, gain_bps;
+    int32_t w, h, wg, hg;  // the decoded base and gain-map sizes
+    double inv_w, inv_h;   // 1.0 / w, 1.0 / h (gain_tap's estimate)
+    int32_t n;             // 1 << B
+    int32_t t_off, e_off;  // bytes from lut, multiples of 8
+    int32_t m[9];          // Q14
+    int32_t k_b, k_a;
+    int32_t alpha_shift;   // PQ: a >> alpha_shift, or a << -alpha_shift, to depth P
+    int32_t maxp;          // PQ: (1 << P) - 1, the alpha of an opaque pixel
+    float alpha_scale;     // linear: the binary32 nearest to 1 / maxa
+    uint32_t gmax;         // 256 * maxg: a plane that holds more than its depth allows still reads inside T
+};
+static_assert(sizeof(GainRef) % 8 == 0, "GainRef: a multiple of 8 bytes behind the descriptors");
+// k_render_gain's formats: bit 0 alpha, bit 1 PQ (HEIFGPU_PIX_HDR_* - 4)
+enum : int { GAIN_RGB16F = 0, GAIN_RGBA16F = 1, GAIN_RGB16PQ = 2, GAIN_RGBA16PQ = 3 };
+
 // parse modes (BatchArgs::parse_mode; heifgpu_batch_opts::parse_mode)
 // (4 was r05's row waves, HEIFGPU_PARSE_ROWS: removed in ABI 6, prepare answers HEIFGPU_E_UNSUPPORTED)
 enum : int { PARSE_AUTO = 0, PARSE_LANES = 1, PARSE_SOLO = 2, PARSE_SPREAD = 3 };
@@ -396,6 +421,10 @@ hipError_t launch_render_chroma<ResampleDesc>(const ResampleDesc *descs, int n_i
 template <>
 hipError_t launch_render_chroma<ResampleTensorDesc>(const ResampleTensorDesc *descs, int n_images, int max_tiles,
                                                     int format, int bytes_per_sample, hipStream_t s);
+// k_render_gain (render_gain.hip): one launch over (max_tiles, n_images); n_images RenderDescs with
+// as many GainRefs behind them on the device; format GAIN_*
+hipError_t launch_render_gain(const RenderDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                              hipStream_t s);
 hipError_t launch_parse(const BatchArgs &a, hipStream_t s);
 // (launch_parse's: the kernels of parse_solo.hip and parse_lean.hip)
 hipError_t launch_parse_solo(const BatchArgs &a, hipStream_t s);

@@ -227,15 +227,17 @@ def _be(v: int, n: int) -> bytes:
 
 def _assemble(items: List[Tuple[int, bytes, bytes]], primary: int, props: List[bytes],
               assoc: List[Tuple[int, List[int]]], iref: bytes, idat: bytes,
-              layout: Optional[BoxLayout] = None) -> bytes:
+              layout: Optional[BoxLayout] = None, hidden: Tuple[int, ...] = (), extra_meta: bytes = b"") -> bytes:
     """items: (item_id, item_type, data); data of 'grid' items lives in idat
     (construction_method 1; `idat` holds the grid items' data back to back in
-    item order), everything else in mdat."""
+    item order), everything else in mdat.  Items named in `hidden` get the infe
+    flag that hides them; `extra_meta` (a grpl box, say) goes in front of iloc."""
     L = layout or BoxLayout()
     ftyp = _box(b"ftyp", b"heic" + struct.pack(">I", 0) + b"mif1heic")
     hdlr = _fbox(b"hdlr", 0, 0, struct.pack(">I", 0) + b"pict" + bytes(12) + b"\0")
     pitm = _fbox(b"pitm", 0, 0, struct.pack(">H", primary))
-    infes = b"".join(_fbox(b"infe", 2, 0, struct.pack(">HH", iid, 0) + typ + b"\0") for iid, typ, _ in items)
+    infes = b"".join(_fbox(b"infe", 2, 1 if iid in hidden else 0, struct.pack(">HH", iid, 0) + typ + b"\0")
+                     for iid, typ, _ in items)
     # ISO/IEC 14496-12 8.11.6 infe v0 / v1: item_ID, protection index, item_name,
     # content_type, content_encoding (+ v1: extension_type); no item_type.  HEIF
     # image items need v2+, so these are metadata items the reader must skip.
@@ -283,7 +285,7 @@ def _assemble(items: List[Tuple[int, bytes, bytes]], primary: int, props: List[b
                 off += len(data)
                 body += data
         iloc = _fbox(b"iloc", 1, 0, ent)
-        meta = _fbox(b"meta", 0, 0, hdlr + pitm + iinf + iref + iprp + idat_box + iloc)
+        meta = _fbox(b"meta", 0, 0, hdlr + pitm + iinf + iref + iprp + idat_box + extra_meta + iloc)
         return meta, body
 
     meta, _ = build(0)
@@ -523,6 +525,79 @@ def display_heic(p: SynthParams, seed: int = 0, transforms: Tuple[bytes, ...] = 
         if a.premultiplied:
             refs += _box(b"prem", struct.pack(">HHH", 1, 1, iid))
     return _assemble(items, 1, props, assoc, _fbox(b"iref", 0, 0, refs) if refs else b"", b"", layout)
+
+
+# ---- HDR gain maps: Apple's auxiliary image, or the ISO 21496-1 'tmap' derived item
+GAIN_URN_APPLE = "urn:com:apple:photo:2020:aux:hdrgainmap"
+
+
+def _fraction(v, signed: bool, den: int = 1 << 16) -> bytes:
+    """A 32/32-bit fraction: a number (over `den`) or an explicit (numerator, denominator)."""
+    n, d = v if isinstance(v, tuple) else (int(round(v * den)), den)
+    return _be(int(n), 4) + _be(int(d), 4)
+
+
+def tmap_box(base_headroom=0.0, alternate_headroom=2.0, gain_min=0.0, gain_max=2.0, gamma=1.0, base_offset=1 / 64,
+             alternate_offset=1 / 64, multichannel: bool = False, use_base_colour_space: bool = True, version: int = 0,
+             minimum_version: int = 0, writer_version: int = 0, truncate: Optional[int] = None) -> bytes:
+    """The data of an ISO 21496-1 'tmap' item as include/heifgpu.h lays it out (headrooms,
+    min and max are log2 values).  Every fraction is a number or an explicit (numerator,
+    denominator); the per-channel values may be 3-sequences of them for a multichannel
+    map (one value is repeated).  truncate = n keeps only the first n bytes."""
+    out = struct.pack(">BHHB", version, minimum_version, writer_version,
+                      (0x80 if multichannel else 0) | (0x40 if use_base_colour_space else 0))
+    out += _fraction(base_headroom, False) + _fraction(alternate_headroom, False)
+    for c in range(3 if multichannel else 1):
+        pick = lambda v: v[c] if isinstance(v, list) else v  # noqa: E731
+        out += (_fraction(pick(gain_min), True) + _fraction(pick(gain_max), True) + _fraction(pick(gamma), False) +
+                _fraction(pick(base_offset), True) + _fraction(pick(alternate_offset), True))
+    return out[:truncate]
+
+
+def gainmap_heic(p: SynthParams, gain: SynthParams, seed: int = 0, gain_seed: int = 1, kind: str = "apple",
+                 tmap: Optional[bytes] = None, transforms: Tuple[bytes, ...] = (), gain_transforms: Tuple[bytes, ...] = (),
+                 colr=None, alpha: Optional[AuxImage] = None, layout: Optional[BoxLayout] = None) -> bytes:
+    """A base picture (item 1) with a gain map (item 2, usually 4:0:0 and smaller).
+    kind "apple": the map is an auxiliary image with Apple's URN and an 'auxl'
+    reference to the base.  kind "iso": the map is a hidden item, and a 'tmap' item
+    (item 3, data `tmap`, default tmap_box()) lists [base, map] in its 'dimg'
+    reference and shares an 'altr' group with the base.  kind "both": both.
+    `transforms` / `colr` go to the base as in display_heic, `gain_transforms` to the
+    map; `alpha` adds an alpha auxiliary image (the last item)."""
+    if kind not in ("apple", "iso", "both"):
+        raise ValueError(f"kind {kind!r}: 'apple', 'iso' or 'both'")
+    props = [hvcc(p, *parameter_sets(p)), _ispe(p.width - p.conf_right, p.height - p.conf_bottom)]
+    base_idx = [1, 2]
+    for box in _colr_boxes(colr) + list(transforms):
+        props.append(box)
+        base_idx.append(len(props))
+    props += [hvcc(gain, *parameter_sets(gain)), _ispe(gain.width - gain.conf_right, gain.height - gain.conf_bottom)]
+    gain_idx = [len(props) - 1, len(props)]
+    if kind != "iso":
+        props.append(auxc_box(GAIN_URN_APPLE))
+        gain_idx.append(len(props))
+    for box in gain_transforms:
+        props.append(box)
+        gain_idx.append(len(props))
+    items = [(1, b"hvc1", picture_item(p, seed)), (2, b"hvc1", picture_item(gain, gain_seed))]
+    assoc = [(1, base_idx), (2, gain_idx)]
+    refs, extra, hidden = b"", b"", ()
+    if kind != "iso":
+        refs += _box(b"auxl", struct.pack(">HHH", 2, 1, 1))
+    next_id = 3
+    if kind != "apple":
+        items.append((3, b"tmap", tmap_box() if tmap is None else tmap))
+        refs += _box(b"dimg", struct.pack(">HHHH", 3, 2, 1, 2))
+        extra = _box(b"grpl", _fbox(b"altr", 0, 0, struct.pack(">IIII", 100, 2, 3, 1)))
+        hidden = (2,) if kind == "iso" else ()
+        next_id = 4
+    if alpha is not None:
+        q = alpha.params
+        props += [hvcc(q, *parameter_sets(q)), _ispe(q.width - q.conf_right, q.height - q.conf_bottom), auxc_box(alpha.urn)]
+        assoc.append((next_id, [len(props) - 2, len(props) - 1, len(props)]))
+        items.append((next_id, b"hvc1", picture_item(q, alpha.seed)))
+        refs += _box(b"auxl", struct.pack(">HHH", next_id, 1, 1))
+    return _assemble(items, 1, props, assoc, _fbox(b"iref", 0, 0, refs), b"", layout, hidden, extra)
 
 
 # BASELINE config 5: 8K 10-bit Main-10 grid, 15 x 9 tiles of 512x512

@@ -659,6 +659,148 @@ int heifgpu_chroma_upsample(const void *in, uint32_t w_c, uint32_t h_c, int32_t 
                             uint32_t chroma_format_idc, uint32_t loc, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                             void *out, int32_t out_pitch);
 
+/* ---- Gain-map HDR render: base picture x gain map -> linear half-float or PQ --------
+ * (added within ABI 6: new entry points only; no existing struct, call or kernel changes.)
+ * An SDR base picture with a gain map is shown as HDR: every pixel of the base, in linear
+ * light, is multiplied by a factor read from a second, usually smaller, picture.
+ *
+ * WHERE THE MAP COMES FROM.  Two sources; the first wins if a file has both:
+ *   ISO 21496-1: an item of type 'tmap' whose 'dimg' reference lists [base item, gain-map
+ *     item] with the parsed image as the base.  Its data (through iloc: mdat, idat, several
+ *     extents) is kept unread at parse and read when a transform or heifgpu_image_get_gain
+ *     asks (the rule of the ICC profiles: such a file always parses and decodes).  Layout,
+ *     big-endian ("parity unpinned": written from memory of the standard and of what libavif
+ *     writes; this layout is the contract here):
+ *       u8 version (0), u16 minimum_version (0), u16 writer_version,
+ *       u8 flags (bit 7 is_multichannel, bit 6 use_base_colour_space),
+ *       u32/u32 base HDR headroom N/D, u32/u32 alternate HDR headroom N/D,
+ *       then per channel (1, or 3 when multichannel): s32/u32 gain_map_min, s32/u32
+ *       gain_map_max, u32/u32 gamma, s32/u32 base_offset, s32/u32 alternate_offset.
+ *     Headrooms, min and max are log2 values.  HEIFGPU_E_PARSE: a payload shorter than its
+ *     fields (an item whose data cannot be fetched, or of more than 64 KiB, counts as empty),
+ *     a zero denominator.  HEIFGPU_E_UNSUPPORTED: a version or minimum_version other
+ *     than 0, multichannel, use_base_colour_space == 0, alternate headroom <= base headroom
+ *     (an HDR base), gamma <= 0, |min|, |max| or a headroom above 8, an offset above 16 in
+ *     magnitude.
+ *   Apple: the first 'auxl' image of the item whose 'auxC' type is
+ *     urn:com:apple:photo:2020:aux:hdrgainmap.  Its headroom lies in the Exif maker note,
+ *     which this library does not read: the caller passes it.
+ *
+ * THE CONTRACT.  U = 65535 is the base picture's SDR white.  The base is W x H decoded
+ * samples; the gain map is Wg x Hg decoded samples of depth Bg (8..12, luma plane only),
+ * maxg = (1 << Bg) - 1; all four sides at most 65535.
+ *   Base: (c0, c1, c2) are the integers the unmanaged render gives at the image's depth B;
+ *     L_c = in_lut[c][c_c], the table heifgpu_color_transform_make builds for this item (same
+ *     ICC / nclx rules and errors; a PQ / HLG base is HEIFGPU_E_UNSUPPORTED).
+ *   Gain sample at decoded base position (sx, sy), aligned centres, exact integers:
+ *     nx = (2 sx + 1) Wg - W, dx = 2 W, ix = floor(nx / dx), fx = floor(256 (nx - ix dx) / dx),
+ *     x0 = clamp(ix, 0, Wg - 1), x1 = clamp(ix + 1, 0, Wg - 1); the same in y;
+ *     g = ((256 - fy) ((256 - fx) G[y0][x0] + fx G[y0][x1])
+ *          + fy ((256 - fx) G[y1][x0] + fx G[y1][x1]) + 128) >> 8       (Q8, 0 .. 256 maxg)
+ *     (Wg == W gives the sample itself).
+ *   Multiplier: i = g >> 8, f = g & 255, M = (T[i] (256 - f) + T[i + 1] f + 128) >> 8.  T holds
+ *     maxg + 2 u32 entries with 16 fractional bits, each at most 2^24; the last repeats.  Built
+ *     in double, rhu = round half up, w = clamp((log2(display_headroom) - Hbase) / (Halt - Hbase),
+ *     0, 1), display_headroom <= 0 meaning full (w = 1):
+ *     ISO:   T[v] = rhu(2^16 2^(w (min + (max - min) (v / maxg)^(1 / gamma)))),
+ *            k_b = rhu(U base_offset), k_a = rhu(U alternate_offset)
+ *     Apple: hr = headroom, or min(headroom, max(display_headroom, 1)) with a display_headroom;
+ *            T[v] = rhu(2^16 (1 + (hr - 1) f709(v / maxg))), f709 the BT.709 inverse OETF
+ *            (V < 0.081: V / 4.5, else ((V + 0.099) / 1.099)^(1 / 0.45)); k_b = k_a = 0; headroom
+ *            is required and lies in [1, 256], else HEIFGPU_E_INVALID.  ("parity unpinned": as
+ *            Apple's published description is remembered.  T is a public field: a caller who
+ *            knows better fills it.)  An image without a map of either kind takes this rule.
+ *   Apply:  H_c = clamp((((L_c + k_b) M + 2^15) >> 16) - k_a, 0, 2^24 - 1)     (64-bit product)
+ *   Matrix: H'_k = clamp((m[3k] H_0 + m[3k+1] H_1 + m[3k+2] H_2 + 8192) >> 14, 0, 2^24 - 1),
+ *     m the Q14 inv(Dst) Src of the colour-managed render with its row fix-up; destinations
+ *     sRGB, Display P3 and, for these calls only, BT.2020 (HEIFGPU_CS_BT2020: the nclx
+ *     primaries 9, Bradford-adapted to D50 in double).  Out of gamut clips.
+ *   Encodings, 16 bits per sample, native-endian:
+ *     linear (HEIFGPU_PIX_HDR_RGB16F / RGBA16F): F = fmul_rn((float)H'_k, c), c the binary32
+ *       nearest to 1 / 65535, then binary16 by round-to-nearest-even: 1.0 is SDR white.  Alpha:
+ *       fmul_rn((float)a, ca), a the alpha sample at its own depth Ba and ca the binary32
+ *       nearest to 1 / ((1 << Ba) - 1), the same way; 1.0 without an alpha image.
+ *     PQ (HEIFGPU_PIX_HDR_RGB16PQ / RGBA16PQ): codes at depth P in {10, 12, 16}, maxp =
+ *       (1 << P) - 1, through a table E of 641 u32 entries on the tone transform's floating
+ *       index extended to 2^24 (node k at Y_k = k for k < 64, else (32 + ((k - 32) & 31)) <<
+ *       ((k - 32) >> 5)): E[k] = rhu(256 maxp N(min(sdr_white Y_k / U, 10000) / 10000)), N the
+ *       ST 2084 inverse EOTF, sdr_white in cd/m2 (<= 0: 203).  v = E[H'] for H' < 64, else
+ *       with e = bitlength(H') - 6, idx = 32 e + (H' >> e), frac = H' & ((1 << e) - 1):
+ *       v = (E[idx] ((1 << e) - frac) + E[idx + 1] frac + (1 << (e - 1))) >> e; code = (v + 128) >> 8.
+ *       Alpha: the 16-bit rule of heifgpu_render_batch at depth P (a << (P - Ba) or
+ *       a >> (Ba - P); maxp without an alpha image).
+ * numpy reproduces this bit for bit (tests/gain_ref.py); kernels/gain_xform.hpp is its one
+ * statement in code, shared by the kernel and heifgpu_gain_apply. */
+enum { HEIFGPU_GAIN_NONE = 0, HEIFGPU_GAIN_APPLE = 1, HEIFGPU_GAIN_ISO = 2 };
+enum { HEIFGPU_CS_BT2020 = 2 };  /* a destination of heifgpu_gain_transform_make only */
+enum { HEIFGPU_GAIN_LINEAR = 0, HEIFGPU_GAIN_PQ = 1 };
+enum { HEIFGPU_PIX_HDR_RGB16F = 4, HEIFGPU_PIX_HDR_RGBA16F = 5, HEIFGPU_PIX_HDR_RGB16PQ = 6, HEIFGPU_PIX_HDR_RGBA16PQ = 7 };
+#define HEIFGPU_GAIN_T_ENTRIES 4097   /* maxg + 2 at 12 bits */
+#define HEIFGPU_GAIN_E_ENTRIES 641
+typedef struct {
+    uint32_t kind;                    /* HEIFGPU_GAIN_* */
+    uint32_t gain_item_id;            /* the gain-map image item, 0 without one */
+    int32_t status;                   /* HEIFGPU_OK, or what a transform answers (Apple: given a headroom) */
+    uint32_t version, minimum_version, writer_version;   /* ISO; zeros otherwise */
+    uint32_t multichannel, use_base_colour_space;
+    double base_headroom, alternate_headroom;            /* log2 */
+    double gain_min, gain_max, gamma, base_offset, alternate_offset;  /* of channel 0 */
+} heifgpu_gain_info;
+typedef struct {
+    uint32_t bits;                    /* B, the base image's depth */
+    uint32_t gain_bits;               /* Bg */
+    uint32_t dst;                     /* HEIFGPU_CS_*, BT.2020 included */
+    uint32_t encoding;                /* HEIFGPU_GAIN_LINEAR / _PQ: the formats it serves */
+    uint32_t pq_bits;                 /* P; 0 for the linear encoding */
+    uint32_t kind;                    /* HEIFGPU_GAIN_*: the rule T was filled by (informative) */
+    int32_t m[9];
+    int32_t k_b, k_a;
+    double weight, headroom, sdr_white;   /* w, hr (Apple) and sdr_white as used (informative) */
+    uint16_t in_lut[3][4096];         /* the first 1 << B entries of each are used */
+    uint32_t T[HEIFGPU_GAIN_T_ENTRIES + 1];  /* maxg + 2 used */
+    uint32_t E[HEIFGPU_GAIN_E_ENTRIES + 1];  /* 641 used (PQ) */
+} heifgpu_gain_transform;
+/* host only, always HEIFGPU_OK for a parsed image */
+int heifgpu_image_get_gain(const heifgpu_image *img, heifgpu_gain_info *out);
+/* host only: the transform of `base` with its gain map `gain` (the parsed gain-map image:
+ * it gives Bg) to dst at depth bits (the base's, 8..12).  headroom: the Apple rule's, ignored
+ * by the ISO rule; display_headroom: a linear ratio, <= 0 for full; sdr_white in cd/m2, <= 0
+ * for 203 (PQ only); pq_bits 10, 12 or 16 (PQ only). */
+int heifgpu_gain_transform_make(const heifgpu_image *base, const heifgpu_image *gain, uint32_t dst, uint32_t bits,
+                                uint32_t encoding, uint32_t pq_bits, double headroom, double display_headroom,
+                                double sdr_white, heifgpu_gain_transform *out);
+/* host only: the per-pixel formula over n R G B triples of codes 0..maxv with their Q8 gain
+ * codes g_q8 (0 .. 256 maxg), binary16 bits or PQ codes out; a larger code, or a transform a
+ * render would refuse, is HEIFGPU_E_INVALID.  out may be rgb_in. */
+int heifgpu_gain_apply(const heifgpu_gain_transform *t, const uint16_t *rgb_in, const uint32_t *g_q8, size_t n,
+                       uint16_t *out);
+/* host only: the Q8 gain code of every decoded base position of a W x H base from a Wg x Hg
+ * map of depth gain_bits (uint8 for 8, else uint16; pitch bytes a row), W * H uint32 out. */
+int heifgpu_gain_sample(const void *gain, uint32_t wg, uint32_t hg, int32_t pitch, uint32_t gain_bits, uint32_t w,
+                        uint32_t h, uint32_t *g_q8);
+/* heifgpu_render_batch for HDR: base pictures in[i] of imgs[i] and the decoded luma planes
+ * gain_in[i] of their gain-map images gain_imgs[i], through the base's display map, as
+ * format HEIFGPU_PIX_HDR_* with ONE launch.  xf[i] is never NULL.  Alpha as in
+ * heifgpu_render_batch (the RGBA formats; its samples may be of another width than the
+ * base's).  The base images' samples must all be 1 byte or all 2 bytes wide; a gain plane may
+ * be of either width beside any base.  All checks run before anything is launched.
+ * The map is sampled at decoded base positions, so its own display map must say the same as
+ * the base's or nothing.  HEIFGPU_E_UNSUPPORTED: a gain image whose own display map is neither
+ * the identity nor the base's (the base's exactly, or the base's m over the whole of the map's
+ * own picture: the same irot / imir at the map's size, as Apple's files carry them), an image
+ * set to bilinear chroma upsampling, a side above 65535.  HEIFGPU_E_INVALID:
+ * xf[i] NULL, bits or gain_bits that disagree with the images, an encoding or pq_bits that
+ * disagree with the format, a T or E entry above 2^24, an offset above 16 * 65535, a pitch
+ * too small.  A window-decoded image is not known to this layer: the caller must have decoded
+ * both images whole (DecodeContext.render_hdr refuses otherwise).  The tables live in the
+ * context's content cache, as those of the colour-managed render do. */
+int heifgpu_render_batch_gain(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                              const heifgpu_planes *in,
+                              const heifgpu_image *const *gain_imgs, const heifgpu_planes *gain_in,
+                              const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in,
+                              uint32_t format, const heifgpu_gain_transform *const *xf,
+                              const heifgpu_surface *out, void *stream);
+
 /* ---- window decode: decode only the pictures a window reads ----------------
  * (added within ABI 6: new entry points only; heifgpu_batch_opts keeps its layout.)
  * A render of a window of the displayed picture (heifgpu_scale's x, y, width,

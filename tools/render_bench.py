@@ -81,8 +81,16 @@ bilinear, alternated in one process.  bilinear / replicate is reported, nothing 
 gated.  With HEIFGPU_LIBRARY naming the parent commit's build (no setter) the replicate
 columns alone are measured: the figures to hold this build's replicate launch against.
 
+--gain measures the gain-map HDR render (heifgpu_render_batch_gain): 8-bit
+pictures of halfmoonbay's geometry with 2016 x 1512 8-bit gain maps (every image its own
+planes), Display P3 to sRGB, Apple rule at headroom 4, against the colour-managed render of
+the same planes that writes as many bytes, alternated in one process in each of the --runs runs:
+  render_rgba16 / render_hdr_rgba16f   heifgpu_render_batch_color RGBA16 / the HDR render, linear half-float
+  render_rgb16 / render_hdr_rgb16pq    the same in RGB16 / the HDR render, PQ at 10 bits
+hdr / managed is reported per pair with the spreads (max - min over runs); nothing is gated.
+
 usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json]
-                                    [--scaled | --tensor | --color | --filter | --tone | --chroma bilinear]
+                                    [--scaled | --tensor | --color | --filter | --tone | --chroma bilinear | --gain]
 """
 import argparse
 import ctypes
@@ -729,6 +737,85 @@ def chroma_main(args):
         pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
 
 
+def gain_main(args):
+    n = args.images
+    dev = torch.device("cuda", 0)
+    ctx = H.DecodeContext(0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    golden = forced_rotation((ROOT / "tests" / "golden" / "halfmoonbay.heic").read_bytes(), 0)
+    g = torch.Generator(device=dev).manual_seed(1)
+    img = H.HeifImage.parse(golden)
+    gimg = H.HeifImage.parse(golden, img.gain_map.item_id)
+    gi = gimg.info
+    assert (img.info.width, img.info.height, gi.width, gi.height) == (W, HGT, W // 2, HGT // 2)
+
+    def plane(h, w):
+        return torch.randint(0, 256, (h, w), generator=g, device=dev, dtype=torch.int32).to(torch.uint8)
+
+    keep = [[plane(HGT, W), plane(HGT // 2, W // 2), plane(HGT // 2, W // 2), plane(gi.height, gi.width)] for _ in range(n)]
+    planes, gplanes = (_lib.Planes * n)(), (_lib.Planes * n)()
+    for i, (y, cb, cr, gm) in enumerate(keep):
+        for c, t in enumerate((y, cb, cr)):
+            planes[i].plane[c], planes[i].pitch[c] = t.data_ptr(), t.stride(0)
+        gplanes[i].plane[0], gplanes[i].pitch[0] = gm.data_ptr(), gm.stride(0)
+    # one 8-byte-per-pixel surface per image; the 6-byte formats write into the same memory
+    outs = [torch.empty((HGT, W, 4), dtype=torch.int16, device=dev) for _ in range(n)]
+    surf = {ch: (_lib.Surface * n)() for ch in (3, 4)}
+    for ch in (3, 4):
+        for i, t in enumerate(outs):
+            surf[ch][i].pixels, surf[ch][i].pitch = t.data_ptr(), W * ch * 2
+    imgs = (ctypes.c_void_p * n)(*[img._h.value] * n)
+    gimgs = (ctypes.c_void_p * n)(*[gimg._h.value] * n)
+    ct = img.color_transform("srgb", 8)
+    assert not ct.identity
+    xf = (ctypes.c_void_p * n)(*[ctypes.addressof(ct)] * n)
+    gts = {enc: img.gain_transform(gimg, "srgb", enc, 10, headroom=4.0) for enc in ("linear", "pq")}
+    gxf = {enc: (ctypes.c_void_p * n)(*[ctypes.addressof(t)] * n) for enc, t in gts.items()}
+
+    def managed(fmt, ch):
+        def run():
+            _lib.check(_lib.lib.heifgpu_render_batch_color(ctx._h, imgs, n, planes, None, None, fmt, xf, surf[ch], stream))
+        return run
+
+    def hdr(fmt, ch, enc):
+        def run():
+            _lib.check(_lib.lib.heifgpu_render_batch_gain(ctx._h, imgs, n, planes, gimgs, gplanes, None, None, fmt, gxf[enc],
+                                                          surf[ch], stream))
+        return run
+
+    px = n * W * HGT
+    variants = [("rgba", "render_rgba16", managed(_lib.PIX_RGBA16, 4), px * 9.5),
+                ("rgba", "render_hdr_rgba16f", hdr(_lib.PIX_HDR_RGBA16F, 4, "linear"), px * 9.75),
+                ("rgb", "render_rgb16", managed(_lib.PIX_RGB16, 3), px * 7.5),
+                ("rgb", "render_hdr_rgb16pq", hdr(_lib.PIX_HDR_RGB16PQ, 3, "pq"), px * 7.75)]
+    result = {"images": n, "width": W, "height": HGT, "gain_width": gi.width, "gain_height": gi.height, "reps": args.reps,
+              "runs": args.runs, "device": torch.cuda.get_device_name(0), "hbm_peak_GBps": HBM_PEAK_GBS,
+              "library": _lib.LIB_PATH.name, "transform": "Display P3 profile (halfmoonbay) -> sRGB; Apple rule, headroom 4",
+              "cases": {}}
+    for *_, fn, _ in variants:  # warm-up (and the tables' one upload)
+        fn()
+    torch.cuda.synchronize()
+    ms = {kind: [] for _, kind, _, _ in variants}
+    for _ in range(args.runs):
+        for _, kind, fn, _ in variants:
+            ms[kind].append(timed(fn, args.reps))
+    for name, kind, _, nbytes in variants:
+        r = summary(ms[kind], nbytes)
+        r["spread_ms"] = round(r["ms_max"] - r["ms_min"], 4)
+        result["cases"].setdefault(name, {})[kind] = r
+    for name, r in result["cases"].items():
+        base, new = [k for k in r if not k.startswith("render_hdr")][0], [k for k in r if k.startswith("render_hdr")][0]
+        r["hdr_over_managed"] = round(r[new]["ms_per_batch"] / r[base]["ms_per_batch"], 4)
+        r["hdr_minus_managed_ms"] = round(r[new]["ms_per_batch"] - r[base]["ms_per_batch"], 4)
+        print(f"{name}: " + ", ".join(f"{k} {r[k]['ms_per_batch']:.3f} ms ({r[k]['GBps']:.0f} GB/s, spread "
+                                      f"{r[k]['spread_ms']:.3f})" for k in (base, new)) +
+              f", ratio {r['hdr_over_managed']:.3f}", flush=True)
+    print(json.dumps(result))
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=128)
@@ -742,7 +829,10 @@ def main():
     ap.add_argument("--tone", action="store_true", help="measure the tone stage of the HDR render (see above)")
     ap.add_argument("--chroma", choices=("replicate", "bilinear"), default=None,
                     help="measure the render, scaled and filtered calls with chroma upsampling set, beside replicate")
+    ap.add_argument("--gain", action="store_true", help="measure the gain-map HDR render (see above)")
     args = ap.parse_args()
+    if args.gain:
+        return gain_main(args)
     if args.chroma:
         return chroma_main(args)
     if args.filter:
