@@ -679,10 +679,10 @@ __device__ __attribute__((always_inline)) inline void predict_pair(IntraScratch 
 // carries no per-format arithmetic)
 // LDS of k_intra's streaming mode beyond the windows: the transform tables
 // (workgroup) and per wave the transform tiles (transform_tb, xform.hpp)
-// (the transposed matrices s_mt; per wave the d tile 32 x 34, the g tile 32 x 32, the extent pair)
+// (the transposed matrices s_mt; per wave the d tile 32 x 34, the g tile 32 x 32)
 constexpr size_t kXfTablesBytes = sizeof(XfTab);
 constexpr size_t kXfDBytes = 32 * kXfDStride32 * sizeof(int16_t), kXfGBytes = 32 * 32 * sizeof(int16_t);
-constexpr size_t kXfWaveBytes = kXfDBytes + kXfGBytes + 16;
+constexpr size_t kXfWaveBytes = kXfDBytes + kXfGBytes;
 static_assert(kXfTablesBytes % 16 == 0 && kXfWaveBytes % 16 == 0, "transform scratch alignment");
 constexpr int kIntraPlanes = 0, kIntraStream = 1;
 
@@ -763,7 +763,7 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
         unsigned char *tab = smem + 64 + (size_t)nw * lay.bytes;
         unsigned char *xw = tab + kXfTablesBytes + (size_t)wave * kXfWaveBytes;
         X = XfScratch{reinterpret_cast<int16_t *>(xw), reinterpret_cast<int16_t *>(xw + kXfDBytes),
-                      reinterpret_cast<int32_t *>(xw + kXfDBytes + kXfGBytes), reinterpret_cast<const XfTab *>(tab)};
+                      reinterpret_cast<const XfTab *>(tab)};
         xf_tables(reinterpret_cast<XfTab *>(tab), lane);
     }
     IntraScratch *S = reinterpret_cast<IntraScratch *>(F.blk);

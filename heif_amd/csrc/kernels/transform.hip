@@ -44,7 +44,6 @@ __global__ void __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_e
     // VGPRs 34 -> 70 and measured 14.6 -> 18.6 ms.)
     HG_BLOCK_SHARED __attribute__((aligned(16))) int16_t dtile[kWaves][32 * kXfDStride32];
     HG_BLOCK_SHARED __attribute__((aligned(16))) int16_t gtile[kWaves][32 * 32];
-    HG_BLOCK_SHARED int32_t extent[kWaves][2];  // last nonzero row / column of d
     HG_BLOCK_SHARED XfTab s_tab;
     // the workgroup's threads copy the tables (the host emulation runs one thread per wave)
 #if defined(HG_HOST_EMU)
@@ -80,9 +79,10 @@ __global__ void __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_e
 
     // Pass A: 4x4 TBs, four at a time, 16 lanes each (sub-tile q of d / g).
     // A 4x4 TB has 16 outputs; run one per wave it left 48 lanes idle and paid
-    // a full round of tile zeroing, extent atomics and wave syncs per TB.
+    // a full round of tile zeroing and wave syncs per TB.
     // Every phase loops over the 64 virtual lanes (one iteration on the GPU;
     // the host emulation runs one lane per wave).
+#if !defined(HG_XABL_PASS_A)  // measurement builds only (wrong pixels): no pass A
     {
         const uint32_t mine = ntu > (uint32_t)wave ? (ntu - (uint32_t)wave + kWaves - 1) / kWaves : 0;
         // the wave's j-th record: a coded 4x4 TB inside its plane?
@@ -116,12 +116,11 @@ __global__ void __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_e
                     pos = r.pos(l16, 2);
                 }
                 if (!(tu.flags & TU_BYPASS)) {
-                    const int qp = tu.qp, bd_shift = bd - 3;
-                    const int ls = c_level_scale[qp % 6] << (qp / 6);
+                    const int bd_shift = bd - 3, ls = xf_level_scale(tu.qp);
                     // pass B's use_m (scaling && !(ts && n > 4)) is just `scaling` at 4x4
                     const int m =
                         scaling ? a.sf[sp.sf_off + sf_size_offset(0) + (uint32_t)cidx * 16u + (uint32_t)pos] : 16;
-                    dv = clip16(((int64_t)dv * m * ls + ((int64_t)1 << (bd_shift - 1))) >> bd_shift);
+                    dv = xf_scale64(dv, m, ls, bd_shift);
                 }
                 d[(vl & 48) + ((pos & 3) << 2) + (pos >> 2)] = (int16_t)dv;  // transposed: dT[x][y]
             }
@@ -202,11 +201,16 @@ __global__ void __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_e
         }
 #endif
     }
+#endif
 
     // Pass B: every larger TB, one per wave
     auto pass_b = [&](const TuRec &tu) {
+#if defined(HG_XABL_TB) && !defined(HG_HOST_EMU)  // measurement builds only: the walk alone, the TB's work dropped
+        asm volatile("" ::"s"(tu.coef), "s"((uint32_t)tu.ncoef), "s"((uint32_t)tu.x), "s"((uint32_t)tu.qp));
+        return;
+#endif
         const int cidx = tu.flags & TU_CIDX_MASK;
-        transform_tb(tu, coefs, sp, a.sf, XfScratch{d, g, extent[wave], &s_tab},
+        transform_tb(tu, coefs, sp, a.sf, XfScratch{d, g, &s_tab},
                      res_plane[cidx] + (size_t)tu.y * pitch[cidx] + tu.x, pitch[cidx], lane);
     };
     auto wanted = [&](const TuRec &tu) {

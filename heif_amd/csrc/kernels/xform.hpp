@@ -6,6 +6,7 @@
 #pragma once
 #include "kernels.hpp"
 #include "tables.hpp"
+#include "xform_rec.hpp"
 
 namespace hg {
 namespace {
@@ -38,7 +39,6 @@ constexpr TransMatrix make_matrix() {
 }
 __constant__ TransMatrix c_tm = make_matrix();
 __constant__ int8_t c_dst[4][4] = {{29, 55, 74, 84}, {74, 74, 0, -74}, {84, -29, -74, 55}, {55, -84, 74, -29}};
-__constant__ int16_t c_level_scale[6] = {40, 45, 51, 57, 64, 72};
 
 #define xf_sync() HG_WAVE_SYNC()
 
@@ -148,10 +148,9 @@ struct alignas(16) XfTab {
 static_assert(sizeof(XfTab) % 16 == 0 && (sizeof(int16_t) * kMtElems) % 16 == 0, "XfTab layout");
 
 // a wave's transform scratch: d (int16, 32 x 34: the transposed layout's
-// padding) and g (32x32) tiles, the extent pair, and the workgroup's tables
+// padding) and g (32x32) tiles, and the workgroup's tables
 struct XfScratch {
     int16_t *d, *g;
-    int32_t *extent;
     const XfTab *tab;
 };
 
@@ -293,10 +292,52 @@ __device__ __forceinline__ int dot2_i16(uint32_t a, uint32_t b, int s) {
 #endif
 }
 
+// eight residual samples (16 bytes) in one store, to global memory or to LDS
+struct alignas(16) XfRow8 {
+    uint32_t w[4];
+};
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ void xf_store8(int16_t HG_GAS *p, const XfRow8 &v) {
+    *reinterpret_cast<XfRow8 HG_GAS *>(p) = v;
+}
+#endif
+__device__ __forceinline__ void xf_store8(int16_t *p, const XfRow8 &v) { *reinterpret_cast<XfRow8 *>(p) = v; }
+
+// the largest v (0 .. 2^bits - 1) among the wave's lanes, in every lane: a ballot
+// per bit from the top, over the lanes that hold the bits found so far
+__device__ __forceinline__ int xf_wave_max(int v, int bits) {
+#if defined(HG_HOST_EMU)
+    (void)bits;
+    return v;  // (one lane)
+#else
+    uint64_t alive = ~0ull;
+    int m = 0;
+    for (int b = bits - 1; b >= 0; --b) {
+        const uint64_t t = __ballot((v >> b) & 1) & alive;
+        if (t) {
+            m |= 1 << b;
+            alive = t;
+        }
+    }
+    return m;
+#endif
+}
+
+#if !defined(HG_HOST_EMU) && !defined(HG_XF_NO_MFMA)
+constexpr bool kXfMfma = true;
+#else
+constexpr bool kXfMfma = false;
+#endif
+
 // Residual of coded TB `tu` into dst (row pitch `pitch` samples) by one wave.
 // The caller has checked that the TB lies inside its plane.
 // dst: the residual plane (global) or, in k_intra's streaming mode, X.d itself
 // (pitch n: the last pass no longer reads d)
+// What the stages skip they learn from the records, not from the tile (xform_rec.hpp):
+// a TB of one record that codes sample (0, 0) alone is a fill and never touches
+// the tile, and the dot products' extents are the records' sub-block coordinates
+// (the tile's last nonzero row and column through two LDS atomics and a read back
+// per TB before; the MFMA stages take no extents at all).
 template <bool Coherent, class DstPtr>
 __device__ __forceinline__ void transform_tb(const TuRec &tu, const CoefSrc<Coherent> &coefs, const SeqParams &sp,
                                              const uint8_t *sf, const XfScratch &X, DstPtr dst, int pitch, int lane) {
@@ -307,52 +348,76 @@ __device__ __forceinline__ void transform_tb(const TuRec &tu, const CoefSrc<Cohe
     if (log2n < 2 || log2n > 5 || cidx > 2) return;
     const int bd = cidx ? sp.bit_depth_c : sp.bit_depth_y;
     const bool bypass = (tu.flags & TU_BYPASS) != 0, ts = (tu.flags & TU_TSKIP) != 0;
-    // 1. zero the tile, scatter d[y][x] (scaled unless bypass; transposed for the dot-product stages)
+    const bool pcm = (tu.flags & TU_PCM) != 0, dst_tr = (tu.flags & TU_DST) != 0;
     const bool dots = !bypass && !ts;
     const int sn = mt_stride(log2n);
-    for (int i = lane; i < (dots ? n * sn : n * n) / 2; i += kWave) reinterpret_cast<int32_t *>(d)[i] = 0;
-    if (lane == 0) X.extent[0] = X.extent[1] = 0;
-    xf_sync();
-    const int qp = tu.qp;
-    const int bd_shift = bd + log2n - 5;
-    const int64_t rnd = (int64_t)1 << (bd_shift - 1);
-    const int ls = c_level_scale[qp % 6] << (qp / 6);
+    const int bd_shift = bd + log2n - 5, bd2 = 20 - bd;
+    const int ls = xf_level_scale(tu.qp);
     const bool use_m = scaling && !(ts && n > 4);
+    // each lane's first record (16 lanes per record; the lanes past the last one read it again)
+    const int nrec = pcm ? 0 : (int)(tu.ncoef >> 2);
+    SbRec r0{0, 0, 0, 0};
+    if (nrec > 0) r0 = load_rec(coefs, tu.coef + 4u * (uint32_t)min(lane >> 4, nrec - 1));
+    if (nrec == 1 && dots && !dst_tr && !use_m && HG_UNI((int)xf_dc_record(r0.w0, r0.w3))) {
+        // DC only: one level (hidden sign and escape as anywhere), both stages constant
+        // (transMatrix[0][*] = 64), then a fill, in 16-byte stores where dst allows them
+        const int v = r0.level(0, 0, coefs);
+        const int dv = xf_scale64(v, 16, ls, bd_shift);
+        const int g0 = xf_clip16((64 * dv + 64) >> 7);
+        const int16_t r = (int16_t)xf_clip16((64 * g0 + (1 << (bd2 - 1))) >> bd2);
+        if (log2n >= 3 && (((uintptr_t)dst | (uintptr_t)(2 * pitch)) & 15u) == 0) {
+            const uint32_t rr = (uint32_t)(uint16_t)r * 0x10001u;
+            const XfRow8 row{{rr, rr, rr, rr}};
+            for (int i = lane; i < (n * n) >> 3; i += kWave)
+                xf_store8(dst + (i >> (log2n - 3)) * pitch + ((i & ((n >> 3) - 1)) << 3), row);
+        } else {
+            for (int i = lane; i < n * n; i += kWave) dst[(i >> log2n) * pitch + (i & (n - 1))] = r;
+        }
+        xf_sync();
+        return;
+    }
+    // 1. zero the tile, scatter d[y][x] (scaled unless bypass; transposed for the dot-product stages)
+    for (int i = lane; i < (dots ? n * sn : n * n) / 2; i += kWave) reinterpret_cast<int32_t *>(d)[i] = 0;
+    xf_sync();
     const uint8_t *mtab = sf + sp.sf_off + sf_size_offset(log2n - 2) + (uint32_t)cidx * (uint32_t)(n * n);
-    int my_row = 0, my_col = 0;
     auto put = [&](int pos, int v) {
         pos &= n * n - 1;
         int dv;
         if (bypass) {
             dv = v;
         } else {
-            const int m = use_m ? mtab[pos] : 16;
-            dv = clip16(((int64_t)v * m * ls + rnd) >> bd_shift);
+            dv = xf_scale64(v, use_m ? mtab[pos] : 16, ls, bd_shift);
         }
         d[dots ? (pos & (n - 1)) * sn + (pos >> log2n) : pos] = (int16_t)dv;
-        my_row = max(my_row, pos >> log2n);
-        my_col = max(my_col, pos & (n - 1));
     };
-    if (tu.flags & TU_PCM) {  // one word per sample
+    // the dot products' extents: the largest sub-block coordinates among the records
+    const bool ext = dots && (!kXfMfma || log2n < 4);
+    int xs_max = 0, ys_max = 0;
+    if (pcm) {  // one word per sample
         for (int k = lane; k < tu.ncoef; k += kWave) {
             const Coef c = coefs.word(tu.coef + (uint32_t)k);
             put((int)(c & 0xffffu), (int)(int16_t)(c >> 16));
         }
     } else {  // 16 lanes per sub-block record, a scan position each (no serial loop per lane)
-        const int nrec = (int)(tu.ncoef >> 2);
-        for (int q = lane; q < 16 * nrec; q += kWave) {
-            const SbRec r = load_rec(coefs, tu.coef + 4u * (uint32_t)(q >> 4));  // (16 lanes, one address)
+        SbRec r = r0;
+        for (int q = lane; q < 16 * nrec;) {
             const int nn = q & 15;
-            if (!((r.sig() >> nn) & 1u)) continue;
-            const int above = nn < 15 ? __builtin_popcountll(r.esc() >> (4 * nn + 4)) : 0;
-            put(r.pos(nn, log2n), r.level(nn, above, coefs));
+            if (ext) {
+                xs_max = max(xs_max, (int)(r.w3 & 7u));
+                ys_max = max(ys_max, (int)((r.w3 >> 3) & 7u));
+            }
+            if ((r.sig() >> nn) & 1u) {
+                const int above = nn < 15 ? __builtin_popcountll(r.esc() >> (4 * nn + 4)) : 0;
+                put(r.pos(nn, log2n), r.level(nn, above, coefs));
+            }
+            q += kWave;
+            if (q < 16 * nrec) r = load_rec(coefs, tu.coef + 4u * (uint32_t)(q >> 4));  // (16 lanes, one address)
         }
     }
-    if (my_row) atomicMax(&X.extent[0], my_row);
-    if (my_col) atomicMax(&X.extent[1], my_col);
     xf_sync();
-    const int rows = X.extent[0] + 1, cols = X.extent[1] + 1;  // d is zero beyond these
-    const int bd2 = 20 - bd;
+#if defined(HG_XABL_STAGES)  // measurement builds only (wrong pixels): no stage after the scatter
+    return;
+#endif
     if (bypass || ts) {
         // bypass: r = TransCoeffLevel; transform skip: r = (d << tsShift) then >> bdShift
         const int ts_shift = 5 + log2n;
@@ -361,15 +426,6 @@ __device__ __forceinline__ void transform_tb(const TuRec &tu, const CoefSrc<Cohe
             if (!bypass) r = (r * (1 << ts_shift) + (1 << (bd2 - 1))) >> bd2;
             dst[(i >> log2n) * pitch + (i & (n - 1))] = (int16_t)clip16(r);
         }
-        xf_sync();
-        return;
-    }
-    const bool dst_tr = (tu.flags & TU_DST) != 0;
-    if (!dst_tr && rows == 1 && cols == 1) {
-        // DC only: both stages are constant (transMatrix[0][*] = 64)
-        const int g0 = clip16(((int64_t)64 * d[0] + 64) >> 7);
-        const int16_t r = (int16_t)clip16(((int64_t)64 * g0 + (1 << (bd2 - 1))) >> bd2);
-        for (int i = lane; i < n * n; i += kWave) dst[(i >> log2n) * pitch + (i & (n - 1))] = r;
         xf_sync();
         return;
     }
@@ -383,10 +439,11 @@ __device__ __forceinline__ void transform_tb(const TuRec &tu, const CoefSrc<Cohe
         return;
     }
 #endif
-    // 2. e[y][x] = sum_{j < rows} M[j][y] dT[x][j] over the nonzero columns, rounded up to a
-    //    multiple of four (d is zero there, so g is too): the row pass's dots read whole quads
+    // 2. e[y][x] = sum_{j < rows4} M[j][y] dT[x][j] over the columns and rows of the sub-blocks
+    //    the records name (d is zero beyond them, so g is too): the row pass's dots read whole quads
     const int16_t *mt = mt_of(X.tab->mt, log2n, dst_tr);
-    const int rows4 = (rows + 3) & ~3, cols4 = (cols + 3) & ~3;
+    int rows4, cols4;
+    xf_extents(xf_wave_max(xs_max, 3), xf_wave_max(ys_max, 3), n, &rows4, &cols4);
     const int lc = cols4 > 4 ? 32 - __builtin_clz((unsigned)(cols4 - 1)) : 2;
     for (int o = lane; o < (n << lc); o += kWave) {
         const int y = o >> lc, x = o & ((1 << lc) - 1);
@@ -402,7 +459,7 @@ __device__ __forceinline__ void transform_tb(const TuRec &tu, const CoefSrc<Cohe
         g[y * n + x] = (int16_t)min(max((s + 64) >> 7, -32768), 32767);  // (|s| < 2^27: 32-bit)
     }
     xf_sync();
-    // 3. r[y][x] = sum_{j < cols} M[j][x] g[y][j]: (r + rnd) >> (20 - bitDepth)
+    // 3. r[y][x] = sum_{j < cols4} M[j][x] g[y][j]: (r + rnd) >> (20 - bitDepth)
     for (int o = lane; o < n * n; o += kWave) {
         const int y = o >> log2n, x = o & (n - 1);
         const uint32_t *pa = reinterpret_cast<const uint32_t *>(mt + x * sn);
