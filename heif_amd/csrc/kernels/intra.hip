@@ -16,10 +16,11 @@
 // the column left of it (kept from the previous CTU), the row above it
 // (2*ctb+1 samples incl. the corner and above-right, loaded once per CTU from
 // the picture after the progress wait) and the CTU's residuals (one coalesced
-// load per CTU).  Every TB then works on LDS only — neighbour gather,
-// substitution (three 64-bit ballots + a nearest-available lookup),
-// filtering, prediction and residual add run one sample per lane — and the
-// finished CTU is written to the picture once.
+// load per CTU).  Every TB then works on LDS only — neighbour gather with
+// the substitution (each lane reads the sample that stands at its search
+// position after 8.4.4.2.2, a closed form on the record's five availability
+// facts: intra_rec.hpp word D), filtering, prediction and residual add run
+// one sample per lane — and the finished CTU is written to the picture once.
 #include "kernels.hpp"
 #include "intra_rec.hpp"
 #include "xform.hpp"
@@ -104,23 +105,12 @@ int intra_waves(int log2ctb, int chroma, int bps, int max_rows) {
 #endif
 
 
-// 6.4.1 availability of a neighbouring luma location (lx, ly), relative to the
-// origin of the TB's CTU of luma size csl.  Everything in the CTU row above (up
-// to the above-right CTU, which the wavefront has finished) and in the CTU to
-// the left is decoded; the CTUs below-left and right are not; inside the CTU a
-// block is available iff it precedes the TB in z-scan order (MinTbAddrZs of
-// 6.5.2 at 4x4 granularity: the CTU's quadtrees are decoded in z-order, so a
-// 4x4 block is decoded before the TB iff its z-index is below the z-index zc
-// of the TB's first luma 4x4 block).
-// (r06 A/B: as one expression of bitwise ands / ors with the z-index always
-// formed, k_intra VALU +0.45 G for SALU -0.2 G, the step not better: the early
-// returns stay)
-__device__ __forceinline__ bool nb_avail(int zc, int lx, int ly, int csl) {
-    if (ly < 0) return true;
-    if (ly >= csl || lx >= csl) return false;
-    if (lx < 0) return true;
-    return tb_zidx(lx >> 2, ly >> 2) < zc;
-}
+// 6.4.1 availability of a TB's neighbours is decided where the wave loads the
+// records (tb_pack_d, intra_rec.hpp): everything in the CTU row above (up to the
+// above-right CTU, which the wavefront has finished) and in the CTU to the left
+// is decoded; the CTUs below-left and right are not; inside the CTU a block is
+// available iff it precedes the TB in z-scan order (MinTbAddrZs of 6.5.2 at 4x4
+// granularity).  Per group of neighbours that is one fact, not one per sample.
 
 // ref[k] of 8.4.4.2.6 read in place: the main-side neighbour for k >= 0, the
 // projected side-side neighbour for k < 0 (only reached when
@@ -154,17 +144,14 @@ struct Win {
     int cx0, cy0;  // CTB origin in component samples
 };
 
-// What a TB's prediction reads of its component's window, in coordinates
-// relative to the CTB's origin (the record's word A holds the TB's position
-// that way): the window, the part of the CTB inside the picture, whether the
-// picture has samples left of and above the CTB, and the TB's residual.
+// What a TB's prediction reads of its component's window: the CTB's samples
+// (the TB's own position in them is in the record's word D), where the column
+// left of the CTB and the row above it stand behind them, and the TB's residual.
 template <typename Pel>
 struct TbWin {
-    Pel *cur, *left, *above;
+    Pel *cur;
+    int dl, da;          // the left column and the row above, in samples from cur
     int lsx;             // log2 of the window's pitch (the component CTB's width)
-    int vw, vh;          // columns, rows from the CTB's origin to the picture's edge (component samples)
-    int minx, miny;      // -1 where the picture has a column left of / a row above the CTB, else 0
-    int csl;             // CTB size in luma samples
     const int16_t *rt;   // the TB's first residual: in the component's residual plane (k_transform), or in
                          // streaming mode the TB's residual tile in LDS
     int rp;              // residual pitch (the plane width; streaming mode: the TB width)
@@ -191,11 +178,6 @@ struct TbWin {
         }
     }
 #endif
-    // a decoded neighbour (lx, ly); only called for available samples, which lie
-    // in the row above, the column to the left or the current CTU
-    __device__ __forceinline__ const Pel *at(int lx, int ly) const {
-        return ly < 0 ? above + lx + 1 : (lx < 0 ? left + ly : cur + (ly << lsx) + lx);
-    }
 };
 
 // One picture's CTU windows, from which a component's Win is formed where it
@@ -251,7 +233,8 @@ struct Frame {
 // (Cr: Cb's + Frame::b1): constants of a CTB row, so a TB's window is a select
 // on cIdx and an add.
 struct WinOffs {
-    uint32_t cur[2], left[2], above[2];
+    uint32_t cur[2];
+    int dl[2], da[2];  // from a window's samples to its left column and its row above, in samples
 };
 template <typename Pel, int CF>
 __device__ __forceinline__ WinOffs win_offs(const Frame<Pel, CF> &F) {
@@ -259,11 +242,11 @@ __device__ __forceinline__ WinOffs win_offs(const Frame<Pel, CF> &F) {
     const uint32_t bps = sizeof(Pel);
     const int l2 = F.log2ctb, lx = l2 - chroma_sx(CF), ly = l2 - chroma_sy(CF);
     o.cur[0] = F.kS0;
-    o.left[0] = o.cur[0] + F.al16(bps << (2 * l2));
-    o.above[0] = o.left[0] + F.al16(bps << l2);
+    o.dl[0] = (int)(F.al16(bps << (2 * l2)) / bps);
+    o.da[0] = o.dl[0] + (int)(F.al16(bps << l2) / bps);
     o.cur[1] = F.kS0 + F.b0;
-    o.left[1] = o.cur[1] + F.al16(bps << (lx + ly));
-    o.above[1] = o.left[1] + F.al16(bps << ly);
+    o.dl[1] = (int)(F.al16(bps << (lx + ly)) / bps);
+    o.da[1] = o.dl[1] + (int)(F.al16(bps << ly) / bps);
     return o;
 }
 
@@ -293,19 +276,29 @@ __device__ __forceinline__ int group_sum(int v, int m) {
 }
 #endif
 
-// One TB from its record's words A and B (intra_rec.hpp) and its component's window.
+// The sample that stands at search position s of a TB's neighbours after the
+// substitution of 8.4.4.2.2, read from the window: the lane's own source
+// position by the closed form on the record's facts (no ballot and no cross-lane
+// read), then one LDS read.  Only called where something is available.
+template <typename Pel>
+__device__ __forceinline__ int gather_at(const TbWin<Pel> &w, const Pel *cur, const TbSrcAddr &sa, int s, int n,
+                                         uint32_t wd) {
+    const int e = tb_src_at(sa, tb_subst_src(s, n, wd));
+#if defined(HG_HOST_EMU)
+    w.check_blk(cur + e, sizeof(Pel));
+#endif
+    return (int)cur[e];
+}
+
+// One TB from its record's words A, B and D (intra_rec.hpp) and its component's window.
 template <typename Pel, int CF>
 __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L, uint32_t wa, uint32_t wb,
-                                                                 const TbWin<Pel> &w, int bd, bool strong, int lane) {
-    constexpr int chroma = CF;
+                                                                 uint32_t wd, const TbWin<Pel> &w, int bd,
+                                                                 bool strong, int lane) {
     const int log2n = tba_log2(wa), n = 1 << log2n, mode = tba_mode(wa), cidx = tba_cidx(wa);
     const int x0 = tba_lx(wa), y0 = tba_ly(wa);  // relative to the CTB's origin
-    const int zc = tbb_zc(wb);
+    const int off = tbd_off(wd);                 // the TB's first sample in the window
     const bool filt = (wa & TBA_FILT) != 0;
-    // component → luma coordinates (6.4.1 takes luma locations; a neighbour's may be -1, so a
-    // product, not a shift of a negative value)
-    const int subx = cidx ? chroma_sx(chroma) : 0, suby = cidx ? chroma_sy(chroma) : 0;
-    const int csl = w.csl;
     const int ns = 4 * n + 1;
     const bool cbf = (wa & TBA_CBF) != 0;
     // residual of a 4x4 / 8x8 TB (one sample per lane): loaded now, used after
@@ -315,121 +308,52 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
     const int16_t *rt = w.rt;
 #if defined(HG_HOST_EMU)
     if (cbf) w.check_res(rt, (size_t)(n - 1) * w.rp + n);
-    w.check_blk(w.cur + ((y0 << w.lsx) + x0), ((size_t)((n - 1) << w.lsx) + n) * sizeof(Pel));
+    w.check_blk(w.cur + off, ((size_t)((n - 1) << w.lsx) + n) * sizeof(Pel));
 #endif
     const int r0 = (cbf && n <= 8 && lane < n * n) ? rt[(lane >> log2n) * w.rp + (lane & (n - 1))] : 0;
 #if defined(HG_IABL_TB)  // measurement builds only (wrong pixels): the TB's work dropped
     if (r0 != 12345) return;
 #endif
-    // 1. gather neighbours in search order (8.4.4.2.2): s < 2n left column bottom-up,
-    //    s == 2n corner, s > 2n top row left-to-right
+    // 1. + 2. the neighbours in search order with the substitution (8.4.4.2.2): s < 2n left
+    //    column bottom-up, s == 2n corner, s > 2n top row left-to-right.  The record's word D says
+    //    which groups are available; every position reads the sample that stands there afterwards.
+    const TbSrcAddr sa = tb_src_addr(x0, y0, n, w.lsx, w.dl, w.da);
+    const bool none = tb_subst_src(0, n, wd) < 0;  // nothing available (uniform): 1 << (bitDepth - 1)
+    auto put = [&](int s, int v) {
+        int16_t *dp = s < 2 * n ? L->left + (2 * n - s) : L->top + (s - 2 * n);  // (a select, not two exec regions)
+        *dp = (int16_t)v;
+        if (s == 2 * n) L->left[0] = (int16_t)v;
+    };
 #if defined(HG_HOST_EMU)
-    {  // scalar equivalent of the ballot-based gather + substitution below
-        int sv[129];
-        bool sa[129];
-        bool any_av = false;
-        for (int s = 0; s < ns; ++s) {
-            int xn, yn;
-            if (s < 2 * n) {
-                xn = x0 - 1;
-                yn = y0 + 2 * n - 1 - s;
-            } else if (s == 2 * n) {
-                xn = x0 - 1;
-                yn = y0 - 1;
-            } else {
-                xn = x0 + s - 2 * n - 1;
-                yn = y0 - 1;
+    for (int s = 0; s < ns; ++s) {  // (one lane: every position in turn, the kernel's arithmetic)
+        const int sp = tb_subst_src(s, n, wd);
+        if (sp >= 0) {  // the source is the window's sample at the position of search index sp
+            int dx, dy;
+            tb_search_pos(sp, n, &dx, &dy);
+            const int xn = x0 + dx, yn = y0 + dy;
+            const int e = yn < 0 ? w.da + xn + 1 : (xn < 0 ? w.dl + yn : (yn << w.lsx) + xn);
+            if (e != tb_src_at(sa, sp)) {
+                fprintf(stderr, "k_intra: search position %d of a TB at (%d, %d) n %d read at %d, not %d\n", sp, x0,
+                        y0, n, tb_src_at(sa, sp), e);
+                abort();
             }
-            sa[s] = xn >= w.minx && yn >= w.miny && xn < w.vw && yn < w.vh && nb_avail(zc, xn * (1 << subx), yn * (1 << suby), csl);
-            if (sa[s]) w.check_blk(w.at(xn, yn), sizeof(Pel));
-            sv[s] = sa[s] ? (int)*w.at(xn, yn) : 0;
-            any_av |= sa[s];
         }
-        int first = -1;
-        for (int s = 0; s < ns && first < 0; ++s)
-            if (sa[s]) first = s;
-        int last = -1;
-        for (int s = 0; s < ns; ++s) {
-            int v;
-            if (!any_av) v = 1 << (bd - 1);
-            else if (sa[s]) v = sv[s], last = s;
-            else v = last >= 0 ? sv[last] : sv[first];
-            if (s < 2 * n) L->left[2 * n - s] = (int16_t)v;
-            else if (s == 2 * n) L->left[0] = L->top[0] = (int16_t)v;
-            else L->top[s - 2 * n] = (int16_t)v;
-        }
+        put(s, none ? 1 << (bd - 1) : gather_at(w, w.cur, sa, s, n, wd));
     }
 #elif defined(HG_IABL_GATHER)  // measurement builds only: no neighbour gather
 #else
     if (ns <= 64) {  // 4x4 and 8x8 TBs (most of them): one chunk of 4n + 1 <= 33 samples
-        const int s = lane;
-        // every step formed for all lanes with selects (the branchy form
-        // split the wave into three exec regions per step): the column left
-        // of the TB bottom-up, the corner, the row above left to right
-        const int xn = s <= 2 * n ? x0 - 1 : x0 + s - 2 * n - 1;
-        const int yn = s < 2 * n ? y0 + 2 * n - 1 - s : y0 - 1;
-        const bool av = s < ns && xn >= w.minx && yn >= w.miny && xn < w.vw && yn < w.vh &&
-                        nb_avail(zc, xn * (1 << subx), yn * (1 << suby), csl);
-        const Pel *src = w.at(xn, yn);
-        const int val = (int)*(av ? src : w.cur);  // (an unavailable lane reads the window's first sample)
-        const uint64_t msk = __ballot(av);
-        const uint64_t below = msk & ((1ull << lane) - 1ull);
-        const int sub = below ? 63 - __clzll(below) : __ffsll((unsigned long long)msk) - 1;
-        const int sv = __shfl(val, av ? lane : sub, 64);
-        const int v = msk ? sv : (1 << (bd - 1));
-        int16_t *dp = s < 2 * n ? L->left + (2 * n - s) : L->top + (s - 2 * n);
-        if (s < ns) *dp = (int16_t)v;
-        if (s == 2 * n) L->left[0] = (int16_t)v;
+        // (lanes past the last position read its source: every lane's address is a sample's)
+        const int v = none ? 1 << (bd - 1) : gather_at(w, w.cur, sa, min(lane, 4 * n), n, wd);
+        if (lane < ns) put(lane, v);
     } else {
-    // 16x16 (65 samples) needs two chunks, 32x32 (129) three
-    const int nch = ns <= 128 ? 2 : 3;
-    int val[3] = {0, 0, 0};
-    uint64_t msk[3] = {0, 0, 0};
-    for (int k = 0; k < nch; ++k) {
-        // (as the one-chunk path: positions and the source by selects)
-        const int s = lane + 64 * k;
-        const int xn = s <= 2 * n ? x0 - 1 : x0 + s - 2 * n - 1;
-        const int yn = s < 2 * n ? y0 + 2 * n - 1 - s : y0 - 1;
-        const bool av = s < ns && xn >= w.minx && yn >= w.miny && xn < w.vw && yn < w.vh &&
-                        nb_avail(zc, xn * (1 << subx), yn * (1 << suby), csl);
-        const Pel *src = w.at(xn, yn);
-        val[k] = av ? (int)*src : 0;
-        msk[k] = __ballot(av);
-    }
-    // 2. substitution: nearest available predecessor in search order, else the first available
-    const bool any = (msk[0] | msk[1] | msk[2]) != 0;
-    for (int k = 0; k < nch; ++k) {
-        const int s = lane + 64 * k;
-        int sc = k, sl = lane;  // source (chunk, lane) of this sample's value
-        if (any && !((msk[k] >> lane) & 1)) {
-            sc = -1;
-            uint64_t below = msk[k] & ((1ull << lane) - 1ull);
-            if (below) {
-                sc = k;
-                sl = 63 - __clzll(below);
-            } else {
-                for (int j = k - 1; j >= 0 && sc < 0; --j)
-                    if (msk[j]) {
-                        sc = j;
-                        sl = 63 - __clzll(msk[j]);
-                    }
-            }
-            if (sc < 0) {  // no predecessor: value of the first available sample
-                for (int j = 0; j < 3 && sc < 0; ++j)
-                    if (msk[j]) {
-                        sc = j;
-                        sl = __ffsll((unsigned long long)msk[j]) - 1;
-                    }
-            }
+        // 16x16 (65 samples) needs two chunks, 32x32 (129) three
+        const int nch = ns <= 128 ? 2 : 3;
+        for (int k = 0; k < nch; ++k) {
+            const int s = lane + 64 * k;
+            const int v = none ? 1 << (bd - 1) : gather_at(w, w.cur, sa, min(s, 4 * n), n, wd);
+            if (s < ns) put(s, v);
         }
-        // all lanes active for the cross-lane reads
-        const int v0 = __shfl(val[0], sl, 64), v1 = __shfl(val[1], sl, 64);
-        const int v2 = nch > 2 ? __shfl(val[2], sl, 64) : 0;
-        const int v = !any ? (1 << (bd - 1)) : (sc == 0 ? v0 : (sc == 1 ? v1 : v2));
-        int16_t *dp = s < 2 * n ? L->left + (2 * n - s) : L->top + (s - 2 * n);
-        if (s < ns) *dp = (int16_t)v;
-        if (s == 2 * n) L->left[0] = (int16_t)v;
-    }
     }
 #endif
     wave_sync();
@@ -514,7 +438,7 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
                 }
             }
         }
-        const int li = ((y0 + y) << w.lsx) + x0 + x;
+        const int li = off + (y << w.lsx) + x;
         if (pcm) pv = 0;  // the residual is the PCM sample itself
         if (cbf) pv += (n <= 8 && o == lane) ? r0 : rt[y * w.rp + x];
         pv = min(max(pv, 0), maxv);
@@ -545,81 +469,41 @@ __device__ __attribute__((always_inline)) inline void predict_tb(IntraScratch *L
 // left / top at + 33 * h.
 template <typename Pel>
 __device__ __attribute__((always_inline)) inline void predict_pair(IntraScratch *L, uint32_t wa, uint32_t wb,
-                                                                   const TbWin<Pel> &wc, uint32_t dwin, uint32_t dres,
-                                                                   int bd, int lane) {
+                                                                   uint32_t wd, const TbWin<Pel> &wc, uint32_t dwin,
+                                                                   uint32_t dres, int bd, int lane) {
     // lanes 0-31 predict Cb and 32-63 Cr: the pairing needs a full 64-lane wave
     static_assert(kWave == 64, "predict_pair splits a 64-lane wave into two halves");
     const int log2n = tba_log2(wa), n = 1 << log2n, mode = tba_mode(wa);
     const int x0 = tba_lx(wa), y0 = tba_ly(wa);  // relative to the CTB's origin
-    const int zc = tbb_zc(wb);
+    const int off = tbd_off(wd);                 // the TB's first sample in the window
     const int h = lane >> 5, sl = lane & 31;
     // wc is the Cb window; Cr's lies dwin samples behind it, its residual dres elements behind Cb's
     // (a per-lane offset: a lane-dependent reference into an array of windows would put it in scratch)
-    TbWin<Pel> w = wc;
-    const uint32_t dw = h ? dwin : 0u;
-    w.cur = wc.cur + dw;
-    w.left = wc.left + dw;
-    w.above = wc.above + dw;
+    const TbWin<Pel> &w = wc;
+    Pel *const cur = wc.cur + (h ? dwin : 0u);
     const int16_t *rt = wc.rt + (h ? dres : 0u);
     const bool cbf = (wa & (h ? TBA_CBF2 : TBA_CBF)) != 0;
     const bool pcm = (wa & (h ? TBA_PCM2 : TBA_PCM)) != 0;
-    const int csl = w.csl;
     const int ns = 4 * n + 1, nch = n == 8 ? 2 : 1;
     // residuals (sample sl and sl + 32 of this half), used after the neighbour phase
     int r0 = 0, r1 = 0;
     if (cbf && sl < n * n) r0 = rt[(sl >> log2n) * w.rp + (sl & (n - 1))];
     if (cbf && sl + 32 < n * n) r1 = rt[((sl + 32) >> log2n) * w.rp + ((sl + 32) & (n - 1))];
     int16_t *left = L->left + 33 * h, *top = L->top + 33 * h;
-    // 1. neighbours in search order (8.4.4.2.2), chunk k = search positions sl + 32 k
-    // (two named registers, not arrays: indexed by a runtime chunk they went to scratch)
-    int val0 = 0, val1 = 0;
-    uint32_t hm0 = 0, hm1 = 0;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (k >= nch) break;
-        const int s = sl + 32 * k;
-        // (positions and the source by selects, as predict_tb's one-chunk path)
-        const int xn = s <= 2 * n ? x0 - 1 : x0 + s - 2 * n - 1;
-        const int yn = s < 2 * n ? y0 + 2 * n - 1 - s : y0 - 1;
-        const bool av = s < ns && xn >= w.minx && yn >= w.miny && xn < w.vw && yn < w.vh &&
-                        nb_avail(zc, xn * 2, yn * 2, csl);
-        const Pel *srcp = w.at(xn, yn);
-        const int vk = av ? (int)*srcp : 0;
-        const uint32_t hk = (uint32_t)(__ballot(av) >> (32 * h));
-        if (k == 0) {
-            val0 = vk;
-            hm0 = hk;
-        } else {
-            val1 = vk;
-            hm1 = hk;
+    // 1. + 2. neighbours in search order with the substitution (8.4.4.2.2), as predict_tb: each half's
+    // lane sl reads the sample that stands at position sl; the 33rd of an 8x8 (position 32, the last
+    // above-right sample) is a second read, the same position in every lane
+    {
+        const TbSrcAddr sa = tb_src_addr(x0, y0, n, w.lsx, w.dl, w.da);
+        const bool none = tb_subst_src(0, n, wd) < 0;  // (uniform)
+        const int v = none ? 1 << (bd - 1) : gather_at(w, cur, sa, min(sl, 4 * n), n, wd);
+        int16_t *dp = sl < 2 * n ? left + (2 * n - sl) : top + (sl - 2 * n);
+        if (sl < ns) *dp = (int16_t)v;
+        if (sl == 2 * n) left[0] = (int16_t)v;
+        if (n == 8) {
+            const int v32 = none ? 1 << (bd - 1) : gather_at(w, cur, sa, 32, n, wd);
+            if (sl == 0) top[16] = (int16_t)v32;
         }
-    }
-    // 2. substitution: nearest available predecessor, else the first available
-    const bool any = (hm0 | hm1) != 0;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (k >= nch) break;
-        const int s = sl + 32 * k;
-        const uint32_t hmk = k ? hm1 : hm0;
-        int sc = k, src = sl;
-        if (any && !((hmk >> sl) & 1u)) {
-            const uint32_t below = hmk & ((1u << sl) - 1u);
-            if (below) {
-                src = 31 - __builtin_clz(below);
-            } else if (k == 1 && hm0) {
-                sc = 0;
-                src = 31 - __builtin_clz(hm0);
-            } else {
-                sc = hm0 ? 0 : 1;
-                src = __builtin_ctz(sc ? hm1 : hm0);
-            }
-        }
-        const int v0 = __shfl(val0, 32 * h + src, 64);
-        const int v1 = nch > 1 ? __shfl(val1, 32 * h + src, 64) : 0;
-        const int v = !any ? (1 << (bd - 1)) : (sc == 0 ? v0 : v1);
-        int16_t *dp = s < 2 * n ? left + (2 * n - s) : top + (s - 2 * n);
-        if (s < ns) *dp = (int16_t)v;
-        if (s == 2 * n) left[0] = (int16_t)v;
     }
     wave_sync();
     const int16_t *lf = left, *tp = top;
@@ -652,7 +536,7 @@ __device__ __attribute__((always_inline)) inline void predict_pair(IntraScratch 
             if (pcm) pv = 0;  // the residual is the PCM sample itself
             if (cbf) pv += it ? r1 : r0;
             pv = min(max(pv, 0), maxv);
-            w.cur[((y0 + y) << w.lsx) + x0 + x] = (Pel)pv;
+            cur[off + (y << w.lsx) + x] = (Pel)pv;
         }
     }
     wave_sync();
@@ -781,7 +665,7 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
     bool gave_up = false;  // (streaming, first launch: no parse progress for a while)
     const TbGeom G{log2ctb, chroma, W, H, cw, ch};
     const WinOffs wo = win_offs(F);  // constants of the picture: a TB's window is a select on cIdx and an add
-    constexpr int SX = chroma_sx(CF), SY = chroma_sy(CF);
+    constexpr int SX = chroma_sx(CF);
     const uint32_t dwin = F.b1 / (uint32_t)sizeof(Pel);  // from a Cb window part to Cr's, samples
     const uint32_t dres = (uint32_t)cw * (uint32_t)ch;   // from a Cb residual to Cr's, elements
 #if defined(HG_HOST_EMU)
@@ -798,6 +682,7 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
         int cur = -1;
         // finish CTU `cur`: write the window back, keep its last column as `left`
         auto finish_ctu = [&]() {
+#if !defined(HG_IABL_CTU)  // (HG_IABL_CTU, measurement builds only, wrong pixels: the per-CTU copies dropped)
             _Pragma("nounroll") for (int k = 0; k < 3; ++k) {
                 if (k >= ncomp) break;
                 if (k < k0 || k >= k1) continue;
@@ -821,6 +706,7 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
                 }
                 for (int y = lane; y < w.csy; y += kWave) w.left[y] = w.cur[y * w.csx + w.csx - 1];
             }
+#endif
             wave_sync();
             HG_FENCE_REL();
             hg_atomic_store(&progress[wave], (uint32_t)r * stride + (uint32_t)cur + 1u);
@@ -842,6 +728,7 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
                 }
                 HG_FENCE_ACQ();
             }
+#if !defined(HG_IABL_CTU)
             _Pragma("nounroll") for (int k = 0; k < 3; ++k) {
                 if (k >= ncomp) break;
                 if (k < k0 || k >= k1) continue;
@@ -854,6 +741,7 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
                     w.above[i] = (yg >= 0 && xg >= 0 && xg < PW) ? plane[(size_t)yg * PW + xg] : (Pel)0;
                 }
             }
+#endif
             wave_sync();
             return true;
         };
@@ -921,13 +809,13 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
             // ---- the block of up to 64 records that holds record t, one per lane: the packed
             // words (intra_rec.hpp) and the two masks the walk below follows
             const uint32_t base = t & ~63u;
-            LaneWord wa, wb, wc, wctu;
+            LaneWord wa, wb, wc, wd, wctu;
 #if !defined(HG_HOST_EMU)
             uint4 tblk = make_uint4(0, 0, 0, 0);  // (streaming: the record itself, for transform_tb)
 #endif
             // lane l's words of record base + l (zero where the block has no such record yet)
-            auto form = [&](int l, uint32_t &A, uint32_t &B, uint32_t &C, uint32_t &ctu) {
-                A = B = C = ctu = 0;
+            auto form = [&](int l, uint32_t &A, uint32_t &B, uint32_t &C, uint32_t &D, uint32_t &ctu) {
+                A = B = C = D = ctu = 0;
                 const uint32_t i = base + (uint32_t)l;
                 if (i < t || i >= ntu) return;
                 TuRec q;
@@ -971,6 +859,7 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
                 }
 #endif
                 B = tb_word_b(A, G);
+                D = tb_pack_d(A, G, (int)q.ctu, r);  // (the neighbours: of the record's CTB column and this row)
             };
             // a record is this wave's where it is OK, of the wave's components, and not the Cr TB of a
             // pair; it opens a CTU where its CTU is not the record's before it (the first one: not `cur`)
@@ -984,7 +873,7 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
             {
                 uint32_t prevA = 0, prevc = (uint32_t)cur;
                 for (int l = 0; l < 64; ++l) {
-                    form(l, wa.v[l], wb.v[l], wc.v[l], wctu.v[l]);
+                    form(l, wa.v[l], wb.v[l], wc.v[l], wd.v[l], wctu.v[l]);
                     const uint32_t i = base + (uint32_t)l;
                     const bool valid = i >= t && i < ntu;
                     if (valid && is_mine(wa.v[l], prevA)) mine_m |= 1ull << l;
@@ -1006,7 +895,7 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
             }
 #else
             {
-                form(lane, wa.v, wb.v, wc.v, wctu.v);
+                form(lane, wa.v, wb.v, wc.v, wd.v, wctu.v);
                 const uint32_t i = base + (uint32_t)lane;
                 const bool valid = i >= t && i < ntu;
                 const int pl = max(lane - 1, 0);
@@ -1041,7 +930,7 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
                     cur = c;
                 }
                 if (!tb) continue;
-                const uint32_t A = wa.at(l), B = wb.at(l);
+                const uint32_t A = wa.at(l), B = wb.at(l), D = wd.at(l);
                 const int cidx = tba_cidx(A), kc = cidx ? 1 : 0;
 #if defined(HG_HOST_EMU)
                 if (walk_stats_on() && !(Poll && a.stream_redo)) {
@@ -1054,15 +943,9 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
                 TbWin<Pel> w;
                 unsigned char *const wbase = F.blk + (cidx == 2 ? F.b1 : 0u);
                 w.cur = reinterpret_cast<Pel *>(wbase + wo.cur[kc]);
-                w.left = reinterpret_cast<Pel *>(wbase + wo.left[kc]);
-                w.above = reinterpret_cast<Pel *>(wbase + wo.above[kc]);
+                w.dl = wo.dl[kc];
+                w.da = wo.da[kc];
                 w.lsx = log2ctb - (cidx ? SX : 0);
-                // (from the CTU's column and the row: a few scalar operations, no SGPR held across the TB)
-                w.vw = (W - (cur << log2ctb)) >> (cidx ? SX : 0);
-                w.vh = (H - (r << log2ctb)) >> (cidx ? SY : 0);
-                w.minx = cur > 0 ? -1 : 0;
-                w.miny = r > 0 ? -1 : 0;
-                w.csl = 1 << log2ctb;
                 w.rp = cidx ? cw : W;
 #if defined(HG_HOST_EMU)
                 w.blk_lo = F.blk;
@@ -1096,20 +979,18 @@ __device__ __attribute__((always_inline)) inline void intra_body(const BatchArgs
                 if (!XfInline && (A & TBA_PAIR)) {
 #if defined(HG_HOST_EMU)
                     // (one lane: the Cb TB, then the Cr TB from the pair's bits, each as a TB of its own)
-                    predict_tb<Pel, CF>(S, A, B, w, sp.bit_depth_c, strong, lane);
+                    predict_tb<Pel, CF>(S, A, B, D, w, sp.bit_depth_c, strong, lane);
                     const uint32_t A2 = (A & ~((3u << TBA_CIDX_SHIFT) | TBA_CBF | TBA_PCM)) | (2u << TBA_CIDX_SHIFT) |
                                         ((A & TBA_CBF2) ? TBA_CBF : 0u) | ((A & TBA_PCM2) ? TBA_PCM : 0u);
                     w.cur += dwin;
-                    w.left += dwin;
-                    w.above += dwin;
                     w.rt += dres;
-                    predict_tb<Pel, CF>(S, A2, B, w, sp.bit_depth_c, strong, lane);
+                    predict_tb<Pel, CF>(S, A2, B, D, w, sp.bit_depth_c, strong, lane);
 #else
-                    predict_pair<Pel>(S, A, B, w, dwin, dres, sp.bit_depth_c, lane);
+                    predict_pair<Pel>(S, A, B, D, w, dwin, dres, sp.bit_depth_c, lane);
 #endif
                     continue;
                 }
-                predict_tb<Pel, CF>(S, A, B, w, cidx ? sp.bit_depth_c : sp.bit_depth_y, strong, lane);
+                predict_tb<Pel, CF>(S, A, B, D, w, cidx ? sp.bit_depth_c : sp.bit_depth_y, strong, lane);
             }
             if (gave_up) break;
             t = min(ntu, base + 64u);

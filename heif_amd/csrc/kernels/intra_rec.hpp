@@ -2,7 +2,7 @@
 //
 // When a wave loads 64 TuRecs, one per lane, each lane forms everything a TB's
 // prediction needs that depends only on the record and on constants of the CTB
-// row; the TB loop then reads the words of one lane (three v_readlane) and
+// row; the TB loop then reads the words of one lane (a v_readlane each) and
 // extracts fields from them, and no TuRec field is decoded on the scalar unit.
 //
 //   word A  bits  0-5   x of the TB inside its CTB, component samples
@@ -18,6 +18,15 @@
 //   word B  bits  0-7   zc, the z-order index of the TB's first luma 4x4 block in its CTU (6.4.1)
 //                 8-15  intraPredAngle (signed)   16-31  invAngle (signed)
 //   word C        the element offset of the TB's first residual from the picture's Y residual plane
+//   word D  the TB's neighbours (6.4.1): which of its 4n + 1 reference samples are decoded.  The
+//           per-sample rule reduces to five facts (tests/intra_avail/avail_driver.cpp holds them
+//           against it over every format, CTB size, TB, picture extent and picture edge):
+//           bits  0-3   below-left samples available, in fours (0-8): a prefix, nearest the TB first
+//                 4-7   above-right samples available, in fours (0-8): a prefix, left to right
+//                 8     the left column (all of it or none)    9  the row above (likewise)
+//                10     the corner             (bits 0-10 all zero: nothing is available)
+//                11-18  the first available position in the search order of 8.4.4.2.2 (0-128)
+//                19-30  the TB's first sample in its window, y * CTB width + x
 //
 // A record that is not OK packs to zero words: no field of a damaged record
 // reaches an index.  Plain inline functions, so the host emulation and a
@@ -108,7 +117,110 @@ HG_REC_FN uint32_t tb_pack_c(const TuRec &q, uint32_t a, const TbGeom &g, bool *
     return (a & TBA_OK) ? (uint32_t)off : 0u;
 }
 
+enum : uint32_t {
+    TBD_BL_SHIFT = 0, TBD_AR_SHIFT = 4, TBD_LEFT = 1u << 8, TBD_ABOVE = 1u << 9, TBD_CORNER = 1u << 10,
+    TBD_FACTS = 0x7ffu, TBD_FIRST_SHIFT = 11, TBD_OFF_SHIFT = 19,
+};
+
+// word D of a TB of size n from its facts (bl4, ar4: available below-left / above-right samples in fours)
+HG_REC_FN uint32_t tbd_make(int n, int bl4, int ar4, bool left, bool above, bool corner, int off) {
+    const int first = bl4 ? n - 4 * bl4 : (left ? n : (corner ? 2 * n : (above ? 2 * n + 1 : (ar4 ? 3 * n + 1 : 0))));
+    return ((uint32_t)bl4 << TBD_BL_SHIFT) | ((uint32_t)ar4 << TBD_AR_SHIFT) | (left ? TBD_LEFT : 0u) |
+           (above ? TBD_ABOVE : 0u) | (corner ? TBD_CORNER : 0u) | ((uint32_t)first << TBD_FIRST_SHIFT) |
+           ((uint32_t)off << TBD_OFF_SHIFT);
+}
+
+// Word D: from word A (position, size, cIdx), the record's CTB column and the row.  A group of
+// neighbours lies in one decoded or undecoded block of the TB's size or in another CTB, so one
+// sample decides it; the picture's edge and the CTB's lower and right edges then cut below-left
+// and above-right to a prefix (extents are multiples of 8 luma samples: whole fours).
+HG_REC_FN uint32_t tb_pack_d(uint32_t a, const TbGeom &g, int ctu, int r) {
+    if (!(a & TBA_OK)) return 0u;
+    const int k = (int)((a >> TBA_CIDX_SHIFT) & 3u);
+    const int subx = k ? chroma_sx(g.chroma) : 0, suby = k ? chroma_sy(g.chroma) : 0;
+    const int lsx = g.log2ctb - subx, csx = 1 << lsx, csy = 1 << (g.log2ctb - suby), csl = 1 << g.log2ctb;
+    const int x0 = (int)((a >> TBA_LX_SHIFT) & 63u), y0 = (int)((a >> TBA_LY_SHIFT) & 63u);
+    const int n = 4 << ((a >> TBA_LOG2_SHIFT) & 3u);
+    // columns, rows from the CTB's origin to the picture's edge; -1 where the picture goes on left of / above it
+    const int vw = (g.W - (ctu << g.log2ctb)) >> subx, vh = (g.H - (r << g.log2ctb)) >> suby;
+    const int minx = ctu > 0 ? -1 : 0, miny = r > 0 ? -1 : 0;
+    const int zc = tb_zidx((x0 << subx) >> 2, (y0 << suby) >> 2);
+    // 6.4.1 for the neighbour (xn, yn): inside the picture; the CTB row above is decoded up to the CTB
+    // above-right and the CTB to the left is decoded, those below and to the right are not; inside the
+    // CTB, a 4x4 luma block that precedes the TB's first in z-scan order
+    auto avail = [&](int xn, int yn) {
+        if (xn < minx || yn < miny || xn >= vw || yn >= vh) return false;
+        const int lx = xn * (1 << subx), ly = yn * (1 << suby);
+        if (ly < 0) return true;
+        if (ly >= csl || lx >= csl) return false;
+        if (lx < 0) return true;
+        return tb_zidx(lx >> 2, ly >> 2) < zc;
+    };
+    const int yend = vh < csy ? vh : csy;               // below-left ends at the picture's or the CTB's edge
+    const int xend = (y0 == 0 || vw < csx) ? vw : csx;  // above-right: the CTB's edge unless it is the row above
+    int bl = avail(x0 - 1, y0 + n) ? yend - (y0 + n) : 0, ar = avail(x0 + n, y0 - 1) ? xend - (x0 + n) : 0;
+    bl = bl < n ? bl : n;
+    ar = ar < n ? ar : n;
+    return tbd_make(n, bl >> 2, ar >> 2, avail(x0 - 1, y0), avail(x0, y0 - 1), avail(x0 - 1, y0 - 1),
+                    (y0 << lsx) + x0);
+}
+
 // the fields of the words
+HG_REC_FN int tbd_bl(uint32_t d) { return (int)((d >> TBD_BL_SHIFT) & 15u) << 2; }  // samples
+HG_REC_FN int tbd_ar(uint32_t d) { return (int)((d >> TBD_AR_SHIFT) & 15u) << 2; }
+HG_REC_FN int tbd_first(uint32_t d) { return (int)((d >> TBD_FIRST_SHIFT) & 0xffu); }
+HG_REC_FN int tbd_off(uint32_t d) { return (int)((d >> TBD_OFF_SHIFT) & 0xfffu); }
+
+// 8.4.4.2.2 on the facts.  Search position s runs 0 .. 4n: the column left of the TB bottom-up
+// (below-left first), the corner at 2n, the row above left to right.  The available positions are
+// at most three runs: one that ends at n - 1 or 2n - 1, the corner, and one from 2n + 1 or 3n + 1
+// to 3n + ar.  The position whose sample stands at s after the substitution is the last
+// available position at or below s, or the first available one where there is none: s clamped
+// into the run it lies in or behind, then to the first position.  No branch and no lane other
+// than s itself.  -1: nothing is available (every sample is 1 << (bitDepth - 1)).
+HG_REC_FN int tb_subst_src(int s, int n, uint32_t d) {
+    if (!(d & TBD_FACTS)) return -1;
+    const int never = 1 << 20, ar = tbd_ar(d);
+    const int h1 = ((d & TBD_LEFT) ? 2 * n : n) - 1;  // (an empty first run ends below the first position)
+    const int c = (d & TBD_CORNER) ? 2 * n : never;
+    const int lo3 = (d & TBD_ABOVE) ? 2 * n + 1 : (ar ? 3 * n + 1 : never), h3 = 3 * n + ar;
+    int t = s < h1 ? s : h1;
+    t = s >= c ? c : t;
+    const int t3 = s < h3 ? s : h3;
+    t = s >= lo3 ? t3 : t;
+    const int first = tbd_first(d);
+    return t > first ? t : first;
+}
+
+// the neighbour at search position s, relative to the TB's first sample
+HG_REC_FN void tb_search_pos(int s, int n, int *dx, int *dy) {
+    *dx = s <= 2 * n ? -1 : s - 2 * n - 1;
+    *dy = s < 2 * n ? 2 * n - 1 - s : -1;
+}
+
+// Where a TB's neighbours stand in its component's window, as element offsets from the window's
+// first sample: the window is the CTB's samples (pitch 1 << lsx), then somewhere behind them the
+// column left of the CTB (from row 0) and the row above it (from the corner); `left` and `above`
+// are those arrays' offsets.  The column left of the TB is the CTB's left column or the TB's
+// neighbour column, the row above it the CTB's row above or the TB's neighbour row.  Positions
+// below `split` are on the column, cbase - (s << cshift), the others on the row, rbase + s; the
+// corner goes with the column below the CTB's first row (the row above the CTB begins with it).
+struct TbSrcAddr {
+    int cbase, cshift, rbase, split;
+};
+HG_REC_FN TbSrcAddr tb_src_addr(int x0, int y0, int n, int lsx, int left, int above) {
+    TbSrcAddr a;
+    a.cshift = x0 == 0 ? 0 : lsx;
+    a.cbase = (x0 == 0 ? left + y0 : (y0 << lsx) + x0 - 1) + ((2 * n - 1) << a.cshift);
+    a.rbase = (y0 == 0 ? above + x0 + 1 : ((y0 - 1) << lsx) + x0) - (2 * n + 1);
+    a.split = y0 == 0 ? 2 * n : 2 * n + 1;
+    return a;
+}
+HG_REC_FN int tb_src_at(const TbSrcAddr &a, int s) {
+    const int c = a.cbase - (s << a.cshift), t = a.rbase + s;
+    return s < a.split ? c : t;
+}
+
 HG_REC_FN int tba_lx(uint32_t a) { return (int)((a >> TBA_LX_SHIFT) & 63u); }
 HG_REC_FN int tba_ly(uint32_t a) { return (int)((a >> TBA_LY_SHIFT) & 63u); }
 HG_REC_FN int tba_log2(uint32_t a) { return (int)((a >> TBA_LOG2_SHIFT) & 3u) + 2; }
