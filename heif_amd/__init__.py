@@ -674,6 +674,58 @@ class DecodeContext:
                                                  self._surfaces(res), ctypes.c_void_p(stream)))
         return res
 
+    def render_hdr_scaled(self, outs: Sequence[DecodedImage], gains: Sequence[DecodedImage], size, mode: str = "cover",
+                          fmt: str = "rgba16f", colorspace: str = "display-p3", headroom: Optional[float] = None,
+                          display_headroom: Optional[float] = None, sdr_white: float = 203.0, pq_bits: int = 10,
+                          alphas: Optional[Sequence[Optional[DecodedImage]]] = None, windows=None,
+                          stream: Optional[int] = None, transforms=None, out=None):
+        """render_hdr() onto a smaller (or any) grid with ONE heifgpu_render_batch_gain_scaled
+        call (one kernel launch); the full-size HDR surface is never written.  size, mode
+        and windows as in render_scaled(): ONE (N, h, w, C) device tensor for cover,
+        stretch and windows, a list of (h_i, w_i, C) tensors for "contain"; float16 or
+        uint16 as in render_hdr().  Every output pixel is the HDR formula applied to the
+        exact area averages of the base's integers, of the Q8 gain codes and of the alpha
+        samples over its footprint (include/heifgpu.h "Gain-map HDR render", the scaled
+        call): what a viewer gives that scales base and map as images and applies the map
+        afterwards, not an average in linear light.  At the window's own size the result
+        is render_hdr()'s window bit for bit.  fmt, colorspace, headroom, display_headroom,
+        sdr_white, pq_bits, alphas and transforms as in render_hdr(); so are the
+        refusals, images decoded for a window included.  out: the (h_i, w_i, C) tensors to
+        write into, which are then returned as a list."""
+        torch = self._torch
+        n = len(outs)
+        if fmt not in _lib.HDR_FORMATS:
+            raise ValueError(f"fmt {fmt!r}: one of {sorted(_lib.HDR_FORMATS)}")
+        if mode not in _lib.FIT_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(_lib.FIT_MODES)}")
+        f = _lib.HDR_FORMATS[fmt]
+        ch, pq = (4 if f & 1 else 3), f >= _lib.PIX_HDR_RGB16PQ
+        self._check_images("render_hdr_scaled", outs, alphas, gains=gains, transforms=transforms, windows=windows, out=out)
+        if any(g is None or g.image is None for g in gains):
+            raise ValueError("render_hdr_scaled needs gain images that carry their HeifImage (alloc_outputs)")
+        for i, o in enumerate(outs):
+            for name, im in (("image", o), ("gain image", gains[i]), ("alpha image", alphas[i] if alphas is not None else None)):
+                if im is not None and im.valid is not None:
+                    raise UnsupportedError(_lib.HEIFGPU_E_UNSUPPORTED,
+                                           f"render_hdr_scaled: {name} {i} was decoded for a window ({im.valid}) only")
+        if transforms is None:
+            transforms = [o.image.gain_transform(g.image, colorspace, "pq" if pq else "linear", pq_bits, headroom,
+                                                 display_headroom, sdr_white) for o, g in zip(outs, gains)]
+        bh, bw, scales = self._scales("render_hdr_scaled", outs, alphas, size, mode, windows)
+        whole, res = self._scaled_outputs(n, scales, (bh, bw) if windows is not None or mode != "contain" else None,
+                                          lambda h, w: (h, w, ch), torch.uint16 if pq else torch.float16) \
+            if out is None else (None, list(out))
+        if n:
+            imgs, aimgs, aplanes = self._render_args(outs, alphas)
+            gimgs, _, _ = self._render_args(gains, None)
+            xf = (ctypes.c_void_p * n)(*[ctypes.addressof(t) for t in transforms])
+            if stream is None:
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(lib.heifgpu_render_batch_gain_scaled(self._h, imgs, n, DecodeContext.planes_of(outs), gimgs,
+                                                            DecodeContext.planes_of(gains), aimgs, aplanes, f, scales, xf,
+                                                            self._surfaces(res), ctypes.c_void_p(stream)))
+        return whole if whole is not None else res
+
     @staticmethod
     def _check_tone(colorspace, tone_map):
         """ValueError for an unknown tone_map, or one without a colorspace to map to."""
@@ -1097,12 +1149,14 @@ class HeicDecoder:
     @classmethod
     def decode_hdr(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, colorspace: str = "display-p3",
                    headroom: Optional[float] = None, display_headroom: Optional[float] = None,
-                   sdr_white: float = 203.0, pq_bits: int = 10):
+                   sdr_white: float = 203.0, pq_bits: int = 10, size=None, mode: str = "contain"):
         """The HDR rendition of a file whose primary image has a gain map
         (HeifImage.gain_map): decodes the primary image, its gain-map image and, when
         it has one, its alpha plane, then DecodeContext.render_hdr of that one picture.
         fmt None picks "rgba16f" when there is alpha, else "rgb16f".  ValueError for a
-        file without a gain map; an Apple map needs the caller's headroom."""
+        file without a gain map; an Apple map needs the caller's headroom.  size = (h, w)
+        renders onto that box instead (DecodeContext.render_hdr_scaled with `mode`, in the
+        same one launch: the full-size HDR picture is never written)."""
         ctx = cls.context(device)
         out, alpha = cls._decode_pair(data, device, None, "contain", "all", True)
         gm = out.image.gain_map
@@ -1112,6 +1166,9 @@ class HeicDecoder:
         if fmt is None:
             fmt = "rgba16f" if alpha is not None else "rgb16f"
         alphas = [alpha] if alpha is not None and fmt.startswith("rgba") else None
+        if size is not None:
+            return ctx.render_hdr_scaled([out], [gain], size, mode, fmt, colorspace, headroom, display_headroom, sdr_white,
+                                         pq_bits, alphas)[0]
         return ctx.render_hdr([out], [gain], fmt, colorspace, headroom, display_headroom, sdr_white, pq_bits, alphas)[0]
 
     @classmethod

@@ -294,7 +294,7 @@ EXPORTS = (
     "heifgpu_image_get_hdr", "heifgpu_color_transform_make_hdr",
     "heifgpu_image_get_chroma", "heifgpu_image_set_chroma_upsampling", "heifgpu_chroma_upsample",
     "heifgpu_image_get_gain", "heifgpu_gain_transform_make", "heifgpu_gain_apply", "heifgpu_gain_sample",
-    "heifgpu_render_batch_gain",
+    "heifgpu_render_batch_gain", "heifgpu_render_batch_gain_scaled", "heifgpu_gain_average",
 )
 
 
@@ -407,6 +407,9 @@ def _load() -> ctypes.CDLL:
         "heifgpu_gain_sample": (I32, [VP, U32, U32, ctypes.c_int32, U32, U32, U32, P(U32)]),
         "heifgpu_render_batch_gain": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), P(VP), P(Planes), U32, P(VP),
                                             P(Surface), VP]),
+        "heifgpu_render_batch_gain_scaled": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), P(VP), P(Planes), U32,
+                                                   P(Scale), P(VP), P(Surface), VP]),
+        "heifgpu_gain_average": (I32, [P(U32), U32, U32, P(Scale), P(U32)]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     # (and no window decode: DecodeContext.prepare without windows then goes through prepare_ex)
@@ -424,7 +427,9 @@ def _load() -> ctypes.CDLL:
                 "heifgpu_image_get_chroma", "heifgpu_image_set_chroma_upsampling", "heifgpu_chroma_upsample",
                 # the gain-map HDR render (render_hdr / decode_hdr then need a build that has it)
                 "heifgpu_image_get_gain", "heifgpu_gain_transform_make", "heifgpu_gain_apply", "heifgpu_gain_sample",
-                "heifgpu_render_batch_gain"}
+                "heifgpu_render_batch_gain",
+                # its scaled form (render_hdr_scaled / decode_hdr(size=) then need a build that has it)
+                "heifgpu_render_batch_gain_scaled", "heifgpu_gain_average"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue

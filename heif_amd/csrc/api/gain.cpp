@@ -1,10 +1,12 @@
 // gain.cpp — the host-only calls of the gain-map HDR render (include/heifgpu.h, "Gain-map HDR
 // render"): what a parsed image says of its gain map, the transform, and the per-pixel formula
-// and the sampler on the host (kernels/gain_xform.hpp: the functions k_render_gain runs).
-// heifgpu_render_batch_gain is with the other renders in render.cpp.
+// and the sampler on the host (kernels/gain_xform.hpp: the functions k_render_gain runs), and the
+// scaled render's averaging of gain codes (kernels/gain_scale.hpp: what k_render_gain_scaled runs).
+// heifgpu_render_batch_gain and heifgpu_render_batch_gain_scaled are with the other renders in render.cpp.
 #include <vector>
 
 #include "../host/gain.hpp"
+#include "../kernels/gain_scale.hpp"
 #include "../kernels/gain_xform.hpp"
 #include "api.hpp"
 
@@ -102,6 +104,25 @@ int heifgpu_gain_sample(const void *gain, uint32_t wg, uint32_t hg_, int32_t pit
                                                   uint32_t(tx.f), uint32_t(ty.f));
         }
     }
+    return HEIFGPU_OK;
+}
+
+int heifgpu_gain_average(const uint32_t *g_q8, uint32_t w, uint32_t h, const heifgpu_scale *scale, uint32_t *out) {
+    if (!g_q8 || !scale || !out) return fail(HEIFGPU_E_INVALID, "null argument");
+    if (!w || !h || w > kGainScaleMaxSide || h > kGainScaleMaxSide) return fail(HEIFGPU_E_INVALID, "a side outside 1..65535");
+    const heifgpu_scale &sc = *scale;
+    if (!sc.out_width || !sc.out_height || sc.out_width > kGainScaleMaxSide || sc.out_height > kGainScaleMaxSide)
+        return fail(HEIFGPU_E_INVALID, "rendered size outside 1..65535");
+    uint32_t cx = 0, cy = 0, cw = w, ch = h;
+    if (sc.width || sc.height) {
+        if (!sc.width || !sc.height || sc.x >= w || sc.y >= h || sc.width > w - sc.x || sc.height > h - sc.y)
+            return fail(HEIFGPU_E_INVALID, "window empty or outside the picture");
+        cx = sc.x, cy = sc.y, cw = sc.width, ch = sc.height;
+    }
+    for (size_t i = 0; i < size_t(w) * h; ++i)
+        if (g_q8[i] > kGainScaleMaxCode) return fail(HEIFGPU_E_INVALID, "gain code above 256 * 4095");
+    std::vector<GsCol> col(cw);
+    gs_average_window(g_q8, w, cx, cy, cw, ch, sc.out_width, sc.out_height, col.data(), out);
     return HEIFGPU_OK;
 }
 

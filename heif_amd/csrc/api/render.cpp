@@ -1,7 +1,8 @@
 // render.cpp — the render family of the C ABI: heifgpu_render_batch, _scaled and _tensor
 // with their _color forms, heifgpu_scale_fit, and the filtered (bilinear / bicubic) forms
-// of the scaled and tensor renders with their host hooks.  Each call checks its arguments
-// and fills its descriptors; render_submit sends any of the descriptor types.
+// of the scaled and tensor renders with their host hooks, and the gain-map HDR render at
+// full size and scaled.  Each call checks its arguments and fills its descriptors;
+// render_submit sends any of the descriptor types (gain_submit those of the HDR renders).
 // (The calls take their C linkage from the declarations of include/heifgpu.h.)
 #include <cmath>
 #include <memory>
@@ -692,99 +693,92 @@ static void gain_table_image(const heifgpu_gain_transform &t, std::vector<uint16
     e_off = ne ? int32_t(eoff) : 0;
 }
 
-int heifgpu_render_batch_gain(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
-                              const heifgpu_image *const *gain_imgs, const heifgpu_planes *gain_in,
-                              const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
-                              const heifgpu_gain_transform *const *xf, const heifgpu_surface *out, void *stream) {
-    static_assert(sizeof(RenderDesc) % 8 == 0, "the GainRefs behind the descriptors are 8-byte aligned");
-    static_assert(HEIFGPU_PIX_HDR_RGB16F - 4 == GAIN_RGB16F && HEIFGPU_PIX_HDR_RGBA16PQ - 4 == GAIN_RGBA16PQ, "HDR formats");
-    if (!ctx || !imgs || !in || !gain_imgs || !gain_in || !xf || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
-    if (format < HEIFGPU_PIX_HDR_RGB16F || format > HEIFGPU_PIX_HDR_RGBA16PQ) return fail(HEIFGPU_E_INVALID, "format");
-    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
-    const int hf = int(format) - 4;
-    const bool pq = (hf & 2) != 0, with_alpha = (hf & 1) != 0;
-    const uint32_t wide = with_alpha ? HEIFGPU_PIX_RGBA16 : HEIFGPU_PIX_RGB16;  // what the descriptors are filled for
-    std::vector<RenderDesc> descs(n);
-    std::vector<GainRef> refs(n);
-    int bps = 0, max_tiles = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if (!imgs[i] || !gain_imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
-        if (!xf[i]) return fail(HEIFGPU_E_INVALID, "null gain transform");
-        const heifgpu_gain_transform &t = *xf[i];
-        if (const char *why = gain_transform_invalid(t)) return fail(HEIFGPU_E_INVALID, why);
-        if (t.encoding != (pq ? HEIFGPU_GAIN_PQ : HEIFGPU_GAIN_LINEAR))
-            return fail(HEIFGPU_E_INVALID, "gain transform made for the other encoding than the format's");
-        const ParsedImage &bi = imgs[i]->img, &gi = gain_imgs[i]->img;
-        if (image_chroma_up(bi).mode != 0 || image_chroma_up(gi).mode != 0 ||
-            (with_alpha && alpha_imgs && alpha_imgs[i] && image_chroma_up(alpha_imgs[i]->img).mode != 0))
-            return fail(HEIFGPU_E_UNSUPPORTED, "gain-map render of an image set to bilinear chroma upsampling");
-        heifgpu_image_info info, ginfo;
-        heifgpu_image_get_info(imgs[i], &info);
-        heifgpu_image_get_info(gain_imgs[i], &ginfo);
-        if (t.bits != info.bit_depth) return fail(HEIFGPU_E_INVALID, "gain transform made for another depth than the base image's");
-        if (t.gain_bits != ginfo.bit_depth) return fail(HEIFGPU_E_INVALID, "gain transform made for another depth than the gain map's");
-        const uint32_t lim = uint32_t(kGainMaxSide);
-        if (info.width > lim || info.height > lim || ginfo.width > lim || ginfo.height > lim)
-            return fail(HEIFGPU_E_UNSUPPORTED, "gain-map render of a side above 65535");
-        // the map is sampled at decoded base positions: its own display map must say nothing, or the same
-        const DisplayMap &dm = bi.display, &gm = gi.display;
-        const bool ident = gm.m[0] == 1 && gm.m[1] == 0 && gm.m[2] == 0 && gm.m[3] == 1 && gm.t[0] == 0 && gm.t[1] == 0 &&
-                           gm.out_width == gi.out_width && gm.out_height == gi.out_height;
-        const bool same = std::memcmp(gm.m, dm.m, sizeof(dm.m)) == 0 && gm.t[0] == dm.t[0] && gm.t[1] == dm.t[1] &&
-                          gm.out_width == dm.out_width && gm.out_height == dm.out_height;
-        // (the base's irot / imir over the map's own whole picture, as Apple's files carry them, is the base's map at the map's size)
-        const bool turned = std::memcmp(gm.m, dm.m, sizeof(dm.m)) == 0 &&
-                            uint64_t(gm.out_width) * gm.out_height == uint64_t(gi.out_width) * gi.out_height;
-        if (!ident && !same && !turned)
-            return fail(HEIFGPU_E_UNSUPPORTED, "gain image with a display map that is neither the identity nor the base's");
-        if (!gain_in[i].plane[0]) return fail(HEIFGPU_E_INVALID, "missing gain plane");
-        if (int64_t(gain_in[i].pitch[0]) < int64_t(ginfo.width) * ginfo.bytes_per_sample)
-            return fail(HEIFGPU_E_INVALID, "gain plane pitch smaller than its row");
-        RenderDesc &d = descs[i];
-        // (the alpha image may be of another sample width here: convert() reads it by alpha_bps)
-        const heifgpu_image *const *am = with_alpha ? alpha_imgs : nullptr;
-        uint32_t abits = 0;
-        if (am && am[i]) {
-            heifgpu_image_info ai;
-            heifgpu_image_get_info(am[i], &ai);
-            abits = ai.bit_depth;
-            if (!alpha_in || !alpha_in[i].plane[0]) return fail(HEIFGPU_E_INVALID, "missing alpha plane");
-            if (ai.width != info.width || ai.height != info.height)
-                return fail(HEIFGPU_E_UNSUPPORTED, "alpha image of another size than its colour image");
-            if (abits > 12) return fail(HEIFGPU_E_UNSUPPORTED, "alpha image deeper than 12 bits");
-            if (int64_t(alpha_in[i].pitch[0]) < int64_t(ai.width) * ai.bytes_per_sample)
-                return fail(HEIFGPU_E_INVALID, "alpha plane pitch smaller than its row");
-        }
-        if (int rc = render_desc_fill(i, imgs, in, nullptr, nullptr, wide, out, dm, dm.out_width, dm.out_height, bps, d))
-            return rc;
-        if (abits) {
-            heifgpu_image_info ai;
-            heifgpu_image_get_info(am[i], &ai);
-            d.alpha = reinterpret_cast<uint64_t>(alpha_in[i].plane[0]);
-            d.alpha_pitch = alpha_in[i].pitch[0];
-            d.alpha_bps = int32_t(ai.bytes_per_sample);
-            d.alpha_shift = 0;  // the sample as decoded: the GainRef says where it goes
-        }
-        const int tw = d.swap ? kRenderTile : kRenderRowW, th = d.swap ? kRenderTile : kRenderRowH;
-        d.tiles_x = (d.out_w + tw - 1) / tw;
-        d.tiles = d.tiles_x * ((d.out_h + th - 1) / th);
-        max_tiles = std::max(max_tiles, d.tiles);
-        GainRef &g = refs[i];
-        g = GainRef{};
-        g.gain = reinterpret_cast<uint64_t>(gain_in[i].plane[0]);
-        g.gain_pitch = gain_in[i].pitch[0];
-        g.gain_bps = int32_t(ginfo.bytes_per_sample);
-        g.w = int32_t(info.width), g.h = int32_t(info.height), g.wg = int32_t(ginfo.width), g.hg = int32_t(ginfo.height);
-        g.inv_w = 1.0 / double(info.width), g.inv_h = 1.0 / double(info.height);
-        g.n = 1 << t.bits;
-        for (int k = 0; k < 9; ++k) g.m[k] = t.m[k];
-        g.k_b = t.k_b, g.k_a = t.k_a;
-        g.gmax = 256u * ((1u << t.gain_bits) - 1);
-        g.maxp = pq ? int32_t((1u << t.pq_bits) - 1) : 0;
-        g.alpha_shift = pq && abits ? int32_t(abits) - int32_t(t.pq_bits) : 0;
-        g.alpha_scale = abits ? 1.0f / float((1u << abits) - 1) : 1.0f;
+// What the two gain-map renders check and fill alike for image i, in front of its descriptor:
+// the transform, the images' depths and sides, the gain image's display map, the planes'
+// pitches.  g: everything of the GainRef but its tables; abits: the alpha image's depth, 0 without one.
+static int gain_image_fill(size_t i, const heifgpu_image *const *imgs, const heifgpu_image *const *gain_imgs,
+                           const heifgpu_planes *gain_in, const heifgpu_image *const *alpha_imgs,
+                           const heifgpu_planes *alpha_in, bool pq, bool with_alpha,
+                           const heifgpu_gain_transform *const *xf, GainRef &g, uint32_t &abits) {
+    if (!imgs[i] || !gain_imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
+    if (!xf[i]) return fail(HEIFGPU_E_INVALID, "null gain transform");
+    const heifgpu_gain_transform &t = *xf[i];
+    if (const char *why = gain_transform_invalid(t)) return fail(HEIFGPU_E_INVALID, why);
+    if (t.encoding != (pq ? HEIFGPU_GAIN_PQ : HEIFGPU_GAIN_LINEAR))
+        return fail(HEIFGPU_E_INVALID, "gain transform made for the other encoding than the format's");
+    const ParsedImage &bi = imgs[i]->img, &gi = gain_imgs[i]->img;
+    if (image_chroma_up(bi).mode != 0 || image_chroma_up(gi).mode != 0 ||
+        (with_alpha && alpha_imgs && alpha_imgs[i] && image_chroma_up(alpha_imgs[i]->img).mode != 0))
+        return fail(HEIFGPU_E_UNSUPPORTED, "gain-map render of an image set to bilinear chroma upsampling");
+    heifgpu_image_info info, ginfo;
+    heifgpu_image_get_info(imgs[i], &info);
+    heifgpu_image_get_info(gain_imgs[i], &ginfo);
+    if (t.bits != info.bit_depth) return fail(HEIFGPU_E_INVALID, "gain transform made for another depth than the base image's");
+    if (t.gain_bits != ginfo.bit_depth) return fail(HEIFGPU_E_INVALID, "gain transform made for another depth than the gain map's");
+    const uint32_t lim = uint32_t(kGainMaxSide);
+    if (info.width > lim || info.height > lim || ginfo.width > lim || ginfo.height > lim)
+        return fail(HEIFGPU_E_UNSUPPORTED, "gain-map render of a side above 65535");
+    // the map is sampled at decoded base positions: its own display map must say nothing, or the same
+    const DisplayMap &dm = bi.display, &gm = gi.display;
+    const bool ident = gm.m[0] == 1 && gm.m[1] == 0 && gm.m[2] == 0 && gm.m[3] == 1 && gm.t[0] == 0 && gm.t[1] == 0 &&
+                       gm.out_width == gi.out_width && gm.out_height == gi.out_height;
+    const bool same = std::memcmp(gm.m, dm.m, sizeof(dm.m)) == 0 && gm.t[0] == dm.t[0] && gm.t[1] == dm.t[1] &&
+                      gm.out_width == dm.out_width && gm.out_height == dm.out_height;
+    // (the base's irot / imir over the map's own whole picture, as Apple's files carry them, is the base's map at the map's size)
+    const bool turned = std::memcmp(gm.m, dm.m, sizeof(dm.m)) == 0 &&
+                        uint64_t(gm.out_width) * gm.out_height == uint64_t(gi.out_width) * gi.out_height;
+    if (!ident && !same && !turned)
+        return fail(HEIFGPU_E_UNSUPPORTED, "gain image with a display map that is neither the identity nor the base's");
+    if (!gain_in[i].plane[0]) return fail(HEIFGPU_E_INVALID, "missing gain plane");
+    if (int64_t(gain_in[i].pitch[0]) < int64_t(ginfo.width) * ginfo.bytes_per_sample)
+        return fail(HEIFGPU_E_INVALID, "gain plane pitch smaller than its row");
+    // (the alpha image may be of another sample width here: convert() reads it by alpha_bps)
+    abits = 0;
+    if (with_alpha && alpha_imgs && alpha_imgs[i]) {
+        heifgpu_image_info ai;
+        heifgpu_image_get_info(alpha_imgs[i], &ai);
+        abits = ai.bit_depth;
+        if (!alpha_in || !alpha_in[i].plane[0]) return fail(HEIFGPU_E_INVALID, "missing alpha plane");
+        if (ai.width != info.width || ai.height != info.height)
+            return fail(HEIFGPU_E_UNSUPPORTED, "alpha image of another size than its colour image");
+        if (abits > 12) return fail(HEIFGPU_E_UNSUPPORTED, "alpha image deeper than 12 bits");
+        if (int64_t(alpha_in[i].pitch[0]) < int64_t(ai.width) * ai.bytes_per_sample)
+            return fail(HEIFGPU_E_INVALID, "alpha plane pitch smaller than its row");
     }
-    // the tables: the context's content cache (color_refs_fill's rules)
+    g = GainRef{};
+    g.gain = reinterpret_cast<uint64_t>(gain_in[i].plane[0]);
+    g.gain_pitch = gain_in[i].pitch[0];
+    g.gain_bps = int32_t(ginfo.bytes_per_sample);
+    g.w = int32_t(info.width), g.h = int32_t(info.height), g.wg = int32_t(ginfo.width), g.hg = int32_t(ginfo.height);
+    g.inv_w = 1.0 / double(info.width), g.inv_h = 1.0 / double(info.height);
+    g.n = 1 << t.bits;
+    for (int k = 0; k < 9; ++k) g.m[k] = t.m[k];
+    g.k_b = t.k_b, g.k_a = t.k_a;
+    g.gmax = 256u * ((1u << t.gain_bits) - 1);
+    g.maxp = pq ? int32_t((1u << t.pq_bits) - 1) : 0;
+    g.alpha_shift = pq && abits ? int32_t(abits) - int32_t(t.pq_bits) : 0;
+    g.alpha_scale = abits ? 1.0f / float((1u << abits) - 1) : 1.0f;
+    return HEIFGPU_OK;
+}
+
+// the alpha image of a gain-map render in its descriptor (gain_image_fill has checked it)
+static void gain_alpha_fill(const heifgpu_image *alpha_img, const heifgpu_planes &alpha_in, RenderDesc &d) {
+    heifgpu_image_info ai;
+    heifgpu_image_get_info(alpha_img, &ai);
+    d.alpha = reinterpret_cast<uint64_t>(alpha_in.plane[0]);
+    d.alpha_pitch = alpha_in.pitch[0];
+    d.alpha_bps = int32_t(ai.bytes_per_sample);
+    d.alpha_shift = 0;  // the sample as decoded: the GainRef says where it goes
+}
+
+// What the two gain-map renders end in, for Desc = RenderDesc or GainScaleDesc: the tables into
+// the context's content cache (color_refs_fill's rules), a ring slot, the descriptors then the
+// GainRefs in one staging image, one copy, the one launch and the slot's event.
+template <class Desc, class Launch>
+static int gain_submit(heifgpu_ctx *ctx, const std::vector<Desc> &descs, std::vector<GainRef> &refs,
+                       const heifgpu_gain_transform *const *xf, Launch launch, void *stream) {
+    static_assert(sizeof(Desc) % 8 == 0, "the GainRefs behind the descriptors are 8-byte aligned");
+    const size_t n = descs.size();
     HIP_TRY(hipSetDevice(ctx->device));
     if (!ctx->color) ctx->color = new ColorCache;
     ColorCache &cache = *ctx->color;
@@ -816,14 +810,90 @@ int heifgpu_render_batch_gain(heifgpu_ctx *ctx, const heifgpu_image *const *imgs
     RenderRing::Slot *slot = nullptr;
     if (int rc = render_ring_slot(ctx, &slot)) return rc;
     RenderRing::Slot &sl = *slot;
-    const size_t dbytes = n * sizeof(RenderDesc), rbytes = n * sizeof(GainRef);
+    const size_t dbytes = n * sizeof(Desc), rbytes = n * sizeof(GainRef);
     HIP_TRY(sl.host.reserve(dbytes + rbytes));
     HIP_TRY(sl.dev.alloc(dbytes + rbytes));
     std::memcpy(sl.host.p, descs.data(), dbytes);
     std::memcpy(sl.host.p + dbytes, refs.data(), rbytes);  // behind the descriptors: one copy
     HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host.p, dbytes + rbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_render_gain(reinterpret_cast<const RenderDesc *>(sl.dev.p), int(n), max_tiles, hf, bps, s));  // the one launch
+    HIP_TRY(launch(reinterpret_cast<const Desc *>(sl.dev.p), s));  // the one launch
     HIP_TRY(hipEventRecord(sl.done, s));
     sl.pending = true;
     return HEIFGPU_OK;
+}
+
+int heifgpu_render_batch_gain(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
+                              const heifgpu_image *const *gain_imgs, const heifgpu_planes *gain_in,
+                              const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
+                              const heifgpu_gain_transform *const *xf, const heifgpu_surface *out, void *stream) {
+    static_assert(HEIFGPU_PIX_HDR_RGB16F - 4 == GAIN_RGB16F && HEIFGPU_PIX_HDR_RGBA16PQ - 4 == GAIN_RGBA16PQ, "HDR formats");
+    if (!ctx || !imgs || !in || !gain_imgs || !gain_in || !xf || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (format < HEIFGPU_PIX_HDR_RGB16F || format > HEIFGPU_PIX_HDR_RGBA16PQ) return fail(HEIFGPU_E_INVALID, "format");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    const int hf = int(format) - 4;
+    const bool pq = (hf & 2) != 0, with_alpha = (hf & 1) != 0;
+    const uint32_t wide = with_alpha ? HEIFGPU_PIX_RGBA16 : HEIFGPU_PIX_RGB16;  // what the descriptors are filled for
+    std::vector<RenderDesc> descs(n);
+    std::vector<GainRef> refs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t abits = 0;
+        if (int rc = gain_image_fill(i, imgs, gain_imgs, gain_in, alpha_imgs, alpha_in, pq, with_alpha, xf, refs[i], abits))
+            return rc;
+        const DisplayMap &dm = imgs[i]->img.display;
+        RenderDesc &d = descs[i];
+        if (int rc = render_desc_fill(i, imgs, in, nullptr, nullptr, wide, out, dm, dm.out_width, dm.out_height, bps, d))
+            return rc;
+        if (abits) gain_alpha_fill(alpha_imgs[i], alpha_in[i], d);
+        const int tw = d.swap ? kRenderTile : kRenderRowW, th = d.swap ? kRenderTile : kRenderRowH;
+        d.tiles_x = (d.out_w + tw - 1) / tw;
+        d.tiles = d.tiles_x * ((d.out_h + th - 1) / th);
+        max_tiles = std::max(max_tiles, d.tiles);
+    }
+    const int nn = int(n);
+    return gain_submit(ctx, descs, refs, xf,
+                       [=](const RenderDesc *dev, hipStream_t s) { return launch_render_gain(dev, nn, max_tiles, hf, bps, s); },
+                       stream);
+}
+
+// heifgpu_render_batch_gain onto another grid (k_render_gain_scaled): its checks, then those of
+// heifgpu_render_batch_scaled for the heifgpu_scale, all before anything is launched.
+int heifgpu_render_batch_gain_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                     const heifgpu_planes *in, const heifgpu_image *const *gain_imgs,
+                                     const heifgpu_planes *gain_in, const heifgpu_image *const *alpha_imgs,
+                                     const heifgpu_planes *alpha_in, uint32_t format, const heifgpu_scale *scales,
+                                     const heifgpu_gain_transform *const *xf, const heifgpu_surface *out, void *stream) {
+    // (the context is looked at last, as in heifgpu_render_batch_scaled)
+    if (!imgs || !in || !gain_imgs || !gain_in || !scales || !xf || !out || n == 0)
+        return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (format < HEIFGPU_PIX_HDR_RGB16F || format > HEIFGPU_PIX_HDR_RGBA16PQ) return fail(HEIFGPU_E_INVALID, "format");
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    const int hf = int(format) - 4;
+    const bool pq = (hf & 2) != 0, with_alpha = (hf & 1) != 0;
+    const uint32_t wide = with_alpha ? HEIFGPU_PIX_RGBA16 : HEIFGPU_PIX_RGB16;
+    std::vector<GainScaleDesc> descs(n);
+    std::vector<GainRef> refs(n);
+    int bps = 0, max_tiles = 0;
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t abits = 0;
+        GainRef &g = refs[i];
+        if (int rc = gain_image_fill(i, imgs, gain_imgs, gain_in, alpha_imgs, alpha_in, pq, with_alpha, xf, g, abits))
+            return rc;
+        GainScaleDesc &gd = descs[i];
+        gd = GainScaleDesc{};
+        if (int rc = scale_desc_fill(i, imgs, in, nullptr, nullptr, wide, scales[i], 0, out, bps, gd.s)) return rc;
+        if (abits) gain_alpha_fill(alpha_imgs[i], alpha_in[i], gd.s.r);
+        gd.gain = g.gain, gd.gain_pitch = g.gain_pitch, gd.gain_bps = g.gain_bps;
+        gd.w = g.w, gd.h = g.h, gd.wg = g.wg, gd.hg = g.hg;
+        gd.inv_w = g.inv_w, gd.inv_h = g.inv_h;
+        gd.gmax = g.gmax;
+        max_tiles = std::max(max_tiles, gd.s.r.tiles);
+    }
+    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
+    const int nn = int(n);
+    return gain_submit(ctx, descs, refs, xf,
+                       [=](const GainScaleDesc *dev, hipStream_t s) {
+                           return launch_render_gain_scaled(dev, nn, max_tiles, hf, bps, s);
+                       },
+                       stream);
 }

@@ -42,13 +42,18 @@ struct GainTap {
 // s in [0, W), W and Wg in [1, kGainMaxSide], inv_w = 1.0 / W.  The quotient is a
 // double-precision estimate (A < 2^40 is exact in a double, the product is off by less
 // than one) corrected exactly in integers, as k_render_scaled's quotient is.
-HG_XF_HD GainTap gain_tap(int s, int W, int Wg, double inv_w) {
+// (in two steps, which a walk shares: q = floor(A / W) and its remainder, then the taps of q)
+HG_XF_HD uint32_t gain_tap_quotient(int s, int W, int Wg, double inv_w, uint32_t &rem_out) {
     const uint64_t A = (uint64_t)(128u * (2u * (uint32_t)s + 1u)) * (uint32_t)Wg;
     uint64_t q = (uint64_t)((double)A * inv_w);
-    const int64_t rem = (int64_t)(A - q * (uint32_t)W);
-    if (rem < 0) --q;
-    else if (rem >= (int64_t)W) ++q;
-    const int32_t t = (int32_t)q - 128;  // q <= 256 Wg < 2^24
+    int64_t rem = (int64_t)(A - q * (uint32_t)W);
+    if (rem < 0) --q, rem += W;
+    else if (rem >= (int64_t)W) ++q, rem -= W;
+    rem_out = (uint32_t)rem;
+    return (uint32_t)q;  // q <= 256 Wg < 2^24
+}
+HG_XF_HD GainTap gain_tap_of(uint32_t q, int Wg) {
+    const int32_t t = (int32_t)q - 128;
     const int32_t i = t >> 8;
     GainTap r;
     r.f = t & 255;
@@ -56,11 +61,57 @@ HG_XF_HD GainTap gain_tap(int s, int W, int Wg, double inv_w) {
     r.i1 = i + 1 < 0 ? 0 : i + 1 > Wg - 1 ? Wg - 1 : i + 1;
     return r;
 }
+HG_XF_HD GainTap gain_tap(int s, int W, int Wg, double inv_w) {
+    uint32_t rem;
+    return gain_tap_of(gain_tap_quotient(s, W, Wg, inv_w, rem), Wg);
+}
+
+// gain_tap along a walk that mostly moves to a neighbouring position (the source rows of
+// k_render_gain_scaled's first stage): A = 128 (2 s + 1) Wg = q W + rem is kept exactly, and
+// a step of s by one adds or takes 256 Wg = dq W + dr.  Integers only after the first position.
+struct GainTapWalk {
+    int32_t s;        // the position the state is at
+    uint32_t q, rem;  // floor(A / W) and A mod W
+    uint32_t dq, dr;
+};
+HG_XF_HD void gain_walk_start(GainTapWalk &w, int s, int W, int Wg, double inv_w) {
+    w.s = s;
+    w.q = gain_tap_quotient(s, W, Wg, inv_w, w.rem);
+    w.dq = 256u * (uint32_t)Wg / (uint32_t)W;
+    w.dr = 256u * (uint32_t)Wg - w.dq * (uint32_t)W;
+}
+// the state at s: a step from a neighbouring position, a fresh start from anywhere else
+HG_XF_HD void gain_walk_seek(GainTapWalk &w, int s, int W, int Wg, double inv_w) {
+    if (s == w.s + 1) {
+        w.q += w.dq, w.rem += w.dr;
+        if (w.rem >= (uint32_t)W) w.rem -= (uint32_t)W, ++w.q;
+        w.s = s;
+    } else if (s == w.s - 1) {
+        w.q -= w.dq;
+        if (w.rem < w.dr) w.rem += (uint32_t)W, --w.q;
+        w.rem -= w.dr;
+        w.s = s;
+    } else if (s != w.s) {
+        gain_walk_start(w, s, W, Wg, inv_w);
+    }
+}
 
 // the Q8 gain code, 0 .. 256 maxg, of the four samples (at most 4095 each: below 2^28 + 128)
 HG_XF_HD uint32_t gain_sample(uint32_t g00, uint32_t g01, uint32_t g10, uint32_t g11, uint32_t fx, uint32_t fy) {
     const uint32_t top = (256u - fx) * g00 + fx * g01, bot = (256u - fx) * g10 + fx * g11;
     return ((256u - fy) * top + fy * bot + 128u) >> 8;
+}
+// gain_sample in its two steps, for a walk that keeps a map row's two taps as their weighted
+// sum: gain_sample(g00, g01, g10, g11, fx, fy) == gain_sample_rows(gain_sample_row(g00, g01, fx),
+// gain_sample_row(g10, g11, fx), fy).  Every factor is below 2^24 even for samples of 16 bits
+// (256 * 65535 < 2^24), and is written so: the masks change nothing and let the device's
+// compiler take its 24-bit multiplier (a quarter of the 32-bit one's cycles).
+HG_XF_HD uint32_t gain_mul24(uint32_t a, uint32_t b) { return (a & 0xffffffu) * (b & 0xffffffu); }
+HG_XF_HD uint32_t gain_sample_row(uint32_t g0, uint32_t g1, uint32_t fx) {
+    return gain_mul24(256u - fx, g0) + gain_mul24(fx, g1);
+}
+HG_XF_HD uint32_t gain_sample_rows(uint32_t top, uint32_t bot, uint32_t fy) {
+    return (gain_mul24(256u - fy, top) + gain_mul24(fy, bot) + 128u) >> 8;
 }
 
 // M of T[i], T[i + 1] (each at most kGainTMax) and f = g & 255

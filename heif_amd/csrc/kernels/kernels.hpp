@@ -309,6 +309,22 @@ static_assert(sizeof(GainRef) % 8 == 0, "GainRef: a multiple of 8 bytes behind t
 // k_render_gain's formats: bit 0 alpha, bit 1 PQ (HEIFGPU_PIX_HDR_* - 4)
 enum : int { GAIN_RGB16F = 0, GAIN_RGBA16F = 1, GAIN_RGB16PQ = 2, GAIN_RGBA16PQ = 3 };
 
+// The scaled gain-map HDR render (k_render_gain_scaled, render_gain_scaled.hip; gain_scale.hpp has
+// the averaging of the gain codes): one descriptor per image, k_render_scaled's (at the 16-bit
+// formats with alpha_shift 0, as above) followed by what the first stage reads of the gain map;
+// the image's GainRef lies behind the call's descriptors as k_render_gain's does and is read in
+// the epilogue only.
+struct GainScaleDesc {
+    ScaleDesc s;
+    uint64_t gain;         // the gain map's luma plane
+    int32_t gain_pitch, gain_bps;
+    int32_t w, h, wg, hg;  // the decoded base and gain-map sizes
+    double inv_w, inv_h;   // 1.0 / w, 1.0 / h (gain_tap's estimate)
+    uint32_t gmax;         // 256 * maxg (GainRef::gmax)
+    int32_t pad;
+};
+static_assert(sizeof(GainScaleDesc) % 8 == 0, "GainScaleDesc: the GainRefs behind the descriptors are 8-byte aligned");
+
 // parse modes (BatchArgs::parse_mode; heifgpu_batch_opts::parse_mode)
 // (4 was r05's row waves, HEIFGPU_PARSE_ROWS: removed in ABI 6, prepare answers HEIFGPU_E_UNSUPPORTED)
 enum : int { PARSE_AUTO = 0, PARSE_LANES = 1, PARSE_SOLO = 2, PARSE_SPREAD = 3 };
@@ -425,6 +441,9 @@ hipError_t launch_render_chroma<ResampleTensorDesc>(const ResampleTensorDesc *de
 // as many GainRefs behind them on the device; format GAIN_*
 hipError_t launch_render_gain(const RenderDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
                               hipStream_t s);
+// k_render_gain_scaled (render_gain_scaled.hip): the same, over GainScaleDescs
+hipError_t launch_render_gain_scaled(const GainScaleDesc *descs, int n_images, int max_tiles, int format,
+                                     int bytes_per_sample, hipStream_t s);
 hipError_t launch_parse(const BatchArgs &a, hipStream_t s);
 // (launch_parse's: the kernels of parse_solo.hip and parse_lean.hip)
 hipError_t launch_parse_solo(const BatchArgs &a, hipStream_t s);

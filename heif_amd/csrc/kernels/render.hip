@@ -187,45 +187,8 @@ void launch_fmt(const RenderDesc *descs, dim3 grid, int format, hipStream_t s) {
 // tile's pixels wait in LDS, packed as Px, and leave through store_row with
 // lanes along the output's x (for swapped axes that read is the transpose,
 // pitch 65 dwords as in k_render).
-constexpr int kScaleRowGroup = 4;  // source rows whose loads are issued together
-
-struct ScaleChroma {
-    int cb[2], cr[2];  // as loaded, for a thread's two columns
-};
-
-// convert()'s arithmetic for the two columns of one source row (samples as loaded),
-// weighted into the column sums; every product has factors below 2^23
-// (UP: cc holds C' of either column, chroma_up.hpp: two sets of products whatever the format)
-template <int FMT, bool UP = false>
-__device__ __forceinline__ void scale_acc(const RenderDesc &d, const int (&ys)[2], const ScaleChroma &cc,
-                                          const int (&al)[2], uint32_t w, uint32_t (&acc)[2][4]) {
-    int tr[2] = {0, 0}, tg[2] = {0, 0}, tb[2] = {0, 0};  // the chroma terms of R, G, B
-    if (d.chroma) {
-        const int n = !UP && chroma_sx(d.chroma) ? 1 : 2;  // a subsampled pair shares its sample: one set of products
-        for (int c = 0; c < n; ++c) {
-            const int cb = (cc.cb[c] >> d.shift) - d.cmid, cr = (cc.cr[c] >> d.shift) - d.cmid;
-            tr[c] = __mul24(d.cr_r, cr);
-            tg[c] = __mul24(d.cb_g, cb) + __mul24(d.cr_g, cr);
-            tb[c] = __mul24(d.cb_b, cb);
-        }
-        if (n == 1) tr[1] = tr[0], tg[1] = tg[0], tb[1] = tb[0];
-    }
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int yv = __mul24(d.ys, (ys[c] >> d.shift) - d.yoff) + 32768;
-        const int R = min(max((yv + tr[c]) >> 16, 0), d.maxv);
-        const int G = min(max((yv - tg[c]) >> 16, 0), d.maxv);
-        const int B = min(max((yv + tb[c]) >> 16, 0), d.maxv);
-        acc[c][0] += __umul24(w, (uint32_t)R);
-        acc[c][1] += __umul24(w, (uint32_t)G);
-        acc[c][2] += __umul24(w, (uint32_t)B);
-        if (FMT & 1) {
-            int A = d.maxv;  // opaque
-            if (d.alpha) A = d.alpha_shift >= 0 ? al[c] >> d.alpha_shift : al[c] << -d.alpha_shift;
-            acc[c][3] += __umul24(w, (uint32_t)A);
-        }
-    }
-}
+// (kScaleRowGroup, ScaleChroma and scale_acc, convert()'s arithmetic for a thread's two columns, are in
+// render_px.hpp: k_render_gain_scaled walks its columns with them too)
 
 // Stage 1 for one thread: its two source columns x0, x1 down the window rows [ka0, ka1)
 // of output line a, weighted.  The loads of kScaleRowGroup rows are issued before the

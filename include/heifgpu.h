@@ -800,6 +800,51 @@ int heifgpu_render_batch_gain(heifgpu_ctx *ctx, const heifgpu_image *const *imgs
                               const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in,
                               uint32_t format, const heifgpu_gain_transform *const *xf,
                               const heifgpu_surface *out, void *stream);
+/* THE SCALED CALL (added within ABI 6: new entry points only; no table or transform struct
+ * changes, a heifgpu_gain_transform made for heifgpu_render_batch_gain serves it).
+ * heifgpu_render_batch_gain onto another grid, with ONE launch and without the full-size HDR
+ * surface: scales[i] names a window (x, y, width, height) of base i's displayed picture and the
+ * rendered size out_width x out_height by heifgpu_render_batch_scaled's rules (0 sizes: the
+ * whole picture; the window non-empty and inside the picture; every side at most 65535), and
+ * out[i] is out_width x out_height pixels.  With wx, wy the weights of the scaled render and
+ *   avg(v) = floor((2 sum_j sum_i wy(Y, j) wx(X, i) v[y + j][x + i] + cw ch) / (2 cw ch))
+ * over the displayed positions of the window, output pixel (X, Y) is made of three rounded
+ * area averages, "alpha like a colour":
+ *   C_c = avg(c_c), c_c the base's integers at depth B as above: what
+ *         heifgpu_render_batch_scaled writes without a transform at the 16-bit formats;
+ *   Gq  = avg(g), g the Q8 gain code of the position's decoded base position (sx, sy),
+ *         exactly as above (aligned centres, the + 128 >> 8 rounding per source pixel);
+ *   A   = avg(a), a the alpha sample at its own depth Ba (the RGBA formats with an alpha image).
+ * Then, per output pixel only, the formula above on (L_c = in_lut[c][C_c], Gq): i = Gq >> 8,
+ * f = Gq & 255 and M from T, the apply with k_b and k_a, the matrix, the encoding; alpha is
+ * encoded from A by the alpha rules of the two encodings.  Nothing of this is computed in
+ * floating point beyond what the formula above already is.  (The rounded averages are
+ * transformed, not the source pixels: the rule of every scaled render here, and what a viewer
+ * does that scales base and map as images and applies the map afterwards.  It is not an
+ * average of the HDR levels in linear light.)  With out_width x out_height the window's own
+ * size every avg is the value itself: the result is bit for bit that window of what
+ * heifgpu_render_batch_gain writes.  RANGES: the weights of an output line add up to the
+ * window's side, so a line's column sum of g reaches 65535 * 256 * 4095 > 2^35, the whole sum
+ * 2^52 and the numerator 2^53: g is summed as its parts g >> 8 and g & 255, each within the
+ * sums of a 12-bit sample, and the quotient taken in two exact steps (kernels/gain_scale.hpp,
+ * the one statement of it in code; tests/gain_scale_ref.py restates the call in numpy).
+ * Refusals: those of heifgpu_render_batch_gain with their codes, then those of
+ * heifgpu_render_batch_scaled for scales[i] (HEIFGPU_E_INVALID: a rendered size outside
+ * 1..65535, a window empty or outside the picture; HEIFGPU_E_UNSUPPORTED: a window side above
+ * 65535), all before anything is launched.  A window-decoded image is not known to this layer
+ * either (DecodeContext.render_hdr_scaled refuses it). */
+int heifgpu_render_batch_gain_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                     const heifgpu_planes *in,
+                                     const heifgpu_image *const *gain_imgs, const heifgpu_planes *gain_in,
+                                     const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in,
+                                     uint32_t format, const heifgpu_scale *scales,
+                                     const heifgpu_gain_transform *const *xf,
+                                     const heifgpu_surface *out, void *stream);
+/* host only: avg(g) of the scaled call over a w x h array of Q8 gain codes in displayed
+ * orientation (each at most 256 * 4095, rows of w entries), for the window and rendered size of
+ * `scale` (by the rules above, the picture being w x h); out_width * out_height uint32 out.
+ * Runs the kernel's own accumulation and quotient. */
+int heifgpu_gain_average(const uint32_t *g_q8, uint32_t w, uint32_t h, const heifgpu_scale *scale, uint32_t *out);
 
 /* ---- window decode: decode only the pictures a window reads ----------------
  * (added within ABI 6: new entry points only; heifgpu_batch_opts keeps its layout.)

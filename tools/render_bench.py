@@ -89,8 +89,19 @@ the same planes that writes as many bytes, alternated in one process in each of 
   render_rgb16 / render_hdr_rgb16pq    the same in RGB16 / the HDR render, PQ at 10 bits
 hdr / managed is reported per pair with the spreads (max - min over runs); nothing is gated.
 
+--gain --scaled measures the scaled gain-map HDR render (heifgpu_render_batch_gain_scaled, DESIGN
+5.35) on --gain's geometry and transforms, to 224 x 224 cover and to 1008 x 756 stretch, as rgba16f
+and as rgb16pq at 10 bits, beside two things the parent commit's code already does, alternated in
+one process in each of the --runs runs:
+  scaled_sdr_rgba16      heifgpu_render_batch_scaled_color RGBA16 to sRGB of the same planes to the
+                         same size: the SDR render that reads the same bytes (hdr / sdr is what the
+                         gain pass costs)
+  full_hdr_*             the full-size heifgpu_render_batch_gain: what a caller pays today before
+                         any resize
+Min and spread (max - min over runs) are reported; nothing is gated.
+
 usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json]
-                                    [--scaled | --tensor | --color | --filter | --tone | --chroma bilinear | --gain]
+                                    [--scaled | --tensor | --color | --filter | --tone | --chroma bilinear | --gain [--scaled]]
 """
 import argparse
 import ctypes
@@ -816,6 +827,114 @@ def gain_main(args):
         pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
 
 
+def gain_scaled_main(args):
+    n = args.images
+    dev = torch.device("cuda", 0)
+    ctx = H.DecodeContext(0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    golden = forced_rotation((ROOT / "tests" / "golden" / "halfmoonbay.heic").read_bytes(), 0)
+    g = torch.Generator(device=dev).manual_seed(1)
+    img = H.HeifImage.parse(golden)
+    gimg = H.HeifImage.parse(golden, img.gain_map.item_id)
+    gi, d = gimg.info, img.display
+    assert (img.info.width, img.info.height, gi.width, gi.height) == (W, HGT, W // 2, HGT // 2)
+
+    def plane(h, w):
+        return torch.randint(0, 256, (h, w), generator=g, device=dev, dtype=torch.int32).to(torch.uint8)
+
+    keep = [[plane(HGT, W), plane(HGT // 2, W // 2), plane(HGT // 2, W // 2), plane(gi.height, gi.width)] for _ in range(n)]
+    planes, gplanes = (_lib.Planes * n)(), (_lib.Planes * n)()
+    for i, (y, cb, cr, gm) in enumerate(keep):
+        for c, t in enumerate((y, cb, cr)):
+            planes[i].plane[c], planes[i].pitch[c] = t.data_ptr(), t.stride(0)
+        gplanes[i].plane[0], gplanes[i].pitch[0] = gm.data_ptr(), gm.stride(0)
+    imgs = (ctypes.c_void_p * n)(*[img._h.value] * n)
+    gimgs = (ctypes.c_void_p * n)(*[gimg._h.value] * n)
+    ct = img.color_transform("srgb", 8)
+    assert not ct.identity
+    xf = (ctypes.c_void_p * n)(*[ctypes.addressof(ct)] * n)
+    gts = {enc: img.gain_transform(gimg, "srgb", enc, 10, headroom=4.0) for enc in ("linear", "pq")}
+    gxf = {enc: (ctypes.c_void_p * n)(*[ctypes.addressof(t)] * n) for enc, t in gts.items()}
+
+    def surfaces(h, w, ch):
+        # one 8-byte-per-pixel surface per image; the 6-byte format writes into the same memory
+        out = torch.empty((n, h, w, 4), dtype=torch.int16, device=dev)
+        surf = (_lib.Surface * n)()
+        for i in range(n):
+            surf[i].pixels, surf[i].pitch = out[i].data_ptr(), w * ch * 2
+        return out, surf
+
+    full_px, full_surf4 = surfaces(HGT, W, 4)
+    full_surf3 = (_lib.Surface * n)()
+    for i in range(n):
+        full_surf3[i].pixels, full_surf3[i].pitch = full_px[i].data_ptr(), W * 6
+
+    def full_hdr(fmt, surf, enc):
+        def run():
+            _lib.check(_lib.lib.heifgpu_render_batch_gain(ctx._h, imgs, n, planes, gimgs, gplanes, None, None, fmt, gxf[enc],
+                                                          surf, stream))
+        return run
+
+    variants = [("full", "full_hdr_rgba16f", full_hdr(_lib.PIX_HDR_RGBA16F, full_surf4, "linear"), n * W * HGT * 9.75),
+                ("full", "full_hdr_rgb16pq", full_hdr(_lib.PIX_HDR_RGB16PQ, full_surf3, "pq"), n * W * HGT * 7.75)]
+    keep_out = []
+    for name, bw, bh, mode in (("cover224", 224, 224, _lib.FIT_COVER), ("stretch1008", 1008, 756, _lib.FIT_STRETCH)):
+        sc = (_lib.Scale * n)()
+        for i in range(n):
+            _lib.check(_lib.lib.heifgpu_scale_fit(ctypes.byref(d), bw, bh, mode, ctypes.byref(sc[i])))
+        window_px = (sc[0].width or d.out_width) * (sc[0].height or d.out_height)
+        out, surf4 = surfaces(bh, bw, 4)
+        surf3 = (_lib.Surface * n)()
+        for i in range(n):
+            surf3[i].pixels, surf3[i].pitch = out[i].data_ptr(), bw * 6
+        keep_out.append(out)
+
+        def sdr(sc=sc, surf=surf4):
+            _lib.check(_lib.lib.heifgpu_render_batch_scaled_color(ctx._h, imgs, n, planes, None, None, _lib.PIX_RGBA16, sc, xf,
+                                                                  surf, stream))
+
+        def hdr(fmt, surf, enc, sc=sc):
+            def run():
+                _lib.check(_lib.lib.heifgpu_render_batch_gain_scaled(ctx._h, imgs, n, planes, gimgs, gplanes, None, None, fmt,
+                                                                     sc, gxf[enc], surf, stream))
+            return run
+
+        # bytes: the window's luma and chroma (1.5 per pixel), for HDR its quarter-size map (0.25), and the output
+        variants += [(name, "scaled_sdr_rgba16", sdr, n * (window_px * 1.5 + bw * bh * 8)),
+                     (name, "scaled_hdr_rgba16f", hdr(_lib.PIX_HDR_RGBA16F, surf4, "linear"), n * (window_px * 1.75 + bw * bh * 8)),
+                     (name, "scaled_hdr_rgb16pq", hdr(_lib.PIX_HDR_RGB16PQ, surf3, "pq"), n * (window_px * 1.75 + bw * bh * 6))]
+    result = {"images": n, "width": W, "height": HGT, "gain_width": gi.width, "gain_height": gi.height, "reps": args.reps,
+              "runs": args.runs, "device": torch.cuda.get_device_name(0), "hbm_peak_GBps": HBM_PEAK_GBS,
+              "library": _lib.LIB_PATH.name, "transform": "Display P3 profile (halfmoonbay) -> sRGB; Apple rule, headroom 4",
+              "cases": {}}
+    for *_, fn, _ in variants:  # warm-up (and the tables' one upload)
+        fn()
+    torch.cuda.synchronize()
+    ms = {(name, kind): [] for name, kind, _, _ in variants}
+    for _ in range(args.runs):
+        for name, kind, fn, _ in variants:
+            ms[(name, kind)].append(timed(fn, args.reps))
+    for name, kind, _, nbytes in variants:
+        r = summary(ms[(name, kind)], nbytes)
+        r["spread_ms"] = round(r["ms_max"] - r["ms_min"], 4)
+        result["cases"].setdefault(name, {})[kind] = r
+    full = result["cases"]["full"]
+    for name, r in result["cases"].items():
+        if name == "full":
+            continue
+        for enc in ("rgba16f", "rgb16pq"):
+            r[f"hdr_{enc}_over_sdr"] = round(r[f"scaled_hdr_{enc}"]["ms_min"] / r["scaled_sdr_rgba16"]["ms_min"], 4)
+            r[f"hdr_{enc}_of_full_hdr"] = round(r[f"scaled_hdr_{enc}"]["ms_min"] / full[f"full_hdr_{enc}"]["ms_min"], 4)
+    for name, r in result["cases"].items():
+        print(f"{name}: " + ", ".join(f"{k} min {v['ms_min']:.3f} ms (spread {v['spread_ms']:.3f})" for k, v in r.items()
+                                      if isinstance(v, dict)) +
+              "".join(f", {k} {v}" for k, v in r.items() if not isinstance(v, dict)), flush=True)
+    print(json.dumps(result))
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=128)
@@ -831,6 +950,8 @@ def main():
                     help="measure the render, scaled and filtered calls with chroma upsampling set, beside replicate")
     ap.add_argument("--gain", action="store_true", help="measure the gain-map HDR render (see above)")
     args = ap.parse_args()
+    if args.gain and args.scaled:
+        return gain_scaled_main(args)
     if args.gain:
         return gain_main(args)
     if args.chroma:
