@@ -24,9 +24,12 @@ __global__ void __launch_bounds__(256) k_gather_tiles(GatherArgs g) {
     if (c >= g.planes || k >= g.n_tiles) return;
     const int sx = c ? g.sx : 0, sy = c ? g.sy : 0;  // chroma subsampling (log2)
     const int pw = (g.W + (1 << sx) - 1) >> sx, ph = (g.H + (1 << sy) - 1) >> sy;
-    const int x0 = ((k % g.cols) * g.tw) >> sx, y0 = ((k / g.cols) * g.th) >> sy;
+    const int tx = (k % g.cols) * g.tw, ty = (k / g.cols) * g.th;  // the tile's luma origin
+    const int x0 = tx >> sx, y0 = ty >> sy;
     if (x0 >= pw || y0 >= ph) return;  // a tile wholly inside the crop
-    const int w = min(g.tw >> sx, pw - x0), h = min(g.th >> sy, ph - y0);
+    // the window ends where the tile does, rounded up as the plane's size is: an image
+    // without a grid is one tile of the picture's size, which may be odd
+    const int w = min((tx + g.tw + (1 << sx) - 1) >> sx, pw) - x0, h = min((ty + g.th + (1 << sy) - 1) >> sy, ph) - y0;
     const int y = (int)blockIdx.x * 4 + (int)threadIdx.y;
     if (y >= h) return;
     const size_t wb = (size_t)w * (size_t)g.bps;

@@ -26,7 +26,8 @@ def coefs(matrix: int, full: bool):
                 cb_g=fx(2 * kb * (1 - kb) / kg * cs), cr_g=fx(2 * kr * (1 - kr) / kg * cs))
 
 
-def ycbcr_to_rgb(y, cb, cr, matrix: int, full: bool, rotation: int, bit_depth: int = 8):
+def unclipped(y, cb, cr, matrix: int, full: bool, bit_depth: int = 8):
+    """(h, w, 3) int64 R, G, B before the clip to 0..255, coded orientation."""
     c = coefs(matrix, full)
     sh = bit_depth - 8
     Y = (y.astype(np.int64) >> sh)
@@ -42,5 +43,9 @@ def ycbcr_to_rgb(y, cb, cr, matrix: int, full: bool, rotation: int, bit_depth: i
     r = (yv + c["cr_r"] * Cr + 32768) >> 16
     g = (yv - c["cb_g"] * Cb - c["cr_g"] * Cr + 32768) >> 16
     b = (yv + c["cb_b"] * Cb + 32768) >> 16
-    rgb = np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
+    return np.stack([r, g, b], axis=-1)
+
+
+def ycbcr_to_rgb(y, cb, cr, matrix: int, full: bool, rotation: int, bit_depth: int = 8):
+    rgb = np.clip(unclipped(y, cb, cr, matrix, full, bit_depth), 0, 255).astype(np.uint8)
     return np.rot90(rgb, k=rotation & 3)
