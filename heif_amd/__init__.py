@@ -870,6 +870,107 @@ class DecodeContext:
                          lambda xf: (f, scales, filt, xf), self._surfaces(res), tone_map)
         return whole if whole is not None else res
 
+    def encode_jpeg(self, pictures, quality: int = 90, subsampling: str = "4:2:0", icc_profiles=None,
+                    restart_mcus: int = 0) -> List[bytes]:
+        """Baseline JPEG files (JFIF, Y Cb Cr) of a batch of RGB pictures, encoded on
+        the device with heifgpu_jpeg_encode_batch: a fixed number of kernel launches
+        for the whole batch, and only the files cross to the host.  pictures is an
+        (N, h, w, 3) uint8 device tensor or a list of (h, w, 3) uint8 device tensors
+        (sizes may differ; rows may be strided, pixels are packed): what render()
+        and render_scaled() return for "rgb8".  quality 1..100 scales the Annex K
+        tables as IJG and Pillow do; subsampling "4:2:0" or "4:4:4"; icc_profiles[i]
+        (bytes or None) goes into picture i's APP2 segments; restart_mcus is the
+        number of MCUs between restart markers (0: one MCU row), the unit the device
+        codes in parallel.  The output buffers are a first guess; a picture that
+        does not fit is encoded once more with the room its size word states.  The
+        call runs on the current stream and waits for it."""
+        torch = self._torch
+        if subsampling not in _lib.JPEG_SUBSAMPLINGS:
+            raise ValueError(f"subsampling {subsampling!r}: one of {sorted(_lib.JPEG_SUBSAMPLINGS)}")
+        pics = list(pictures) if isinstance(pictures, (list, tuple)) else [pictures[i] for i in range(len(pictures))]
+        n = len(pics)
+        if icc_profiles is not None and len(icc_profiles) != n:
+            raise ValueError("icc_profiles must have one entry per picture")
+        for t in pics:
+            if (t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or not t.is_cuda or t.device.index != self.device
+                    or t.stride(2) != 1 or t.stride(1) != 3 or 0 in t.shape):
+                raise ValueError("encode_jpeg takes (h, w, 3) uint8 tensors of this context's device with packed pixels")
+        if n == 0:
+            return []
+        opts = _lib.JpegOpts(int(quality), _lib.JPEG_SUBSAMPLINGS[subsampling], int(restart_mcus), 0)
+        heads = []
+        for i, t in enumerate(pics):
+            icc = (icc_profiles[i] if icc_profiles is not None else None) or b""
+            ln = ctypes.c_size_t()
+            args = (t.shape[1], t.shape[0], ctypes.byref(opts), _lib.u8buf(icc), len(icc))
+            _lib.check(lib.heifgpu_jpeg_header(*args, None, 0, ctypes.byref(ln)))
+            buf = (ctypes.c_uint8 * ln.value)()
+            _lib.check(lib.heifgpu_jpeg_header(*args, buf, ln.value, ctypes.byref(ln)))
+            heads.append(bytes(buf))
+        dev = torch.device("cuda", self.device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        per_px = 0.75 if subsampling == "4:2:0" else 1.25  # bytes: room for quality 90 and some above
+        caps = [min(int(t.shape[0] * t.shape[1] * per_px) + 4096, 2 ** 31 - 16) for t in pics]
+        scans = [None] * n
+        todo = list(range(n))
+        for _ in range(2):  # the guess, then the stated sizes
+            offs, total = [], 0
+            for i in todo:
+                offs.append(total)
+                total += (caps[i] + 15) // 16 * 16
+            out = torch.empty(total, dtype=torch.uint8, device=dev)
+            sizes = torch.empty(len(todo), dtype=torch.int64, device=dev)
+            src = self._surfaces([pics[i] for i in todo])
+            dst = (_lib.Surface * len(todo))()
+            for k, i in enumerate(todo):
+                dst[k].pixels = out.data_ptr() + offs[k]
+                dst[k].pitch = caps[i]
+            ws = (ctypes.c_uint32 * len(todo))(*[pics[i].shape[1] for i in todo])
+            hs = (ctypes.c_uint32 * len(todo))(*[pics[i].shape[0] for i in todo])
+            _lib.check(lib.heifgpu_jpeg_encode_batch(self._h, len(todo), src, ws, hs, ctypes.byref(opts), dst,
+                                                     ctypes.cast(sizes.data_ptr(), ctypes.POINTER(ctypes.c_uint64)), stream))
+            got = [int(v) & (2 ** 64 - 1) for v in sizes.cpu().tolist()]  # (the copy waits for the kernels)
+            again = []
+            for k, i in enumerate(todo):
+                size = got[k] & ~_lib.JPEG_TOO_SMALL
+                if got[k] & _lib.JPEG_TOO_SMALL:
+                    caps[i] = size
+                    again.append(i)
+                else:
+                    scans[i] = bytes(out[offs[k]:offs[k] + size].cpu().numpy())
+            todo = again
+            if not todo:
+                break
+        if todo:
+            raise HeifGpuError(_lib.HEIFGPU_E_DEVICE, "encode_jpeg: a picture did not fit the size the device stated")
+        return [h + s for h, s in zip(heads, scans)]
+
+    def render_jpeg(self, outs: Sequence[DecodedImage], size=None, mode: str = "cover", windows=None,
+                    filter: str = "area", colorspace: Optional[str] = None, tone_map: Optional[str] = None,
+                    quality: int = 90, subsampling: str = "4:2:0", embed_icc: bool = True, icc_profiles=None,
+                    restart_mcus: int = 0) -> List[bytes]:
+        """The JPEG files of a batch of decoded images: render() (render_scaled() when
+        size or windows is given; windows need a size) as "rgb8", then encode_jpeg(),
+        all on the device.  JPEG has no alpha: the pictures are rendered opaque.
+        With colorspace None and embed_icc, each item's own ICC profile
+        (HeifImage.icc_profile, when it has one) is embedded, which is what makes a
+        Display P3 picture look right in a viewer; an nclx-only item gets none.  With
+        colorspace "srgb" nothing is embedded (an untagged JPEG is taken as sRGB).
+        With "display-p3" nothing is embedded either, so most viewers will show the
+        picture as sRGB, unless the caller passes icc_profiles (one profile or None
+        per image, embedded as given whatever the colorspace): this library reads
+        ICC profiles and does not write them."""
+        if windows is not None and size is None:
+            raise ValueError("render_jpeg: windows need a size")
+        if size is not None:
+            rgb = self.render_scaled(outs, size, mode, "rgb8", None, windows, colorspace=colorspace, filter=filter,
+                                     tone_map=tone_map)
+        else:
+            rgb = self.render(outs, "rgb8", None, colorspace=colorspace, tone_map=tone_map)
+        if icc_profiles is None and colorspace is None and embed_icc:
+            icc_profiles = [o.image.icc_profile for o in outs]
+        return self.encode_jpeg(rgb, quality, subsampling, icc_profiles, restart_mcus)
+
     def render_tensor(self, outs: Sequence[DecodedImage], size, mode: str = "cover", dtype=None, layout: str = "chw",
                       mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), src: str = "rgb8", windows=None,
                       flips=None, alphas: Optional[Sequence[Optional[DecodedImage]]] = None, scale_bias=None,
@@ -1145,6 +1246,19 @@ class HeicDecoder:
             return ctx.render_scaled([out], size, mode, fmt, alphas, colorspace=colorspace, filter=filter,
                                      tone_map=tone_map)[0]
         return ctx.render([out], fmt, alphas, colorspace=colorspace, tone_map=tone_map)[0]
+
+    @classmethod
+    def decode_jpeg(cls, data: bytes, device: int = 0, size=None, mode: str = "cover", filter: str = "area",
+                    colorspace: Optional[str] = None, tone_map: Optional[str] = None, quality: int = 90,
+                    subsampling: str = "4:2:0", embed_icc: bool = True, icc_profile: Optional[bytes] = None,
+                    restart_mcus: int = 0) -> bytes:
+        """One HEIC file as one baseline JPEG file: decodes the primary image, then
+        DecodeContext.render_jpeg of that one picture (its arguments; icc_profile is
+        render_jpeg's icc_profiles for the one picture)."""
+        DecodeContext._check_tone(colorspace, tone_map)
+        out, _ = cls._decode_pair(data, device, size, mode, "all", False, filter)
+        return cls.context(device).render_jpeg([out], size, mode, None, filter, colorspace, tone_map, quality, subsampling,
+                                               embed_icc, None if icc_profile is None else [icc_profile], restart_mcus)[0]
 
     @classmethod
     def decode_hdr(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, colorspace: str = "display-p3",

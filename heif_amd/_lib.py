@@ -267,6 +267,16 @@ PIX_HDR_RGB16F, PIX_HDR_RGBA16F, PIX_HDR_RGB16PQ, PIX_HDR_RGBA16PQ = 4, 5, 6, 7
 HDR_FORMATS = {"rgb16f": PIX_HDR_RGB16F, "rgba16f": PIX_HDR_RGBA16F, "rgb16pq": PIX_HDR_RGB16PQ,
                "rgba16pq": PIX_HDR_RGBA16PQ}
 
+class JpegOpts(ctypes.Structure):
+    """heifgpu_jpeg_opts: quality 1..100, JPEG_444 / JPEG_420, MCUs per restart interval (0: a row)."""
+    _fields_ = [("quality", ctypes.c_uint32), ("subsampling", ctypes.c_uint32), ("restart_mcus", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+JPEG_444, JPEG_420 = 0, 1
+JPEG_SUBSAMPLINGS = {"4:4:4": JPEG_444, "4:2:0": JPEG_420}
+JPEG_TOO_SMALL = 1 << 63  # a bit of heifgpu_jpeg_encode_batch's sizes
+
 PARSE_AUTO, PARSE_LANES, PARSE_SOLO, PARSE_SPREAD = 0, 1, 2, 3
 PARSE_ROWS = 4  # ABI 5 only; removed in ABI 6 (prepare answers HEIFGPU_E_UNSUPPORTED)
 PARSE_MODES = {"auto": PARSE_AUTO, "lanes": PARSE_LANES, "solo": PARSE_SOLO, "spread": PARSE_SPREAD}
@@ -295,6 +305,7 @@ EXPORTS = (
     "heifgpu_image_get_chroma", "heifgpu_image_set_chroma_upsampling", "heifgpu_chroma_upsample",
     "heifgpu_image_get_gain", "heifgpu_gain_transform_make", "heifgpu_gain_apply", "heifgpu_gain_sample",
     "heifgpu_render_batch_gain", "heifgpu_render_batch_gain_scaled", "heifgpu_gain_average",
+    "heifgpu_jpeg_quant_tables", "heifgpu_jpeg_header", "heifgpu_jpeg_encode_host", "heifgpu_jpeg_encode_batch",
 )
 
 
@@ -410,6 +421,11 @@ def _load() -> ctypes.CDLL:
         "heifgpu_render_batch_gain_scaled": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), P(VP), P(Planes), U32,
                                                    P(Scale), P(VP), P(Surface), VP]),
         "heifgpu_gain_average": (I32, [P(U32), U32, U32, P(Scale), P(U32)]),
+        "heifgpu_jpeg_quant_tables": (I32, [U32, u8p, u8p]),
+        "heifgpu_jpeg_header": (I32, [U32, U32, P(JpegOpts), u8p, SZ, u8p, SZ, P(SZ)]),
+        "heifgpu_jpeg_encode_host": (I32, [VP, ctypes.c_int32, U32, U32, P(JpegOpts), u8p, SZ, u8p, SZ, P(SZ)]),
+        "heifgpu_jpeg_encode_batch": (I32, [VP, SZ, P(Surface), P(U32), P(U32), P(JpegOpts), P(Surface),
+                                            P(ctypes.c_uint64), VP]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     # (and no window decode: DecodeContext.prepare without windows then goes through prepare_ex)
@@ -429,7 +445,10 @@ def _load() -> ctypes.CDLL:
                 "heifgpu_image_get_gain", "heifgpu_gain_transform_make", "heifgpu_gain_apply", "heifgpu_gain_sample",
                 "heifgpu_render_batch_gain",
                 # its scaled form (render_hdr_scaled / decode_hdr(size=) then need a build that has it)
-                "heifgpu_render_batch_gain_scaled", "heifgpu_gain_average"}
+                "heifgpu_render_batch_gain_scaled", "heifgpu_gain_average",
+                # the JPEG output (encode_jpeg / render_jpeg / decode_jpeg then need a build that has it)
+                "heifgpu_jpeg_quant_tables", "heifgpu_jpeg_header", "heifgpu_jpeg_encode_host",
+                "heifgpu_jpeg_encode_batch"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue

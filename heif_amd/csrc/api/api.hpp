@@ -1,6 +1,6 @@
 // api.hpp — what the units of the C ABI layer (include/heifgpu.h) share: the two
 // opaque handles every unit looks into, the error message, and the device and
-// pinned buffers.  image.cpp, gain.cpp, context.cpp, render.cpp and batch.cpp hold the calls.
+// pinned buffers.  image.cpp, gain.cpp, context.cpp, render.cpp, jpeg.cpp and batch.cpp hold the calls.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,7 @@ struct heifgpu_image {
 constexpr int kTimingSlots = 32;
 struct RenderRing;  // the render calls' descriptor staging
 struct ColorCache;  // the colour-managed renders' tables on the device
+struct JpegState;   // the JPEG encoder's scratch and descriptor staging
 struct heifgpu_ctx {
     int device = 0;
     bool timing = false;
@@ -40,6 +41,8 @@ struct heifgpu_ctx {
     // render.cpp's, opaque here; heifgpu_destroy frees them with render_state_free
     RenderRing *render = nullptr;  // created by the first render call
     ColorCache *color = nullptr;   // created by the first colour-managed render
+    // jpeg.cpp's, opaque here; heifgpu_destroy frees it with jpeg_state_free
+    JpegState *jpeg = nullptr;     // created by the first heifgpu_jpeg_encode_batch
 };
 
 namespace hg {
@@ -122,5 +125,7 @@ inline Rect rect_of(const heifgpu_rect &r) { return Rect{r.x, r.y, r.width, r.he
 hipError_t fold_timing(heifgpu_ctx *ctx, int slot);
 // deletes ctx->render and ctx->color (render.cpp, which alone knows their layouts)
 void render_state_free(heifgpu_ctx *ctx);
+// deletes ctx->jpeg (jpeg.cpp)
+void jpeg_state_free(heifgpu_ctx *ctx);
 
 }  // namespace hg

@@ -90,6 +90,7 @@ void heifgpu_destroy(heifgpu_ctx *ctx) {
     if (ctx->upload) (void)hipStreamDestroy(ctx->upload);
     if (ctx->prep) (void)hipStreamDestroy(ctx->prep);
     render_state_free(ctx);
+    jpeg_state_free(ctx);
     delete ctx;
 }
 

@@ -846,6 +846,51 @@ int heifgpu_render_batch_gain_scaled(heifgpu_ctx *ctx, const heifgpu_image *cons
  * Runs the kernel's own accumulation and quotient. */
 int heifgpu_gain_average(const uint32_t *g_q8, uint32_t w, uint32_t h, const heifgpu_scale *scale, uint32_t *out);
 
+/* ---- JPEG output: RGB8 surfaces to baseline JPEG files on the device --------
+ * (added within ABI 6: new entry points only.)
+ * The input is what the renders write for HEIFGPU_PIX_RGB8 (R, G, B interleaved, a pitch in
+ * bytes, any alignment), so every render option composes with it.  The file is baseline
+ * sequential JPEG (SOF0), JFIF, Y Cb Cr (BT.601 full range) at 4:4:4 or 4:2:0, the Annex K
+ * tables scaled by `quality` as IJG and Pillow scale them, the Huffman tables of K.3, and a
+ * restart marker every `restart_mcus` MCUs (0: every MCU row; at most 65535).  Its bytes are
+ * fully determined by the pixels and the options: heif_amd/csrc/kernels/jpeg.hpp states the
+ * arithmetic, heifgpu_jpeg_encode_host restates the whole encoder on the host.
+ * A file is heifgpu_jpeg_header's bytes followed by what heifgpu_jpeg_encode_batch writes (the
+ * scan and EOI).  quality outside 1..100, a zero side, a side above 65535, a pitch below
+ * 3 * width, a profile above 255 * 65519 bytes or n above 65535 is HEIFGPU_E_INVALID, reported
+ * before anything is launched or written. */
+#define HEIFGPU_JPEG_444 0u
+#define HEIFGPU_JPEG_420 1u
+typedef struct {
+    uint32_t quality;      /* 1..100 */
+    uint32_t subsampling;  /* HEIFGPU_JPEG_444 or HEIFGPU_JPEG_420 */
+    uint32_t restart_mcus; /* MCUs per restart interval; 0: one MCU row */
+    uint32_t reserved;     /* 0 */
+} heifgpu_jpeg_opts;
+/* host only: the two quantisation tables of `quality` in natural (row-major) order */
+int heifgpu_jpeg_quant_tables(uint32_t quality, uint8_t luma[64], uint8_t chroma[64]);
+/* host only: the bytes before the scan (SOI, APP0, APP2 with the ICC profile in chunks when
+ * icc_len > 0, DQT, SOF0, DHT, DRI, SOS) of a width x height picture.  *len receives their
+ * length; they are written when buf is not NULL and cap >= *len. */
+int heifgpu_jpeg_header(uint32_t width, uint32_t height, const heifgpu_jpeg_opts *opts, const uint8_t *icc,
+                        size_t icc_len, uint8_t *buf, size_t cap, size_t *len);
+/* host only: the whole file of one picture in host memory, by the kernels' own arithmetic;
+ * *len and buf as above. */
+int heifgpu_jpeg_encode_host(const uint8_t *rgb, int32_t pitch, uint32_t width, uint32_t height,
+                             const heifgpu_jpeg_opts *opts, const uint8_t *icc, size_t icc_len, uint8_t *buf,
+                             size_t cap, size_t *len);
+/* Asynchronous on `stream`: the scan and EOI of n pictures (sizes may differ; one set of options)
+ * in a fixed number of launches.  out[i].pixels receives picture i's bytes, out[i].pitch is its
+ * capacity in bytes.  sizes (n entries, device memory or pinned host memory the device can
+ * write) receives the exact length of every picture's scan and EOI; when that exceeds the
+ * capacity, bit 63 of sizes[i] is set as well, nothing at or past the capacity is written and
+ * what was written is to be discarded: the caller encodes that picture again with room for
+ * the stated length.  The call's scratch belongs to the context: a call waits on the host for
+ * the context's previous encode call to finish. */
+int heifgpu_jpeg_encode_batch(heifgpu_ctx *ctx, size_t n, const heifgpu_surface *rgb, const uint32_t *width,
+                              const uint32_t *height, const heifgpu_jpeg_opts *opts, const heifgpu_surface *out,
+                              uint64_t *sizes, void *stream);
+
 /* ---- window decode: decode only the pictures a window reads ----------------
  * (added within ABI 6: new entry points only; heifgpu_batch_opts keeps its layout.)
  * A render of a window of the displayed picture (heifgpu_scale's x, y, width,

@@ -101,7 +101,7 @@ one process in each of the --runs runs:
 Min and spread (max - min over runs) are reported; nothing is gated.
 
 usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json]
-                                    [--scaled | --tensor | --color | --filter | --tone | --chroma bilinear | --gain [--scaled]]
+                                    [--scaled | --tensor | --color | --filter | --tone | --chroma bilinear | --gain [--scaled] | --jpeg]
 """
 import argparse
 import ctypes
@@ -935,6 +935,99 @@ def gain_scaled_main(args):
         pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
 
 
+def jpeg_main(args):
+    """--jpeg: n copies of the golden twelve-megapixel picture to JPEG files in host memory
+    (quality 90, 4:2:0).  "device": render() then encode_jpeg(), the files copied to the host;
+    "pillow": render(), every surface copied to the host, Pillow's save() at the same settings,
+    one picture after another on one core.  Wall-clock time per batch.  Beside them the encode
+    call alone (events around heifgpu_jpeg_encode_batch, buffers allocated beforehand) for a
+    restart interval of one MCU row and of 16 MCUs, which is what the default was chosen by."""
+    import io
+    import time
+
+    from PIL import Image
+
+    n = args.images
+    ctx = H.DecodeContext(0)
+    golden = (ROOT / "tests" / "golden" / "halfmoonbay.heic").read_bytes()
+    out = H.HeicDecoder.decode(golden)
+    outs = [out] * n
+    d = out.image.display
+    result = {"images": n, "width": d.out_width, "height": d.out_height, "quality": 90, "subsampling": "4:2:0",
+              "reps": args.reps, "runs": args.runs, "device": torch.cuda.get_device_name(0)}
+
+    def wall(fn, reps):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3 / reps
+
+    files = {}
+
+    def device_route(restart):
+        def run():
+            files[restart] = ctx.encode_jpeg(ctx.render(outs, "rgb8"), 90, "4:2:0", restart_mcus=restart)
+        return run
+
+    def pillow_route():
+        res = []
+        for t in ctx.render(outs, "rgb8"):
+            b = io.BytesIO()
+            Image.fromarray(t.cpu().numpy()).save(b, "JPEG", quality=90, subsampling="4:2:0")
+            res.append(b.getvalue())
+        files["pillow"] = res
+
+    def render_only():
+        ctx.render(outs, "rgb8")
+
+    # the encode call alone
+    rgb = ctx.render(outs, "rgb8")
+    cap = d.out_width * d.out_height
+    buf = torch.empty((n, cap), dtype=torch.uint8, device="cuda:0")
+    sizes = torch.empty(n, dtype=torch.int64, device="cuda:0")
+    src, dst = ctx._surfaces(rgb), (_lib.Surface * n)()
+    for i in range(n):
+        dst[i].pixels, dst[i].pitch = buf[i].data_ptr(), cap
+    ws, hs = (ctypes.c_uint32 * n)(*[d.out_width] * n), (ctypes.c_uint32 * n)(*[d.out_height] * n)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+
+    def call_of(restart):
+        o = _lib.JpegOpts(90, _lib.JPEG_420, restart, 0)
+        return lambda: _lib.check(_lib.lib.heifgpu_jpeg_encode_batch(
+            ctx._h, n, src, ws, hs, ctypes.byref(o), dst, ctypes.cast(sizes.data_ptr(), ctypes.POINTER(ctypes.c_uint64)), stream))
+
+    result["encode_call"] = {}
+    for restart in (0, 16):
+        fn = call_of(restart)
+        fn()
+        torch.cuda.synchronize()
+        ms = [timed(fn, args.reps) for _ in range(args.runs)]
+        total = int(sizes.sum().item())
+        result["encode_call"][f"restart_{restart}"] = {
+            "ms_per_batch": round(statistics.median(ms), 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+            "scan_bytes_per_picture": total // n}
+        print(f"encode call, restart_mcus {restart}: {statistics.median(ms):.3f} ms per batch of {n} "
+              f"(min {min(ms):.3f}, max {max(ms):.3f}), {total // n} scan bytes per picture", flush=True)
+    del buf, rgb
+    for name, fn, reps in (("render", render_only, args.reps), ("device_row", device_route(0), 2),
+                           ("device_16", device_route(16), 2), ("pillow", pillow_route, 1)):
+        fn()
+        ms = [wall(fn, reps) for _ in range(min(args.runs, 3) if name != "pillow" else 1)]
+        result[name] = {"ms_per_batch": round(statistics.median(ms), 2), "ms_min": round(min(ms), 2),
+                        "ms_max": round(max(ms), 2), "ms_per_picture": round(statistics.median(ms) / n, 3)}
+        print(f"{name}: {statistics.median(ms):.2f} ms per batch of {n}, {statistics.median(ms) / n:.3f} ms per picture",
+              flush=True)
+    result["file_bytes_per_picture"] = {k: sum(len(f) for f in v) // n for k, v in files.items()}
+    result["pillow_over_device_row"] = round(result["pillow"]["ms_per_batch"] / result["device_row"]["ms_per_batch"], 2)
+    result["pillow_over_device_16"] = round(result["pillow"]["ms_per_batch"] / result["device_16"]["ms_per_batch"], 2)
+    print(json.dumps(result))
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=128)
@@ -949,7 +1042,10 @@ def main():
     ap.add_argument("--chroma", choices=("replicate", "bilinear"), default=None,
                     help="measure the render, scaled and filtered calls with chroma upsampling set, beside replicate")
     ap.add_argument("--gain", action="store_true", help="measure the gain-map HDR render (see above)")
+    ap.add_argument("--jpeg", action="store_true", help="measure render + encode_jpeg against render + copy + Pillow")
     args = ap.parse_args()
+    if args.jpeg:
+        return jpeg_main(args)
     if args.gain and args.scaled:
         return gain_scaled_main(args)
     if args.gain:
