@@ -645,21 +645,8 @@ class DecodeContext:
         decoded for a window, or set to bilinear chroma, are refused (UnsupportedError)
         before anything is launched."""
         torch = self._torch
-        if fmt not in _lib.HDR_FORMATS:
-            raise ValueError(f"fmt {fmt!r}: one of {sorted(_lib.HDR_FORMATS)}")
-        f = _lib.HDR_FORMATS[fmt]
-        ch, pq = (4 if f & 1 else 3), f >= _lib.PIX_HDR_RGB16PQ
-        self._check_images("render_hdr", outs, alphas, gains=gains, transforms=transforms, out=out)
-        if any(g is None or g.image is None for g in gains):
-            raise ValueError("render_hdr needs gain images that carry their HeifImage (alloc_outputs)")
-        for i, o in enumerate(outs):
-            for name, im in (("image", o), ("gain image", gains[i]), ("alpha image", alphas[i] if alphas is not None else None)):
-                if im is not None and im.valid is not None:
-                    raise UnsupportedError(_lib.HEIFGPU_E_UNSUPPORTED,
-                                           f"render_hdr: {name} {i} was decoded for a window ({im.valid}) only")
-        if transforms is None:
-            transforms = [o.image.gain_transform(g.image, colorspace, "pq" if pq else "linear", pq_bits, headroom,
-                                                 display_headroom, sdr_white) for o, g in zip(outs, gains)]
+        f, ch, pq, transforms = self._hdr_args("render_hdr", outs, gains, fmt, alphas, transforms,
+                                               (colorspace, pq_bits, headroom, display_headroom, sdr_white), out=out)
         dev = torch.device("cuda", self.device)
         dtype = torch.uint16 if pq else torch.float16
         res = out if out is not None else [
@@ -694,23 +681,11 @@ class DecodeContext:
         write into, which are then returned as a list."""
         torch = self._torch
         n = len(outs)
-        if fmt not in _lib.HDR_FORMATS:
-            raise ValueError(f"fmt {fmt!r}: one of {sorted(_lib.HDR_FORMATS)}")
-        if mode not in _lib.FIT_MODES:
+        if fmt in _lib.HDR_FORMATS and mode not in _lib.FIT_MODES:  # (a bad fmt answers first, in _hdr_args)
             raise ValueError(f"mode {mode!r}: one of {sorted(_lib.FIT_MODES)}")
-        f = _lib.HDR_FORMATS[fmt]
-        ch, pq = (4 if f & 1 else 3), f >= _lib.PIX_HDR_RGB16PQ
-        self._check_images("render_hdr_scaled", outs, alphas, gains=gains, transforms=transforms, windows=windows, out=out)
-        if any(g is None or g.image is None for g in gains):
-            raise ValueError("render_hdr_scaled needs gain images that carry their HeifImage (alloc_outputs)")
-        for i, o in enumerate(outs):
-            for name, im in (("image", o), ("gain image", gains[i]), ("alpha image", alphas[i] if alphas is not None else None)):
-                if im is not None and im.valid is not None:
-                    raise UnsupportedError(_lib.HEIFGPU_E_UNSUPPORTED,
-                                           f"render_hdr_scaled: {name} {i} was decoded for a window ({im.valid}) only")
-        if transforms is None:
-            transforms = [o.image.gain_transform(g.image, colorspace, "pq" if pq else "linear", pq_bits, headroom,
-                                                 display_headroom, sdr_white) for o, g in zip(outs, gains)]
+        f, ch, pq, transforms = self._hdr_args("render_hdr_scaled", outs, gains, fmt, alphas, transforms,
+                                               (colorspace, pq_bits, headroom, display_headroom, sdr_white),
+                                               windows=windows, out=out)
         bh, bw, scales = self._scales("render_hdr_scaled", outs, alphas, size, mode, windows)
         whole, res = self._scaled_outputs(n, scales, (bh, bw) if windows is not None or mode != "contain" else None,
                                           lambda h, w: (h, w, ch), torch.uint16 if pq else torch.float16) \
@@ -725,6 +700,28 @@ class DecodeContext:
                                                             DecodeContext.planes_of(gains), aimgs, aplanes, f, scales, xf,
                                                             self._surfaces(res), ctypes.c_void_p(stream)))
         return whole if whole is not None else res
+
+    def _hdr_args(self, what, outs, gains, fmt, alphas, transforms, make, **more):
+        """What render_hdr and render_hdr_scaled (`what`) do alike before anything else: fmt
+        as (f, channels, pq), the checks of the images, and the transforms, made here from
+        make = (colorspace, pq_bits, headroom, display_headroom, sdr_white) when none are given."""
+        if fmt not in _lib.HDR_FORMATS:
+            raise ValueError(f"fmt {fmt!r}: one of {sorted(_lib.HDR_FORMATS)}")
+        f = _lib.HDR_FORMATS[fmt]
+        ch, pq = (4 if f & 1 else 3), f >= _lib.PIX_HDR_RGB16PQ
+        self._check_images(what, outs, alphas, gains=gains, transforms=transforms, **more)
+        if any(g is None or g.image is None for g in gains):
+            raise ValueError(f"{what} needs gain images that carry their HeifImage (alloc_outputs)")
+        for i, o in enumerate(outs):
+            for name, im in (("image", o), ("gain image", gains[i]), ("alpha image", alphas[i] if alphas is not None else None)):
+                if im is not None and im.valid is not None:
+                    raise UnsupportedError(_lib.HEIFGPU_E_UNSUPPORTED,
+                                           f"{what}: {name} {i} was decoded for a window ({im.valid}) only")
+        if transforms is None:
+            colorspace, pq_bits, headroom, display_headroom, sdr_white = make
+            transforms = [o.image.gain_transform(g.image, colorspace, "pq" if pq else "linear", pq_bits, headroom,
+                                                 display_headroom, sdr_white) for o, g in zip(outs, gains)]
+        return f, ch, pq, transforms
 
     @staticmethod
     def _check_tone(colorspace, tone_map):

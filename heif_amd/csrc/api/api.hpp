@@ -20,7 +20,7 @@ struct heifgpu_image {
 
 constexpr int kTimingSlots = 32;
 struct RenderRing;  // the render calls' descriptor staging
-struct ColorCache;  // the colour-managed renders' tables on the device
+struct ColorCache;  // the tables of the colour, tone and gain transforms on the device
 struct JpegState;   // the JPEG encoder's scratch and descriptor staging
 struct heifgpu_ctx {
     int device = 0;
@@ -40,7 +40,7 @@ struct heifgpu_ctx {
     double acc[6] = {};
     // render.cpp's, opaque here; heifgpu_destroy frees them with render_state_free
     RenderRing *render = nullptr;  // created by the first render call
-    ColorCache *color = nullptr;   // created by the first colour-managed render
+    ColorCache *color = nullptr;   // created by the first render that has a table to upload
     // jpeg.cpp's, opaque here; heifgpu_destroy frees it with jpeg_state_free
     JpegState *jpeg = nullptr;     // created by the first heifgpu_jpeg_encode_batch
 };

@@ -1,10 +1,13 @@
 // render.cpp — the render family of the C ABI: heifgpu_render_batch, _scaled and _tensor
 // with their _color forms, heifgpu_scale_fit, and the filtered (bilinear / bicubic) forms
 // of the scaled and tensor renders with their host hooks, and the gain-map HDR render at
-// full size and scaled.  Each call checks its arguments and fills its descriptors;
-// render_submit sends any of the descriptor types (gain_submit those of the HDR renders).
+// full size and scaled.  Each call begins with call_check, checks its arguments and fills its
+// descriptors, all without the context; submit then sends any of the descriptor types with the
+// blocks that follow them (render_submit: the ColorRefs and ChromaUps; gain_submit: the GainRefs),
+// their tables out of the one ColorCache.
 // (The calls take their C linkage from the declarations of include/heifgpu.h.)
 #include <cmath>
+#include <initializer_list>
 #include <memory>
 #include <vector>
 
@@ -25,7 +28,7 @@ constexpr int kRenderSlots = 4;
 struct RenderRing {
     struct Slot {
         PinnedBuf host;
-        DevBuf<uint8_t> dev;  // n descriptors of the call's type, then its ColorRefs, then its ChromaRefs
+        DevBuf<uint8_t> dev;  // n descriptors of the call's type, then its trailing blocks (submit)
         hipEvent_t done = nullptr;
         bool pending = false;
     } slot[kRenderSlots];
@@ -38,11 +41,11 @@ struct RenderRing {
 
 // The tables of the transforms on the device, keyed by content: in_lut[3][1 << B] then
 // out_lut as 4096 pairs (xf_out_pair), as ColorRef::lut addresses them; for a tone transform
-// in_lut32[3][1 << B], the same pairs and a ToneBlock (another size: the two kinds never compare
-// equal).  An entry is written once, by a blocking
-// copy before the call that first uses it launches anything, and never again, so no
-// launch in flight can see a table change; a steady-state call finds its tables here.
-// When kColorCacheMax tables are held the cache is emptied after a device synchronise.
+// in_lut32[3][1 << B], the same pairs and a ToneBlock (another size), for a gain transform
+// gain_table_image's, which ends in a tag: keys of two kinds never compare equal.  An entry is
+// written once, by a blocking copy before the call that first uses it launches anything, and
+// never again, so no launch in flight can see a table change; a steady-state call finds its
+// tables here.
 constexpr size_t kColorCacheMax = 256;
 struct ColorCache {
     struct Entry {
@@ -50,6 +53,26 @@ struct ColorCache {
         uint16_t *dev = nullptr;
     };
     std::vector<Entry> entries;
+    // lut: where the table with this content lies on the device, uploaded now if it is new
+    // (what: "colour" or "gain", for the message of an upload that fails)
+    int table(const std::vector<uint16_t> &key, const char *what, uint64_t &lut) {
+        for (const Entry &e : entries)
+            if (e.key == key) {
+                lut = reinterpret_cast<uint64_t>(e.dev);
+                return HEIFGPU_OK;
+            }
+        Entry e;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e.dev), key.size() * 2));
+        const hipError_t up = hipMemcpy(e.dev, key.data(), key.size() * 2, hipMemcpyHostToDevice);  // blocking
+        if (up != hipSuccess) {
+            (void)hipFree(e.dev);
+            return fail(HEIFGPU_E_DEVICE, std::string(what) + " table upload: " + hipGetErrorString(up));
+        }
+        lut = reinterpret_cast<uint64_t>(e.dev);
+        e.key = key;
+        entries.push_back(std::move(e));
+        return HEIFGPU_OK;
+    }
     void clear() {
         for (Entry &e : entries)
             if (e.dev) (void)hipFree(e.dev);
@@ -58,9 +81,32 @@ struct ColorCache {
     ~ColorCache() { clear(); }
 };
 
+// The context's cache for the tables of one call, made by the first call that needs it.  When it
+// holds kColorCacheMax tables it is emptied, here and so once per call (a call may go past the
+// limit by its own tables, and none of them is freed under it), after a device synchronise:
+// nothing in flight reads a table that is freed.
+static int color_cache_open(heifgpu_ctx *ctx, ColorCache *&cache) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->color) ctx->color = new ColorCache;
+    cache = ctx->color;
+    if (cache->entries.size() >= kColorCacheMax) {
+        HIP_TRY(hipDeviceSynchronize());
+        cache->clear();
+    }
+    return HEIFGPU_OK;
+}
+
 void hg::render_state_free(heifgpu_ctx *ctx) {
     delete ctx->render;
     delete ctx->color;
+}
+
+// the 4096 words out_lut[k] | out_lut[k + 1] << 16 of a colour table's image (xf_out_pair), at dst
+static void out_pairs_write(const uint16_t *out_lut, void *dst) {
+    for (int k = 0; k < kXfPairEntries; ++k) {
+        const uint32_t w = xf_out_pair(out_lut, k);
+        std::memcpy(static_cast<uint8_t *>(dst) + 4 * k, &w, 4);
+    }
 }
 
 // The device image of a tone transform (t->tone != 0: the first member of a
@@ -71,10 +117,7 @@ static void tone_table_image(const heifgpu_color_transform *t, std::vector<uint1
     const size_t off = 4 * (3 * tn + kXfPairEntries);  // bytes: a multiple of 8
     std::vector<uint8_t> img(off + sizeof(ToneBlock));
     for (int c = 0; c < 3; ++c) std::memcpy(img.data() + 4 * c * tn, h.in_lut32[c], 4 * tn);
-    for (int k = 0; k < kXfPairEntries; ++k) {
-        const uint32_t w = xf_out_pair(t->out_lut, k);
-        std::memcpy(img.data() + 4 * (3 * tn + k), &w, 4);
-    }
+    out_pairs_write(t->out_lut, img.data() + 4 * 3 * tn);
     ToneBlock tb{};
     for (int c = 0; c < 3; ++c) tb.w[c] = h.w[c];
     for (int k = 0; k < kXfTonePairs; ++k) tb.pairs[2 * k] = h.T[k], tb.pairs[2 * k + 1] = h.T[k + 1];
@@ -108,13 +151,8 @@ static int color_refs_fill(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, s
         any = any || !t->identity;
     }
     if (!any) return HEIFGPU_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->color) ctx->color = new ColorCache;
-    ColorCache &cache = *ctx->color;
-    if (cache.entries.size() >= kColorCacheMax) {  // (checked once per call: a call may go past it by its own tables)
-        HIP_TRY(hipDeviceSynchronize());  // nothing in flight reads a table that is freed
-        cache.clear();
-    }
+    ColorCache *cache = nullptr;
+    if (int rc = color_cache_open(ctx, cache)) return rc;
     refs.assign(n, ColorRef{});
     std::vector<uint16_t> key;
     for (size_t i = 0; i < n; ++i) {
@@ -128,33 +166,29 @@ static int color_refs_fill(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, s
         } else {
             key.resize(3 * tn + 2 * kXfPairEntries);
             for (int c = 0; c < 3; ++c) std::memcpy(key.data() + c * tn, t->in_lut[c], tn * 2);
-            for (int k = 0; k < kXfPairEntries; ++k) {
-                const uint32_t w = xf_out_pair(t->out_lut, k);
-                std::memcpy(key.data() + 3 * tn + 2 * k, &w, 4);
-            }
+            out_pairs_write(t->out_lut, key.data() + 3 * tn);
         }
-        ColorCache::Entry *hit = nullptr;
-        for (ColorCache::Entry &e : cache.entries)
-            if (e.key == key) hit = &e;
-        if (!hit) {
-            ColorCache::Entry e;
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e.dev), key.size() * 2));
-            const hipError_t up = hipMemcpy(e.dev, key.data(), key.size() * 2, hipMemcpyHostToDevice);  // blocking
-            if (up != hipSuccess) {
-                (void)hipFree(e.dev);
-                return fail(HEIFGPU_E_DEVICE, std::string("colour table upload: ") + hipGetErrorString(up));
-            }
-            e.key = key;
-            cache.entries.push_back(std::move(e));
-            hit = &cache.entries.back();
-        }
-        refs[i].lut = reinterpret_cast<uint64_t>(hit->dev);
+        if (int rc = cache->table(key, "colour", refs[i].lut)) return rc;
         refs[i].n = int32_t(tn);
         for (int k = 0; k < 9; ++k) refs[i].m[k] = t->m[k];
         refs[i].tone = int32_t(t->tone);
         refs[i].tone_off = tone_off;
     }
     return HEIFGPU_OK;
+}
+
+// What every render call checks first: its pointers (all: none of them is null) and n, its
+// format (format_invalid: what is wrong with it, or nullptr), and n again.  The context is not
+// among them: every check of the arguments answers without one, and the submit looks at it.
+static int call_check(bool all, size_t n, const char *format_invalid) {
+    if (!all || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
+    if (format_invalid) return fail(HEIFGPU_E_INVALID, format_invalid);
+    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    return HEIFGPU_OK;
+}
+// call_check's format_invalid for a pixel format of first..last
+static const char *format_outside(uint32_t format, uint32_t first, uint32_t last) {
+    return format < first || format > last ? "format" : nullptr;
 }
 
 // What heifgpu_render_batch and heifgpu_render_batch_scaled check and fill alike for
@@ -222,8 +256,18 @@ static int render_desc_fill(size_t i, const heifgpu_image *const *imgs, const he
     return HEIFGPU_OK;
 }
 
-// The next slot of the context's descriptor ring, drained of the call that used it last.
-static int render_ring_slot(heifgpu_ctx *ctx, RenderRing::Slot **out) {
+// What every render call ends in, for any descriptor type: the next slot of the context's ring,
+// drained of the call that used it last, the descriptors then the call's trailing blocks in one
+// staging image, in the order given, one copy, the one launch (launch(descriptors on the device,
+// stream)) and the slot's event.
+struct Block {
+    const void *p;
+    size_t bytes;  // a multiple of 8, or 0: the call has no such block
+};
+template <class Desc, class Launch>
+static int submit(heifgpu_ctx *ctx, const std::vector<Desc> &descs, std::initializer_list<Block> blocks, Launch launch,
+                  void *stream) {
+    static_assert(sizeof(Desc) % 8 == 0, "the blocks behind the descriptors are 8-byte aligned");
     HIP_TRY(hipSetDevice(ctx->device));
     if (!ctx->render) {
         auto ring = std::make_unique<RenderRing>();
@@ -234,26 +278,41 @@ static int render_ring_slot(heifgpu_ctx *ctx, RenderRing::Slot **out) {
     ctx->render->next = (ctx->render->next + 1) % kRenderSlots;
     if (sl.pending) HIP_TRY(hipEventSynchronize(sl.done));  // the call that used this slot last
     sl.pending = false;
-    *out = &sl;
+    const size_t dbytes = descs.size() * sizeof(Desc);
+    size_t bytes = dbytes;
+    for (const Block &b : blocks) bytes += b.bytes;
+    HIP_TRY(sl.host.reserve(bytes));
+    HIP_TRY(sl.dev.alloc(bytes));
+    std::memcpy(sl.host.p, descs.data(), dbytes);
+    size_t at = dbytes;
+    for (const Block &b : blocks) {  // behind the descriptors: one copy
+        if (b.bytes) std::memcpy(sl.host.p + at, b.p, b.bytes);
+        at += b.bytes;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch(reinterpret_cast<const Desc *>(sl.dev.p), s));  // the one launch
+    HIP_TRY(hipEventRecord(sl.done, s));
+    sl.pending = true;
     return HEIFGPU_OK;
 }
 
-// What every render call ends in, for Desc = RenderDesc, ScaleDesc or TensorDesc: the
-// colour refs, a ring slot, the descriptors then the refs in one staging image, one
-// copy, the one launch and the slot's event.  When an image of the call is set to
-// bilinear chroma upsampling (image_chroma_up: the setting window_source_rect reads too)
-// the call goes to the kernels that know it: a ChromaRef per image follows the ColorRefs,
-// which are then always there (lut == 0 for an image without a transform).
+// The tail of every render but the gain-map renders, for Desc = RenderDesc, ScaleDesc, TensorDesc
+// or the filtered calls': the context, the colour refs, and the submit.  When an image of the
+// call is set to bilinear chroma upsampling (image_chroma_up: the setting window_source_rect
+// reads too) the call goes to the kernels that know it: a ChromaRef per image follows the
+// ColorRefs, which are then always there (lut == 0 for an image without a transform).
 template <class Desc>
 static int render_submit(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, const std::vector<Desc> &descs,
                          int max_tiles, uint32_t format, int bps, const heifgpu_color_transform *const *xf,
                          void *stream) {
-    static_assert(sizeof(Desc) % 8 == 0, "the ColorRefs behind the descriptors are 8-byte aligned");
+    static_assert(sizeof(ColorRef) % 8 == 0, "the ChromaUps behind the ColorRefs are 8-byte aligned");
+    static_assert(sizeof(ChromaUp) == sizeof(ChromaRef), "ChromaUp is ChromaRef's image");
+    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
     const size_t n = descs.size();
     std::vector<ColorRef> refs;
     bool tone = false;
     if (int rc = color_refs_fill(ctx, imgs, n, format, xf, refs, tone)) return rc;
-    static_assert(sizeof(ChromaUp) == sizeof(ChromaRef) && sizeof(ColorRef) % 8 == 0, "ChromaUp is ChromaRef's image");
     std::vector<ChromaUp> ups;
     bool any_up = false;
     for (size_t i = 0; i < n; ++i) any_up = any_up || image_chroma_up(imgs[i]->img).mode != 0;
@@ -262,45 +321,34 @@ static int render_submit(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, con
         ups.resize(n);
         for (size_t i = 0; i < n; ++i) ups[i] = image_chroma_up(imgs[i]->img);
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    RenderRing::Slot *slot = nullptr;
-    if (int rc = render_ring_slot(ctx, &slot)) return rc;
-    RenderRing::Slot &sl = *slot;
-    const size_t dbytes = n * sizeof(Desc), rbytes = refs.size() * sizeof(ColorRef);
-    const size_t bytes = dbytes + rbytes + ups.size() * sizeof(ChromaUp);
-    HIP_TRY(sl.host.reserve(bytes));
-    HIP_TRY(sl.dev.alloc(bytes));
-    std::memcpy(sl.host.p, descs.data(), dbytes);
-    if (!refs.empty()) std::memcpy(sl.host.p + dbytes, refs.data(), rbytes);  // behind the descriptors: one copy
-    if (!ups.empty()) std::memcpy(sl.host.p + dbytes + rbytes, ups.data(), ups.size() * sizeof(ChromaUp));
-    HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host.p, bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_render(reinterpret_cast<const Desc *>(sl.dev.p), int(n), max_tiles, int(format), bps,
-                          any_up ? RENDER_CHROMA : refs.empty() ? RENDER_PLAIN : tone ? RENDER_TONE : RENDER_MANAGED,
-                          s));  // the one launch
-    HIP_TRY(hipEventRecord(sl.done, s));
-    sl.pending = true;
-    return HEIFGPU_OK;
+    const int nn = int(n), fmt = int(format);
+    const int color = any_up ? RENDER_CHROMA : refs.empty() ? RENDER_PLAIN : tone ? RENDER_TONE : RENDER_MANAGED;
+    return submit(ctx, descs, {{refs.data(), refs.size() * sizeof(ColorRef)}, {ups.data(), ups.size() * sizeof(ChromaUp)}},
+                  [=](const Desc *dev, hipStream_t s) { return launch_render(dev, nn, max_tiles, fmt, bps, color, s); },
+                  stream);
+}
+
+// the tile geometry of a full-size render (k_render, k_render_gain) in its descriptor; returns d.tiles
+static int full_size_tiles(RenderDesc &d) {
+    const int tw = d.swap ? kRenderTile : kRenderRowW, th = d.swap ? kRenderTile : kRenderRowH;
+    d.tiles_x = (d.out_w + tw - 1) / tw;
+    d.tiles = d.tiles_x * ((d.out_h + th - 1) / th);
+    return d.tiles;
 }
 
 static int render_batch_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
                              const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
                              const heifgpu_color_transform *const *xf, const heifgpu_surface *out, void *stream) {
-    if (!ctx || !imgs || !in || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
-    if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
-    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    if (int rc = call_check(imgs && in && out, n, format_outside(format, 0, HEIFGPU_PIX_RGBA16))) return rc;
     std::vector<RenderDesc> descs(n);
     int bps = 0, max_tiles = 0;
     for (size_t i = 0; i < n; ++i) {
         if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
         const DisplayMap &dm = imgs[i]->img.display;
-        RenderDesc &d = descs[i];
         if (int rc = render_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, out, dm, dm.out_width, dm.out_height,
-                                      bps, d))
+                                      bps, descs[i]))
             return rc;
-        const int tw = d.swap ? kRenderTile : kRenderRowW, th = d.swap ? kRenderTile : kRenderRowH;
-        d.tiles_x = (d.out_w + tw - 1) / tw;
-        d.tiles = d.tiles_x * ((d.out_h + th - 1) / th);
-        max_tiles = std::max(max_tiles, d.tiles);
+        max_tiles = std::max(max_tiles, full_size_tiles(descs[i]));
     }
     return render_submit(ctx, imgs, descs, max_tiles, format, bps, xf, stream);
 }
@@ -348,23 +396,34 @@ int heifgpu_scale_fit(const heifgpu_display_info *d, uint32_t box_w, uint32_t bo
     return HEIFGPU_OK;
 }
 
+// The one reading of a heifgpu_scale: its rendered size, and its window of image img as
+// (x, y, w, h) of the displayed picture (the whole picture when it names none).
+static int scale_window(const heifgpu_image *img, const heifgpu_scale &sc, uint32_t (&w)[4]) {
+    if (!img) return fail(HEIFGPU_E_INVALID, "null image");
+    const DisplayMap &dm = img->img.display;
+    if (!sc.out_width || !sc.out_height || sc.out_width > 65535 || sc.out_height > 65535)
+        return fail(HEIFGPU_E_INVALID, "rendered size outside 1..65535");
+    w[0] = w[1] = 0, w[2] = dm.out_width, w[3] = dm.out_height;
+    if (sc.width || sc.height) {
+        if (!sc.width || !sc.height || sc.x >= dm.out_width || sc.y >= dm.out_height ||
+            sc.width > dm.out_width - sc.x || sc.height > dm.out_height - sc.y)
+            return fail(HEIFGPU_E_INVALID, "window empty or outside the displayed picture");
+        w[0] = sc.x, w[1] = sc.y, w[2] = sc.width, w[3] = sc.height;
+    }
+    return HEIFGPU_OK;
+}
+
 // What heifgpu_render_batch_scaled and heifgpu_render_batch_tensor check and fill alike
-// for image i: the window, then `flip` (bit 0: columns, bit 1: rows of the rendered
+// for image i: the window (scale_window), then `flip` (bit 0: columns, bit 1: rows of the rendered
 // picture, which is the mirrored window rendered: the weights are symmetric) as further
 // steps of the display map, render_desc_fill through that map, and the tile geometry.
 static int scale_desc_fill(size_t i, const heifgpu_image *const *imgs, const heifgpu_planes *in,
                            const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
                            const heifgpu_scale &sc, uint32_t flip, const heifgpu_surface *out, int &bps, ScaleDesc &sd) {
-    if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
+    uint32_t w[4];
+    if (int rc = scale_window(imgs[i], sc, w)) return rc;
     DisplayMap dm = imgs[i]->img.display;
-    if (!sc.out_width || !sc.out_height || sc.out_width > 65535 || sc.out_height > 65535)
-        return fail(HEIFGPU_E_INVALID, "rendered size outside 1..65535");
-    if (sc.width || sc.height) {
-        if (!sc.width || !sc.height || sc.x >= dm.out_width || sc.y >= dm.out_height ||
-            sc.width > dm.out_width - sc.x || sc.height > dm.out_height - sc.y)
-            return fail(HEIFGPU_E_INVALID, "window empty or outside the displayed picture");
-        display_window(dm, sc.x, sc.y, sc.width, sc.height);
-    }
+    if (sc.width || sc.height) display_window(dm, w[0], w[1], w[2], w[3]);
     if (flip & 1) display_imir(dm, 0);
     if (flip & 2) display_imir(dm, 1);
     if (dm.out_width > 65535 || dm.out_height > 65535)
@@ -403,10 +462,7 @@ static int render_scaled_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs
                               const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
                               const heifgpu_scale *scale, const heifgpu_color_transform *const *xf,
                               const heifgpu_surface *out, void *stream) {
-    // (the context is looked at last: every check of the arguments answers without one)
-    if (!imgs || !in || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
-    if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
-    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    if (int rc = call_check(imgs && in && scale && out, n, format_outside(format, 0, HEIFGPU_PIX_RGBA16))) return rc;
     std::vector<ScaleDesc> descs(n);
     int bps = 0, max_tiles = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -414,7 +470,6 @@ static int render_scaled_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs
             return rc;
         max_tiles = std::max(max_tiles, descs[i].r.tiles);
     }
-    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
     return render_submit(ctx, imgs, descs, max_tiles, format, bps, xf, stream);
 }
 
@@ -432,50 +487,58 @@ int heifgpu_render_batch_scaled_color(heifgpu_ctx *ctx, const heifgpu_image *con
     return render_scaled_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, scale, xf, out, stream);
 }
 
+// what is wrong with the heifgpu_tensor_format of a tensor call, or nullptr (call_check's format_invalid)
+static const char *tensor_format_invalid(const heifgpu_tensor_format *fmt) {
+    if (!fmt) return "invalid argument";
+    if (fmt->src > HEIFGPU_PIX_RGBA16) return "source format";
+    if (fmt->elem > HEIFGPU_ELEM_BF16) return "element type";
+    if (fmt->layout > HEIFGPU_LAYOUT_HWC) return "layout";
+    for (int c = 0; c < ((fmt->src & 1) ? 4 : 3); ++c)
+        if (!std::isfinite(fmt->a[c]) || !std::isfinite(fmt->b[c])) return "scale or bias not finite";
+    return nullptr;
+}
+
+// The output half of image i's TensorDesc, behind the fill of td.s.r (its out_w is the row): the
+// image's flip and tensor surface checked, the surface and the format's constants filled in.
+static int tensor_out_fill(const heifgpu_tensor_format &fmt, const heifgpu_tensor_surface &o, uint32_t flip, TensorDesc &td) {
+    if (flip > 3) return fail(HEIFGPU_E_INVALID, "flip above 3");
+    const int nch = (fmt.src & 1) ? 4 : 3;
+    const int64_t esz = fmt.elem == HEIFGPU_ELEM_F32 ? 4 : 2;
+    if (!o.data || (reinterpret_cast<uintptr_t>(o.data) & uintptr_t(esz - 1)))
+        return fail(HEIFGPU_E_INVALID, "tensor data null or not aligned to its element");
+    const int64_t row = int64_t(td.s.r.out_w) * esz * (fmt.layout == HEIFGPU_LAYOUT_HWC ? nch : 1);
+    if (o.stride_y < row || (o.stride_y & (esz - 1)))
+        return fail(HEIFGPU_E_INVALID, "stride_y below the row or not a multiple of the element size");
+    if (fmt.layout == HEIFGPU_LAYOUT_CHW && (o.stride_c & (esz - 1)))
+        return fail(HEIFGPU_E_INVALID, "stride_c not a multiple of the element size");
+    td.s.r.out = reinterpret_cast<uint64_t>(o.data);
+    td.stride_c = fmt.layout == HEIFGPU_LAYOUT_CHW ? o.stride_c : 0;
+    td.stride_y = o.stride_y;
+    td.elem = int32_t(fmt.elem);
+    td.layout = int32_t(fmt.layout);
+    for (int c = 0; c < 4; ++c) {
+        td.a[c] = c < nch ? fmt.a[c] : 0.f;
+        td.b[c] = c < nch ? fmt.b[c] : 0.f;
+    }
+    return HEIFGPU_OK;
+}
+
 static int render_tensor_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
                               const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in,
                               const heifgpu_tensor_format *fmt, const heifgpu_scale *scale, const uint32_t *flip,
                               const heifgpu_color_transform *const *xf, const heifgpu_tensor_surface *out,
                               void *stream) {
-    // (the context is looked at last, as in heifgpu_render_batch_scaled)
-    if (!imgs || !in || !fmt || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
-    if (fmt->src > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "source format");
-    if (fmt->elem > HEIFGPU_ELEM_BF16) return fail(HEIFGPU_E_INVALID, "element type");
-    if (fmt->layout > HEIFGPU_LAYOUT_HWC) return fail(HEIFGPU_E_INVALID, "layout");
-    const int nch = (fmt->src & 1) ? 4 : 3;
-    for (int c = 0; c < nch; ++c)
-        if (!std::isfinite(fmt->a[c]) || !std::isfinite(fmt->b[c]))
-            return fail(HEIFGPU_E_INVALID, "scale or bias not finite");
-    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
-    const int64_t esz = fmt->elem == HEIFGPU_ELEM_F32 ? 4 : 2;
+    if (int rc = call_check(imgs && in && fmt && scale && out, n, tensor_format_invalid(fmt))) return rc;
     std::vector<TensorDesc> descs(n);
     int bps = 0, max_tiles = 0;
     for (size_t i = 0; i < n; ++i) {
         const uint32_t fl = flip ? flip[i] : 0;
-        if (fl > 3) return fail(HEIFGPU_E_INVALID, "flip above 3");
         TensorDesc &td = descs[i];
         if (int rc = scale_desc_fill(i, imgs, in, alpha_imgs, alpha_in, fmt->src, scale[i], fl, nullptr, bps, td.s))
             return rc;
-        const heifgpu_tensor_surface &o = out[i];
-        if (!o.data || (reinterpret_cast<uintptr_t>(o.data) & uintptr_t(esz - 1)))
-            return fail(HEIFGPU_E_INVALID, "tensor data null or not aligned to its element");
-        const int64_t row = int64_t(td.s.r.out_w) * esz * (fmt->layout == HEIFGPU_LAYOUT_HWC ? nch : 1);
-        if (o.stride_y < row || (o.stride_y & (esz - 1)))
-            return fail(HEIFGPU_E_INVALID, "stride_y below the row or not a multiple of the element size");
-        if (fmt->layout == HEIFGPU_LAYOUT_CHW && (o.stride_c & (esz - 1)))
-            return fail(HEIFGPU_E_INVALID, "stride_c not a multiple of the element size");
-        td.s.r.out = reinterpret_cast<uint64_t>(o.data);
-        td.stride_c = fmt->layout == HEIFGPU_LAYOUT_CHW ? o.stride_c : 0;
-        td.stride_y = o.stride_y;
-        td.elem = int32_t(fmt->elem);
-        td.layout = int32_t(fmt->layout);
-        for (int c = 0; c < 4; ++c) {
-            td.a[c] = c < nch ? fmt->a[c] : 0.f;
-            td.b[c] = c < nch ? fmt->b[c] : 0.f;
-        }
+        if (int rc = tensor_out_fill(*fmt, out[i], fl, td)) return rc;
         max_tiles = std::max(max_tiles, td.s.r.tiles);
     }
-    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
     return render_submit(ctx, imgs, descs, max_tiles, fmt->src, bps, xf, stream);
 }
 
@@ -487,20 +550,10 @@ int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *im
 }
 
 // ---- the filtered renders (k_render_resampled) ----
-// heifgpu_scale's window of image img as (x, y, w, h) of its displayed picture
-static int scale_window(const heifgpu_image *img, const heifgpu_scale &sc, uint32_t (&w)[4]) {
-    if (!img) return fail(HEIFGPU_E_INVALID, "null image");
-    const DisplayMap &dm = img->img.display;
-    if (!sc.out_width || !sc.out_height || sc.out_width > 65535 || sc.out_height > 65535)
-        return fail(HEIFGPU_E_INVALID, "rendered size outside 1..65535");
-    w[0] = w[1] = 0, w[2] = dm.out_width, w[3] = dm.out_height;
-    if (sc.width || sc.height) {
-        if (!sc.width || !sc.height || sc.x >= dm.out_width || sc.y >= dm.out_height ||
-            sc.width > dm.out_width - sc.x || sc.height > dm.out_height - sc.y)
-            return fail(HEIFGPU_E_INVALID, "window empty or outside the displayed picture");
-        w[0] = sc.x, w[1] = sc.y, w[2] = sc.width, w[3] = sc.height;
-    }
-    if (dm.out_width > 65535 || dm.out_height > 65535)
+// scale_window for the filtered calls, whose taps reach over the whole displayed picture
+static int filtered_window(const heifgpu_image *img, const heifgpu_scale &sc, uint32_t (&w)[4]) {
+    if (int rc = scale_window(img, sc, w)) return rc;
+    if (img->img.display.out_width > 65535 || img->img.display.out_height > 65535)
         return fail(HEIFGPU_E_UNSUPPORTED, "displayed side above 65535");
     return HEIFGPU_OK;
 }
@@ -512,7 +565,7 @@ static int resample_desc_fill(size_t i, const heifgpu_image *const *imgs, const 
                               const heifgpu_scale &sc, uint32_t filter, uint32_t flip, const heifgpu_surface *out,
                               int &bps, RenderDesc &d, RsParams &p) {
     uint32_t w[4];
-    if (int rc = scale_window(imgs[i], sc, w)) return rc;
+    if (int rc = filtered_window(imgs[i], sc, w)) return rc;
     const DisplayMap &dm = imgs[i]->img.display;
     if (int rc = render_desc_fill(i, imgs, in, alpha_imgs, alpha_in, format, out, dm, sc.out_width, sc.out_height, bps, d))
         return rc;
@@ -537,10 +590,7 @@ int heifgpu_render_batch_resampled(heifgpu_ctx *ctx, const heifgpu_image *const 
     if (filter > HEIFGPU_FILTER_BICUBIC) return fail(HEIFGPU_E_INVALID, "filter");
     if (filter == HEIFGPU_FILTER_AREA)
         return render_scaled_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, scale, xf, out, stream);
-    // (the context is looked at last, as in heifgpu_render_batch_scaled)
-    if (!imgs || !in || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
-    if (format > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "format");
-    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
+    if (int rc = call_check(imgs && in && scale && out, n, format_outside(format, 0, HEIFGPU_PIX_RGBA16))) return rc;
     std::vector<ResampleDesc> descs(n);
     int bps = 0, max_tiles = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -549,7 +599,6 @@ int heifgpu_render_batch_resampled(heifgpu_ctx *ctx, const heifgpu_image *const 
             return rc;
         max_tiles = std::max(max_tiles, descs[i].r.tiles);
     }
-    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
     return render_submit(ctx, imgs, descs, max_tiles, format, bps, xf, stream);
 }
 
@@ -562,46 +611,18 @@ int heifgpu_render_batch_tensor_resampled(heifgpu_ctx *ctx, const heifgpu_image 
     if (filter > HEIFGPU_FILTER_BICUBIC) return fail(HEIFGPU_E_INVALID, "filter");
     if (filter == HEIFGPU_FILTER_AREA)
         return render_tensor_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, fmt, scale, flip, xf, out, stream);
-    if (!imgs || !in || !fmt || !scale || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
-    if (fmt->src > HEIFGPU_PIX_RGBA16) return fail(HEIFGPU_E_INVALID, "source format");
-    if (fmt->elem > HEIFGPU_ELEM_BF16) return fail(HEIFGPU_E_INVALID, "element type");
-    if (fmt->layout > HEIFGPU_LAYOUT_HWC) return fail(HEIFGPU_E_INVALID, "layout");
-    const int nch = (fmt->src & 1) ? 4 : 3;
-    for (int c = 0; c < nch; ++c)
-        if (!std::isfinite(fmt->a[c]) || !std::isfinite(fmt->b[c]))
-            return fail(HEIFGPU_E_INVALID, "scale or bias not finite");
-    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
-    const int64_t esz = fmt->elem == HEIFGPU_ELEM_F32 ? 4 : 2;
+    if (int rc = call_check(imgs && in && fmt && scale && out, n, tensor_format_invalid(fmt))) return rc;
     std::vector<ResampleTensorDesc> descs(n);
     int bps = 0, max_tiles = 0;
     for (size_t i = 0; i < n; ++i) {
         const uint32_t fl = flip ? flip[i] : 0;
-        if (fl > 3) return fail(HEIFGPU_E_INVALID, "flip above 3");
         TensorDesc &td = descs[i].t;
-        td = TensorDesc{};
         if (int rc = resample_desc_fill(i, imgs, in, alpha_imgs, alpha_in, fmt->src, scale[i], filter, fl, nullptr, bps,
                                         td.s.r, descs[i].p))
             return rc;
-        const heifgpu_tensor_surface &o = out[i];
-        if (!o.data || (reinterpret_cast<uintptr_t>(o.data) & uintptr_t(esz - 1)))
-            return fail(HEIFGPU_E_INVALID, "tensor data null or not aligned to its element");
-        const int64_t row = int64_t(td.s.r.out_w) * esz * (fmt->layout == HEIFGPU_LAYOUT_HWC ? nch : 1);
-        if (o.stride_y < row || (o.stride_y & (esz - 1)))
-            return fail(HEIFGPU_E_INVALID, "stride_y below the row or not a multiple of the element size");
-        if (fmt->layout == HEIFGPU_LAYOUT_CHW && (o.stride_c & (esz - 1)))
-            return fail(HEIFGPU_E_INVALID, "stride_c not a multiple of the element size");
-        td.s.r.out = reinterpret_cast<uint64_t>(o.data);
-        td.stride_c = fmt->layout == HEIFGPU_LAYOUT_CHW ? o.stride_c : 0;
-        td.stride_y = o.stride_y;
-        td.elem = int32_t(fmt->elem);
-        td.layout = int32_t(fmt->layout);
-        for (int c = 0; c < 4; ++c) {
-            td.a[c] = c < nch ? fmt->a[c] : 0.f;
-            td.b[c] = c < nch ? fmt->b[c] : 0.f;
-        }
+        if (int rc = tensor_out_fill(*fmt, out[i], fl, td)) return rc;
         max_tiles = std::max(max_tiles, td.s.r.tiles);
     }
-    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
     return render_submit(ctx, imgs, descs, max_tiles, fmt->src, bps, xf, stream);
 }
 
@@ -644,7 +665,7 @@ int heifgpu_window_source_rect_resampled(const heifgpu_image *img, const heifgpu
     if (!img || !scale || !src) return fail(HEIFGPU_E_INVALID, "null argument");
     if (filter > HEIFGPU_FILTER_BICUBIC) return fail(HEIFGPU_E_INVALID, "filter");
     uint32_t w[4];
-    if (int rc = scale_window(img, *scale, w)) return rc;
+    if (int rc = filtered_window(img, *scale, w)) return rc;
     if (filter != HEIFGPU_FILTER_AREA) {
         // per axis the taps of the first output to those of the last, in the displayed picture
         const DisplayMap &dm = img->img.display;
@@ -693,13 +714,27 @@ static void gain_table_image(const heifgpu_gain_transform &t, std::vector<uint16
     e_off = ne ? int32_t(eoff) : 0;
 }
 
+// The fields GainRef and GainScaleDesc have alike, in either (G): the gain plane, the decoded
+// base and gain-map sizes, the top gain code.
+template <class G>
+static void gain_map_fill(const heifgpu_planes &gain_in, const heifgpu_image_info &info, const heifgpu_image_info &ginfo,
+                          uint32_t gain_bits, G &g) {
+    g.gain = reinterpret_cast<uint64_t>(gain_in.plane[0]);
+    g.gain_pitch = gain_in.pitch[0];
+    g.gain_bps = int32_t(ginfo.bytes_per_sample);
+    g.w = int32_t(info.width), g.h = int32_t(info.height), g.wg = int32_t(ginfo.width), g.hg = int32_t(ginfo.height);
+    g.inv_w = 1.0 / double(info.width), g.inv_h = 1.0 / double(info.height);
+    g.gmax = 256u * ((1u << gain_bits) - 1);
+}
+
 // What the two gain-map renders check and fill alike for image i, in front of its descriptor:
 // the transform, the images' depths and sides, the gain image's display map, the planes'
-// pitches.  g: everything of the GainRef but its tables; abits: the alpha image's depth, 0 without one.
+// pitches.  g: everything of the GainRef but its tables; gd: the scaled render's descriptor, which
+// gets its gain_map_fill too (nullptr at full size); abits: the alpha image's depth, 0 without one.
 static int gain_image_fill(size_t i, const heifgpu_image *const *imgs, const heifgpu_image *const *gain_imgs,
                            const heifgpu_planes *gain_in, const heifgpu_image *const *alpha_imgs,
                            const heifgpu_planes *alpha_in, bool pq, bool with_alpha,
-                           const heifgpu_gain_transform *const *xf, GainRef &g, uint32_t &abits) {
+                           const heifgpu_gain_transform *const *xf, GainRef &g, GainScaleDesc *gd, uint32_t &abits) {
     if (!imgs[i] || !gain_imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
     if (!xf[i]) return fail(HEIFGPU_E_INVALID, "null gain transform");
     const heifgpu_gain_transform &t = *xf[i];
@@ -746,15 +781,11 @@ static int gain_image_fill(size_t i, const heifgpu_image *const *imgs, const hei
             return fail(HEIFGPU_E_INVALID, "alpha plane pitch smaller than its row");
     }
     g = GainRef{};
-    g.gain = reinterpret_cast<uint64_t>(gain_in[i].plane[0]);
-    g.gain_pitch = gain_in[i].pitch[0];
-    g.gain_bps = int32_t(ginfo.bytes_per_sample);
-    g.w = int32_t(info.width), g.h = int32_t(info.height), g.wg = int32_t(ginfo.width), g.hg = int32_t(ginfo.height);
-    g.inv_w = 1.0 / double(info.width), g.inv_h = 1.0 / double(info.height);
+    gain_map_fill(gain_in[i], info, ginfo, t.gain_bits, g);
+    if (gd) gain_map_fill(gain_in[i], info, ginfo, t.gain_bits, *gd);
     g.n = 1 << t.bits;
     for (int k = 0; k < 9; ++k) g.m[k] = t.m[k];
     g.k_b = t.k_b, g.k_a = t.k_a;
-    g.gmax = 256u * ((1u << t.gain_bits) - 1);
     g.maxp = pq ? int32_t((1u << t.pq_bits) - 1) : 0;
     g.alpha_shift = pq && abits ? int32_t(abits) - int32_t(t.pq_bits) : 0;
     g.alpha_scale = abits ? 1.0f / float((1u << abits) - 1) : 1.0f;
@@ -771,55 +802,21 @@ static void gain_alpha_fill(const heifgpu_image *alpha_img, const heifgpu_planes
     d.alpha_shift = 0;  // the sample as decoded: the GainRef says where it goes
 }
 
-// What the two gain-map renders end in, for Desc = RenderDesc or GainScaleDesc: the tables into
-// the context's content cache (color_refs_fill's rules), a ring slot, the descriptors then the
-// GainRefs in one staging image, one copy, the one launch and the slot's event.
+// What the two gain-map renders end in, for Desc = RenderDesc or GainScaleDesc: the context, the
+// tables of the transforms out of the context's cache into the GainRefs, and the submit with the
+// GainRefs behind the descriptors.
 template <class Desc, class Launch>
 static int gain_submit(heifgpu_ctx *ctx, const std::vector<Desc> &descs, std::vector<GainRef> &refs,
                        const heifgpu_gain_transform *const *xf, Launch launch, void *stream) {
-    static_assert(sizeof(Desc) % 8 == 0, "the GainRefs behind the descriptors are 8-byte aligned");
-    const size_t n = descs.size();
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->color) ctx->color = new ColorCache;
-    ColorCache &cache = *ctx->color;
-    if (cache.entries.size() >= kColorCacheMax) {
-        HIP_TRY(hipDeviceSynchronize());  // nothing in flight reads a table that is freed
-        cache.clear();
-    }
+    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
+    ColorCache *cache = nullptr;
+    if (int rc = color_cache_open(ctx, cache)) return rc;
     std::vector<uint16_t> key;
-    for (size_t i = 0; i < n; ++i) {
+    for (size_t i = 0; i < refs.size(); ++i) {
         gain_table_image(*xf[i], key, refs[i].t_off, refs[i].e_off);
-        ColorCache::Entry *hit = nullptr;
-        for (ColorCache::Entry &e : cache.entries)
-            if (e.key == key) hit = &e;
-        if (!hit) {
-            ColorCache::Entry e;
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&e.dev), key.size() * 2));
-            const hipError_t up = hipMemcpy(e.dev, key.data(), key.size() * 2, hipMemcpyHostToDevice);  // blocking
-            if (up != hipSuccess) {
-                (void)hipFree(e.dev);
-                return fail(HEIFGPU_E_DEVICE, std::string("gain table upload: ") + hipGetErrorString(up));
-            }
-            e.key = key;
-            cache.entries.push_back(std::move(e));
-            hit = &cache.entries.back();
-        }
-        refs[i].lut = reinterpret_cast<uint64_t>(hit->dev);
+        if (int rc = cache->table(key, "gain", refs[i].lut)) return rc;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    RenderRing::Slot *slot = nullptr;
-    if (int rc = render_ring_slot(ctx, &slot)) return rc;
-    RenderRing::Slot &sl = *slot;
-    const size_t dbytes = n * sizeof(Desc), rbytes = n * sizeof(GainRef);
-    HIP_TRY(sl.host.reserve(dbytes + rbytes));
-    HIP_TRY(sl.dev.alloc(dbytes + rbytes));
-    std::memcpy(sl.host.p, descs.data(), dbytes);
-    std::memcpy(sl.host.p + dbytes, refs.data(), rbytes);  // behind the descriptors: one copy
-    HIP_TRY(hipMemcpyAsync(sl.dev.p, sl.host.p, dbytes + rbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch(reinterpret_cast<const Desc *>(sl.dev.p), s));  // the one launch
-    HIP_TRY(hipEventRecord(sl.done, s));
-    sl.pending = true;
-    return HEIFGPU_OK;
+    return submit(ctx, descs, {{refs.data(), refs.size() * sizeof(GainRef)}}, launch, stream);
 }
 
 int heifgpu_render_batch_gain(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
@@ -827,10 +824,10 @@ int heifgpu_render_batch_gain(heifgpu_ctx *ctx, const heifgpu_image *const *imgs
                               const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
                               const heifgpu_gain_transform *const *xf, const heifgpu_surface *out, void *stream) {
     static_assert(HEIFGPU_PIX_HDR_RGB16F - 4 == GAIN_RGB16F && HEIFGPU_PIX_HDR_RGBA16PQ - 4 == GAIN_RGBA16PQ, "HDR formats");
-    if (!ctx || !imgs || !in || !gain_imgs || !gain_in || !xf || !out || n == 0) return fail(HEIFGPU_E_INVALID, "invalid argument");
-    if (format < HEIFGPU_PIX_HDR_RGB16F || format > HEIFGPU_PIX_HDR_RGBA16PQ) return fail(HEIFGPU_E_INVALID, "format");
-    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
-    const int hf = int(format) - 4;
+    if (int rc = call_check(imgs && in && gain_imgs && gain_in && xf && out, n,
+                            format_outside(format, HEIFGPU_PIX_HDR_RGB16F, HEIFGPU_PIX_HDR_RGBA16PQ)))
+        return rc;
+    const int hf = int(format) - 4;  // k_render_gain's: GAIN_*
     const bool pq = (hf & 2) != 0, with_alpha = (hf & 1) != 0;
     const uint32_t wide = with_alpha ? HEIFGPU_PIX_RGBA16 : HEIFGPU_PIX_RGB16;  // what the descriptors are filled for
     std::vector<RenderDesc> descs(n);
@@ -838,17 +835,15 @@ int heifgpu_render_batch_gain(heifgpu_ctx *ctx, const heifgpu_image *const *imgs
     int bps = 0, max_tiles = 0;
     for (size_t i = 0; i < n; ++i) {
         uint32_t abits = 0;
-        if (int rc = gain_image_fill(i, imgs, gain_imgs, gain_in, alpha_imgs, alpha_in, pq, with_alpha, xf, refs[i], abits))
+        if (int rc = gain_image_fill(i, imgs, gain_imgs, gain_in, alpha_imgs, alpha_in, pq, with_alpha, xf, refs[i], nullptr,
+                                     abits))
             return rc;
         const DisplayMap &dm = imgs[i]->img.display;
         RenderDesc &d = descs[i];
         if (int rc = render_desc_fill(i, imgs, in, nullptr, nullptr, wide, out, dm, dm.out_width, dm.out_height, bps, d))
             return rc;
         if (abits) gain_alpha_fill(alpha_imgs[i], alpha_in[i], d);
-        const int tw = d.swap ? kRenderTile : kRenderRowW, th = d.swap ? kRenderTile : kRenderRowH;
-        d.tiles_x = (d.out_w + tw - 1) / tw;
-        d.tiles = d.tiles_x * ((d.out_h + th - 1) / th);
-        max_tiles = std::max(max_tiles, d.tiles);
+        max_tiles = std::max(max_tiles, full_size_tiles(d));
     }
     const int nn = int(n);
     return gain_submit(ctx, descs, refs, xf,
@@ -863,33 +858,25 @@ int heifgpu_render_batch_gain_scaled(heifgpu_ctx *ctx, const heifgpu_image *cons
                                      const heifgpu_planes *gain_in, const heifgpu_image *const *alpha_imgs,
                                      const heifgpu_planes *alpha_in, uint32_t format, const heifgpu_scale *scales,
                                      const heifgpu_gain_transform *const *xf, const heifgpu_surface *out, void *stream) {
-    // (the context is looked at last, as in heifgpu_render_batch_scaled)
-    if (!imgs || !in || !gain_imgs || !gain_in || !scales || !xf || !out || n == 0)
-        return fail(HEIFGPU_E_INVALID, "invalid argument");
-    if (format < HEIFGPU_PIX_HDR_RGB16F || format > HEIFGPU_PIX_HDR_RGBA16PQ) return fail(HEIFGPU_E_INVALID, "format");
-    if (n > 65535) return fail(HEIFGPU_E_INVALID, "more than 65535 images in one render call");
-    const int hf = int(format) - 4;
+    if (int rc = call_check(imgs && in && gain_imgs && gain_in && scales && xf && out, n,
+                            format_outside(format, HEIFGPU_PIX_HDR_RGB16F, HEIFGPU_PIX_HDR_RGBA16PQ)))
+        return rc;
+    const int hf = int(format) - 4;  // k_render_gain's: GAIN_*
     const bool pq = (hf & 2) != 0, with_alpha = (hf & 1) != 0;
-    const uint32_t wide = with_alpha ? HEIFGPU_PIX_RGBA16 : HEIFGPU_PIX_RGB16;
+    const uint32_t wide = with_alpha ? HEIFGPU_PIX_RGBA16 : HEIFGPU_PIX_RGB16;  // what the descriptors are filled for
     std::vector<GainScaleDesc> descs(n);
     std::vector<GainRef> refs(n);
     int bps = 0, max_tiles = 0;
     for (size_t i = 0; i < n; ++i) {
         uint32_t abits = 0;
-        GainRef &g = refs[i];
-        if (int rc = gain_image_fill(i, imgs, gain_imgs, gain_in, alpha_imgs, alpha_in, pq, with_alpha, xf, g, abits))
-            return rc;
         GainScaleDesc &gd = descs[i];
-        gd = GainScaleDesc{};
+        if (int rc = gain_image_fill(i, imgs, gain_imgs, gain_in, alpha_imgs, alpha_in, pq, with_alpha, xf, refs[i], &gd,
+                                     abits))
+            return rc;
         if (int rc = scale_desc_fill(i, imgs, in, nullptr, nullptr, wide, scales[i], 0, out, bps, gd.s)) return rc;
         if (abits) gain_alpha_fill(alpha_imgs[i], alpha_in[i], gd.s.r);
-        gd.gain = g.gain, gd.gain_pitch = g.gain_pitch, gd.gain_bps = g.gain_bps;
-        gd.w = g.w, gd.h = g.h, gd.wg = g.wg, gd.hg = g.hg;
-        gd.inv_w = g.inv_w, gd.inv_h = g.inv_h;
-        gd.gmax = g.gmax;
         max_tiles = std::max(max_tiles, gd.s.r.tiles);
     }
-    if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
     const int nn = int(n);
     return gain_submit(ctx, descs, refs, xf,
                        [=](const GainScaleDesc *dev, hipStream_t s) {

@@ -2,7 +2,8 @@
 'tmap' payload's fields and refusals, the tables against the float64 rules of gain_ref,
 heifgpu_gain_apply and heifgpu_gain_sample (the functions the kernel runs) against gain_ref's
 numpy formula exactly, the properties of the stage, its accuracy against the unquantised
-float64 model, the ABI structs, and the reader and builder as a stand-alone ASan + UBSan
+float64 model, the ABI structs, the argument checks of heifgpu_render_batch_gain, which
+answer without a context, and the reader and builder as a stand-alone ASan + UBSan
 program.  The kernel is in tests/test_gain_gpu.py."""
 import ctypes
 import subprocess
@@ -265,6 +266,35 @@ def test_apply_refuses_what_a_render_would(H, S):
         with pytest.raises(H.HeifGpuError) as e:
             apply_lib(bad, *ok)
         assert e.value.code == E_INVALID
+
+
+def test_render_argument_checks_need_no_device(H, S):
+    """heifgpu_render_batch_gain with a null context: every check of the arguments answers
+    before the context is looked at, so a call with good arguments fails on the context and
+    one with a bad argument on that argument."""
+    from heif_amd import _lib as L
+
+    base, gain = pair(H, S, kind="apple")
+    t = base.gain_transform(gain, "srgb", "linear", 10, headroom=4.0)
+    imgs, gimgs = (ctypes.c_void_p * 1)(base._h.value), (ctypes.c_void_p * 1)(gain._h.value)
+    planes, gplanes = (L.Planes * 1)(), (L.Planes * 1)()
+    for c in range(3):
+        planes[0].plane[c], planes[0].pitch[c] = 0x1000 * (c + 1), 32  # never read: no launch happens
+    gplanes[0].plane[0], gplanes[0].pitch[0] = 0x8000, 16
+    surf = (L.Surface * 1)()
+    surf[0].pixels, surf[0].pitch = 0x10000, base.display.out_width * 6
+
+    def call(fmt=L.PIX_HDR_RGB16F, n=1, gimgs=gimgs, xf=t):
+        xfs = (ctypes.c_void_p * 1)(ctypes.addressof(xf) if xf is not None else None)
+        rc = L.lib.heifgpu_render_batch_gain(None, imgs, n, planes, gimgs, gplanes, None, None, fmt, xfs, surf, None)
+        return rc, L.last_error()
+
+    rc, msg = call()
+    assert rc == E_INVALID and "context" in msg, msg  # good arguments: only the context is missing
+    for kw, word in ((dict(fmt=L.PIX_RGB16), "format"), (dict(fmt=8), "format"), (dict(n=65536), "65535"),
+                     (dict(gimgs=(ctypes.c_void_p * 1)(None)), "null image"), (dict(xf=None), "null gain transform")):
+        rc, msg = call(**kw)
+        assert rc == E_INVALID and word in msg and "context" not in msg, (kw, msg)
 
 
 SAMPLER = [(320, 48, 160, 24, 8), (96, 64, 40, 24, 8), (33, 17, 33, 17, 10), (40, 24, 96, 64, 12), (7, 5, 1, 1, 8),
