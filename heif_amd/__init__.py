@@ -734,6 +734,22 @@ class DecodeContext:
             raise ValueError("tone_map needs a colorspace to map to")
 
     @staticmethod
+    def _check_linear(what, linear, colorspace, filter="area", tone_map=None, size=True):
+        """ValueError for linear=True where the area average in linear light is not
+        defined: without a colorspace (whose tables make it linear), with another
+        filter than "area", with a tone_map, or (render_jpeg) without a size."""
+        if not linear:
+            return
+        if colorspace is None:
+            raise ValueError(f"{what}: linear=True needs a colorspace")
+        if filter != "area":
+            raise ValueError(f"{what}: linear=True averages areas; filter {filter!r} is not done in linear light")
+        if tone_map is not None:
+            raise ValueError(f"{what}: linear=True with a tone_map is not done")
+        if size is None:
+            raise ValueError(f"{what}: linear=True needs a size (a full-size render averages nothing)")
+
+    @staticmethod
     def _check_images(what, outs, alphas, **more):
         """ValueError unless every image and alpha image carries its HeifImage and
         alphas and the sequences of `more` have one entry per image."""
@@ -752,9 +768,10 @@ class DecodeContext:
             surf[i].pitch = t.stride(0) * t.element_size()
         return surf
 
-    def _submit(self, name, outs, alphas, colorspace, wide, stream, mid, surf, tone_map=None):
+    def _submit(self, name, outs, alphas, colorspace, wide, stream, mid, surf, tone_map=None, linear=False):
         """The one call of a render: lib.<name>, or lib.<name>_color with the images'
-        transforms in front of the surfaces when a colorspace is asked for.  mid: the
+        transforms in front of the surfaces when a colorspace is asked for
+        (lib.<name>_linear with linear, which _check_linear has let through).  mid: the
         arguments between the alpha planes and the surfaces."""
         imgs, aimgs, aplanes = self._render_args(outs, alphas)
         if stream is None:
@@ -762,6 +779,8 @@ class DecodeContext:
         xf, keep = self._transforms(outs, colorspace, wide, tone_map)
         if callable(mid):  # a filtered render: one entry point, its transforms (or NULL) where mid puts them
             fn, mid = getattr(lib, name), mid(xf)
+        elif linear:
+            fn, mid = getattr(lib, name + "_linear"), mid + (xf,)
         else:
             fn, mid = (getattr(lib, name), mid) if xf is None else (getattr(lib, name + "_color"), mid + (xf,))
         _lib.check(fn(self._h, imgs, len(outs), DecodeContext.planes_of(outs), aimgs, aplanes, *mid, surf,
@@ -829,7 +848,7 @@ class DecodeContext:
     def render_scaled(self, outs: Sequence[DecodedImage], size, mode: str = "cover", fmt: str = "rgb8",
                       alphas: Optional[Sequence[Optional[DecodedImage]]] = None, windows=None,
                       stream: Optional[int] = None, colorspace: Optional[str] = None, filter: str = "area",
-                      tone_map: Optional[str] = None):
+                      tone_map: Optional[str] = None, linear: bool = False):
         """render() onto a smaller grid: the exact area average of a window of
         every displayed picture, with ONE heifgpu_render_batch_scaled call (one
         kernel launch).  size = (h, w) is the box; mode "cover" (a centred
@@ -846,8 +865,13 @@ class DecodeContext:
         "bicubic" resamples with Pillow's antialiased filter of that name
         instead of the area average (heifgpu_render_batch_resampled): per
         channel, for the 8-bit formats, exactly what PIL's
-        Image.resize(size, filter, box=window) makes of render()'s picture."""
+        Image.resize(size, filter, box=window) makes of render()'s picture.
+        linear=True (with a colorspace and the area filter) takes the average in
+        linear light instead (heifgpu_render_batch_scaled_linear): every source
+        pixel is decoded to linear before the sum and the mean is encoded after it,
+        so fine bright detail keeps its light; alpha is averaged as before."""
         self._check_tone(colorspace, tone_map)
+        self._check_linear("render_scaled", linear, colorspace, filter, tone_map)
         torch = self._torch
         n = len(outs)
         f = _lib.PIX_FORMATS[fmt]
@@ -861,7 +885,7 @@ class DecodeContext:
                                           lambda h, w: (h, w, ch), torch.int16 if wide else torch.uint8)
         if n and filt == _lib.FILTER_AREA:
             self._submit("heifgpu_render_batch_scaled", outs, alphas, colorspace, wide, stream, (f, scales),
-                         self._surfaces(res), tone_map)
+                         self._surfaces(res), tone_map, linear)
         elif n:
             self._submit("heifgpu_render_batch_resampled", outs, alphas, colorspace, wide, stream,
                          lambda xf: (f, scales, filt, xf), self._surfaces(res), tone_map)
@@ -945,7 +969,7 @@ class DecodeContext:
     def render_jpeg(self, outs: Sequence[DecodedImage], size=None, mode: str = "cover", windows=None,
                     filter: str = "area", colorspace: Optional[str] = None, tone_map: Optional[str] = None,
                     quality: int = 90, subsampling: str = "4:2:0", embed_icc: bool = True, icc_profiles=None,
-                    restart_mcus: int = 0) -> List[bytes]:
+                    restart_mcus: int = 0, linear: bool = False) -> List[bytes]:
         """The JPEG files of a batch of decoded images: render() (render_scaled() when
         size or windows is given; windows need a size) as "rgb8", then encode_jpeg(),
         all on the device.  JPEG has no alpha: the pictures are rendered opaque.
@@ -956,12 +980,14 @@ class DecodeContext:
         With "display-p3" nothing is embedded either, so most viewers will show the
         picture as sRGB, unless the caller passes icc_profiles (one profile or None
         per image, embedded as given whatever the colorspace): this library reads
-        ICC profiles and does not write them."""
+        ICC profiles and does not write them.  linear (with a size) as in
+        render_scaled()."""
         if windows is not None and size is None:
             raise ValueError("render_jpeg: windows need a size")
+        self._check_linear("render_jpeg", linear, colorspace, filter, tone_map, size)
         if size is not None:
             rgb = self.render_scaled(outs, size, mode, "rgb8", None, windows, colorspace=colorspace, filter=filter,
-                                     tone_map=tone_map)
+                                     tone_map=tone_map, linear=linear)
         else:
             rgb = self.render(outs, "rgb8", None, colorspace=colorspace, tone_map=tone_map)
         if icc_profiles is None and colorspace is None and embed_icc:
@@ -972,7 +998,7 @@ class DecodeContext:
                       mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), src: str = "rgb8", windows=None,
                       flips=None, alphas: Optional[Sequence[Optional[DecodedImage]]] = None, scale_bias=None,
                       stream: Optional[int] = None, colorspace: Optional[str] = None, filter: str = "area",
-                      tone_map: Optional[str] = None):
+                      tone_map: Optional[str] = None, linear: bool = False):
         """render_scaled() as a loader wants it: crop, flip and normalise into
         float elements with ONE heifgpu_render_batch_tensor call (one kernel
         launch).  With R the integers render_scaled(fmt=src) gives, flipped
@@ -989,9 +1015,12 @@ class DecodeContext:
         colorspace, tone_map and filter as in render_scaled(): R is then what
         render_scaled(colorspace=, filter=, tone_map=) gives (with "bilinear" or "bicubic"
         the pixels Pillow's resize gives, which is what most vision models were
-        trained on; a flip then acts on R, not on the taps)."""
+        trained on; a flip then acts on R, not on the taps).  linear as in
+        render_scaled(): R is then what render_scaled(linear=True) gives
+        (heifgpu_render_batch_tensor_linear)."""
         filt = _filter_code(filter)
         self._check_tone(colorspace, tone_map)
+        self._check_linear("render_tensor", linear, colorspace, filter, tone_map)
         torch = self._torch
         n = len(outs)
         f = _lib.PIX_FORMATS[src]
@@ -1037,7 +1066,7 @@ class DecodeContext:
         fl = None if flips is None else (ctypes.c_uint32 * n)(*[int(v) for v in flips])
         if filt == _lib.FILTER_AREA:
             self._submit("heifgpu_render_batch_tensor", outs, alphas, colorspace, wide, stream,
-                         (ctypes.byref(tf), scales, fl), surf, tone_map)
+                         (ctypes.byref(tf), scales, fl), surf, tone_map, linear)
         else:
             self._submit("heifgpu_render_batch_tensor_resampled", outs, alphas, colorspace, wide, stream,
                          lambda xf: (ctypes.byref(tf), scales, filt, fl, xf), surf, tone_map)
@@ -1212,7 +1241,7 @@ class HeicDecoder:
     def decode_display(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, size=None,
                        mode: str = "contain", tiles: str = "all", colorspace: Optional[str] = None,
                        filter: str = "area", tone_map: Optional[str] = None, peak_nits: Optional[float] = None,
-                       chroma: str = "replicate", chroma_loc: Optional[int] = None):
+                       chroma: str = "replicate", chroma_loc: Optional[int] = None, linear: bool = False):
         """The picture a viewer shows: decodes the primary image and, when it
         has one (display.alpha_item_id), its alpha plane, then renders
         (DecodeContext.render) with clap / irot / imir applied.  fmt None picks
@@ -1231,8 +1260,10 @@ class HeicDecoder:
         states (clli, mdcv).  chroma "bilinear" interpolates 4:2:0 / 4:2:2 chroma at
         the sample location the stream signals (chroma_loc 0..5 replaces it) instead
         of replicating it (HeifImage.chroma_upsampling); with tiles="window" the
-        decoded rectangle then includes the samples the taps read."""
+        decoded rectangle then includes the samples the taps read.  linear=True, with a
+        size and a colorspace, averages in linear light (DecodeContext.render_scaled)."""
         DecodeContext._check_tone(colorspace, tone_map)
+        DecodeContext._check_linear("decode_display", linear, colorspace, filter, tone_map, size)
         ctx = cls.context(device)
         out, alpha = cls._decode_pair(data, device, size, mode, tiles, True, filter, chroma, chroma_loc)
         out.image.peak_nits = peak_nits
@@ -1241,21 +1272,23 @@ class HeicDecoder:
         alphas = [alpha] if alpha is not None else None
         if size is not None:
             return ctx.render_scaled([out], size, mode, fmt, alphas, colorspace=colorspace, filter=filter,
-                                     tone_map=tone_map)[0]
+                                     tone_map=tone_map, linear=linear)[0]
         return ctx.render([out], fmt, alphas, colorspace=colorspace, tone_map=tone_map)[0]
 
     @classmethod
     def decode_jpeg(cls, data: bytes, device: int = 0, size=None, mode: str = "cover", filter: str = "area",
                     colorspace: Optional[str] = None, tone_map: Optional[str] = None, quality: int = 90,
                     subsampling: str = "4:2:0", embed_icc: bool = True, icc_profile: Optional[bytes] = None,
-                    restart_mcus: int = 0) -> bytes:
+                    restart_mcus: int = 0, linear: bool = False) -> bytes:
         """One HEIC file as one baseline JPEG file: decodes the primary image, then
         DecodeContext.render_jpeg of that one picture (its arguments; icc_profile is
         render_jpeg's icc_profiles for the one picture)."""
         DecodeContext._check_tone(colorspace, tone_map)
+        DecodeContext._check_linear("decode_jpeg", linear, colorspace, filter, tone_map, size)
         out, _ = cls._decode_pair(data, device, size, mode, "all", False, filter)
         return cls.context(device).render_jpeg([out], size, mode, None, filter, colorspace, tone_map, quality, subsampling,
-                                               embed_icc, None if icc_profile is None else [icc_profile], restart_mcus)[0]
+                                               embed_icc, None if icc_profile is None else [icc_profile], restart_mcus,
+                                               linear)[0]
 
     @classmethod
     def decode_hdr(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, colorspace: str = "display-p3",
@@ -1290,9 +1323,11 @@ class HeicDecoder:
         primary image (and its alpha plane when `src` is an RGBA format and the
         file has one), then DecodeContext.render_tensor of that one picture:
         (C, h, w), or (h, w, C) for layout="hwc".  dtype, layout, mean, std, src
-        scale_bias, colorspace, tone_map and filter go through to render_tensor; tiles and
+        scale_bias, colorspace, tone_map, filter and linear go through to render_tensor; tiles and
         peak_nits, chroma and chroma_loc as in decode_display."""
         DecodeContext._check_tone(kw.get("colorspace"), kw.get("tone_map"))
+        DecodeContext._check_linear("decode_tensor", kw.get("linear", False), kw.get("colorspace"), kw.get("filter", "area"),
+                                    kw.get("tone_map"))
         ctx = cls.context(device)
         rgba = kw.get("src", "rgb8").startswith("rgba")
         out, alpha = cls._decode_pair(data, device, size, mode, tiles, rgba, kw.get("filter", "area"), chroma, chroma_loc)

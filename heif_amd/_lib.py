@@ -306,6 +306,7 @@ EXPORTS = (
     "heifgpu_image_get_gain", "heifgpu_gain_transform_make", "heifgpu_gain_apply", "heifgpu_gain_sample",
     "heifgpu_render_batch_gain", "heifgpu_render_batch_gain_scaled", "heifgpu_gain_average",
     "heifgpu_jpeg_quant_tables", "heifgpu_jpeg_header", "heifgpu_jpeg_encode_host", "heifgpu_jpeg_encode_batch",
+    "heifgpu_render_batch_scaled_linear", "heifgpu_render_batch_tensor_linear", "heifgpu_linear_average_apply",
 )
 
 
@@ -426,6 +427,12 @@ def _load() -> ctypes.CDLL:
         "heifgpu_jpeg_encode_host": (I32, [VP, ctypes.c_int32, U32, U32, P(JpegOpts), u8p, SZ, u8p, SZ, P(SZ)]),
         "heifgpu_jpeg_encode_batch": (I32, [VP, SZ, P(Surface), P(U32), P(U32), P(JpegOpts), P(Surface),
                                             P(ctypes.c_uint64), VP]),
+        "heifgpu_render_batch_scaled_linear": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), U32, P(Scale), P(VP),
+                                                     P(Surface), VP]),
+        "heifgpu_render_batch_tensor_linear": (I32, [VP, P(VP), SZ, P(Planes), P(VP), P(Planes), P(TensorFormat), P(Scale),
+                                                     P(U32), P(VP), P(TensorSurface), VP]),
+        "heifgpu_linear_average_apply": (I32, [P(ColorTransform), P(ctypes.c_uint16), U32, U32, U32, P(Rect), U32, U32,
+                                               P(ctypes.c_uint16)]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     # (and no window decode: DecodeContext.prepare without windows then goes through prepare_ex)
@@ -448,7 +455,10 @@ def _load() -> ctypes.CDLL:
                 "heifgpu_render_batch_gain_scaled", "heifgpu_gain_average",
                 # the JPEG output (encode_jpeg / render_jpeg / decode_jpeg then need a build that has it)
                 "heifgpu_jpeg_quant_tables", "heifgpu_jpeg_header", "heifgpu_jpeg_encode_host",
-                "heifgpu_jpeg_encode_batch"}
+                "heifgpu_jpeg_encode_batch",
+                # the linear-light scaled renders (linear=True then needs a build that has them)
+                "heifgpu_render_batch_scaled_linear", "heifgpu_render_batch_tensor_linear",
+                "heifgpu_linear_average_apply"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue

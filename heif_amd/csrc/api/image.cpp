@@ -239,6 +239,65 @@ int heifgpu_color_apply(const heifgpu_color_transform *t, const uint16_t *rgb_in
     return HEIFGPU_OK;
 }
 
+// The linear-light scaled render's contract on the host (include/heifgpu.h "Linear-light scaled
+// render"), through the functions the kernel calls: color_linear_level per sample, the separable
+// sum in the kernel's order (a line's column sums, then the row of outputs), color_linear_mean,
+// color_linear_encode.  A fourth channel is averaged as codes.
+int heifgpu_linear_average_apply(const heifgpu_color_transform *t, const uint16_t *rgb_in, uint32_t in_width,
+                                 uint32_t in_height, uint32_t channels, const heifgpu_rect *window, uint32_t out_width,
+                                 uint32_t out_height, uint16_t *rgb_out) {
+    if (!t || !rgb_in || !rgb_out) return fail(HEIFGPU_E_INVALID, "null argument");
+    if (t->tone) return fail(HEIFGPU_E_UNSUPPORTED, "linear-light average of a tone transform");
+    if (t->bits < 8 || t->bits > 12) return fail(HEIFGPU_E_INVALID, "transform depth outside 8..12");
+    if (channels != 3 && channels != 4) return fail(HEIFGPU_E_INVALID, "channels other than 3 or 4");
+    heifgpu_rect w{0, 0, in_width, in_height};
+    if (window && (window->width || window->height)) w = *window;
+    if (!w.width || !w.height || w.x >= in_width || w.y >= in_height || w.width > in_width - w.x ||
+        w.height > in_height - w.y)
+        return fail(HEIFGPU_E_INVALID, "window empty or outside the picture");
+    if (w.width > 65535 || w.height > 65535) return fail(HEIFGPU_E_UNSUPPORTED, "window side above 65535");
+    if (!out_width || !out_height || out_width > 65535 || out_height > 65535)
+        return fail(HEIFGPU_E_INVALID, "rendered size outside 1..65535");
+    const int n = 1 << t->bits;
+    const size_t count = size_t(in_width) * in_height * channels;
+    for (size_t k = 0; k < count; ++k)
+        if (rgb_in[k] >= n) return fail(HEIFGPU_E_INVALID, "code above maxv");
+    std::vector<uint16_t> in_lut(size_t(3) * n);
+    for (int c = 0; c < 3; ++c) std::memcpy(in_lut.data() + size_t(c) * n, t->in_lut[c], size_t(n) * 2);
+    const uint16_t *in = in_lut.data();
+    const XfOutLut<const uint16_t *> out{t->out_lut};
+    const uint64_t cw = w.width, ch = w.height, ow = out_width, oh = out_height;
+    std::vector<uint64_t> col(size_t(cw) * channels);  // a line's column sums: at most 65535 * 65535 each
+    for (uint64_t Y = 0; Y < oh; ++Y) {
+        const uint64_t alo = Y * ch, ahi = alo + ch;
+        std::fill(col.begin(), col.end(), 0);
+        for (uint64_t j = alo / oh; j < (ahi + oh - 1) / oh; ++j) {
+            const uint64_t wy = std::min((j + 1) * oh, ahi) - std::max(j * oh, alo);
+            const uint16_t *row = rgb_in + (size_t(w.y + j) * in_width + w.x) * channels;
+            for (uint64_t i = 0; i < cw; ++i)
+                for (uint32_t c = 0; c < channels; ++c) {
+                    const uint32_t code = row[i * channels + c];
+                    col[i * channels + c] += wy * (c < 3 ? color_linear_level(in, n, int(c), code) : code);
+                }
+        }
+        for (uint64_t X = 0; X < ow; ++X) {
+            const uint64_t blo = X * cw, bhi = blo + cw;
+            uint64_t S[4] = {0, 0, 0, 0};  // below 2^48
+            for (uint64_t i = blo / ow; i < (bhi + ow - 1) / ow; ++i) {
+                const uint64_t wx = std::min((i + 1) * ow, bhi) - std::max(i * ow, blo);
+                for (uint32_t c = 0; c < channels; ++c) S[c] += wx * col[i * channels + c];
+            }
+            uint16_t *o = rgb_out + (size_t(Y) * out_width + X) * channels;
+            uint32_t r, g, b;
+            color_linear_encode(out, t->m, color_linear_mean(S[0], cw * ch), color_linear_mean(S[1], cw * ch),
+                                color_linear_mean(S[2], cw * ch), r, g, b);
+            o[0] = uint16_t(r), o[1] = uint16_t(g), o[2] = uint16_t(b);
+            if (channels == 4) o[3] = uint16_t(color_linear_mean(S[3], cw * ch));
+        }
+    }
+    return HEIFGPU_OK;
+}
+
 // ---- chroma upsampling (include/heifgpu.h): the signalled location, the setting, the rule ----
 int heifgpu_image_get_chroma(const heifgpu_image *img, heifgpu_chroma_info *out) {
     if (!img || !out) return fail(HEIFGPU_E_INVALID, "null argument");

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <initializer_list>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "../common/desc.hpp"
@@ -129,9 +130,11 @@ static void tone_table_image(const heifgpu_color_transform *t, std::vector<uint1
 
 // refs[i] for the images of a render call (empty when no image is to be transformed:
 // the call is then the unmanaged call); tone: some image has a tone transform.  Every
-// check runs before anything is launched.
+// check runs before anything is launched.  linear (the linear-light calls, behind linear_check):
+// every image has a transform and every transform its tables, an identity too.
 static int color_refs_fill(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, uint32_t format,
-                           const heifgpu_color_transform *const *xf, std::vector<ColorRef> &refs, bool &tone) {
+                           const heifgpu_color_transform *const *xf, bool linear, std::vector<ColorRef> &refs,
+                           bool &tone) {
     static_assert(sizeof(ToneBlock) == 16 + 8 * kXfTonePairs && sizeof(ToneBlock) % 8 == 0, "ToneBlock: weights, then pairs");
     refs.clear();
     tone = false;
@@ -148,7 +151,7 @@ static int color_refs_fill(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, s
         if (t->tone && (t->tone != HEIFGPU_TONE_BT2390 || t->identity ||
                         !hdr_transform_valid(*reinterpret_cast<const heifgpu_hdr_transform *>(t))))
             return fail(HEIFGPU_E_INVALID, "tone transform: tag, weights or a level above 2^22 - 1");
-        any = any || !t->identity;
+        any = any || linear || !t->identity;
     }
     if (!any) return HEIFGPU_OK;
     ColorCache *cache = nullptr;
@@ -157,7 +160,7 @@ static int color_refs_fill(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, s
     std::vector<uint16_t> key;
     for (size_t i = 0; i < n; ++i) {
         const heifgpu_color_transform *t = xf[i];
-        if (!t || t->identity) continue;  // lut == 0: untouched
+        if (!t || (t->identity && !linear)) continue;  // lut == 0: untouched
         const size_t tn = size_t(1) << t->bits;
         int32_t tone_off = 0;
         if (t->tone) {
@@ -302,27 +305,35 @@ static int submit(heifgpu_ctx *ctx, const std::vector<Desc> &descs, std::initial
 // call is set to bilinear chroma upsampling (image_chroma_up: the setting window_source_rect
 // reads too) the call goes to the kernels that know it: a ChromaRef per image follows the
 // ColorRefs, which are then always there (lut == 0 for an image without a transform).
+// linear (Desc = ScaleDesc or TensorDesc, behind linear_check): the call goes to the kernels that
+// average in linear light, which always read a ColorRef with tables and a ChromaRef per image.
 template <class Desc>
 static int render_submit(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, const std::vector<Desc> &descs,
                          int max_tiles, uint32_t format, int bps, const heifgpu_color_transform *const *xf,
-                         void *stream) {
+                         void *stream, bool linear = false) {
     static_assert(sizeof(ColorRef) % 8 == 0, "the ChromaUps behind the ColorRefs are 8-byte aligned");
     static_assert(sizeof(ChromaUp) == sizeof(ChromaRef), "ChromaUp is ChromaRef's image");
     if (!ctx) return fail(HEIFGPU_E_INVALID, "null context");
     const size_t n = descs.size();
     std::vector<ColorRef> refs;
     bool tone = false;
-    if (int rc = color_refs_fill(ctx, imgs, n, format, xf, refs, tone)) return rc;
+    if (int rc = color_refs_fill(ctx, imgs, n, format, xf, linear, refs, tone)) return rc;
     std::vector<ChromaUp> ups;
     bool any_up = false;
     for (size_t i = 0; i < n; ++i) any_up = any_up || image_chroma_up(imgs[i]->img).mode != 0;
-    if (any_up) {
+    if (any_up || linear) {
         if (refs.empty()) refs.assign(n, ColorRef{});
         ups.resize(n);
         for (size_t i = 0; i < n; ++i) ups[i] = image_chroma_up(imgs[i]->img);
     }
     const int nn = int(n), fmt = int(format);
     const int color = any_up ? RENDER_CHROMA : refs.empty() ? RENDER_PLAIN : tone ? RENDER_TONE : RENDER_MANAGED;
+    if constexpr (std::is_same<Desc, ScaleDesc>::value || std::is_same<Desc, TensorDesc>::value) {
+        if (linear)
+            return submit(ctx, descs, {{refs.data(), refs.size() * sizeof(ColorRef)}, {ups.data(), ups.size() * sizeof(ChromaUp)}},
+                          [=](const Desc *dev, hipStream_t s) { return launch_render_linear(dev, nn, max_tiles, fmt, bps, s); },
+                          stream);
+    }
     return submit(ctx, descs, {{refs.data(), refs.size() * sizeof(ColorRef)}, {ups.data(), ups.size() * sizeof(ChromaUp)}},
                   [=](const Desc *dev, hipStream_t s) { return launch_render(dev, nn, max_tiles, fmt, bps, color, s); },
                   stream);
@@ -458,11 +469,33 @@ static int scale_desc_fill(size_t i, const heifgpu_image *const *imgs, const hei
     return HEIFGPU_OK;
 }
 
+// What the two linear-light calls refuse beside their siblings' checks (include/heifgpu.h
+// "Linear-light scaled render"), before the context is looked at: an image without a transform
+// (an identity transform is applied here, not skipped), one made for another depth, a tone stage.
+static int linear_check(const heifgpu_image *const *imgs, size_t n, uint32_t format,
+                        const heifgpu_color_transform *const *xf) {
+    if (!xf) return fail(HEIFGPU_E_INVALID, "linear-light render without transforms");
+    for (size_t i = 0; i < n; ++i) {
+        if (!imgs[i]) return fail(HEIFGPU_E_INVALID, "null image");
+        const heifgpu_color_transform *t = xf[i];
+        if (!t) return fail(HEIFGPU_E_INVALID, "linear-light render of an image without a transform");
+        heifgpu_image_info info;
+        heifgpu_image_get_info(imgs[i], &info);
+        const uint32_t depth = format >= HEIFGPU_PIX_RGB16 ? info.bit_depth : 8;
+        if (t->bits != depth || t->bits < 8 || t->bits > 12)
+            return fail(HEIFGPU_E_INVALID, "transform made for another depth than the image is rendered at");
+        if (t->tone) return fail(HEIFGPU_E_UNSUPPORTED, "linear-light render of a tone transform");
+    }
+    return HEIFGPU_OK;
+}
+
 static int render_scaled_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
                               const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in, uint32_t format,
                               const heifgpu_scale *scale, const heifgpu_color_transform *const *xf,
-                              const heifgpu_surface *out, void *stream) {
+                              const heifgpu_surface *out, void *stream, bool linear = false) {
     if (int rc = call_check(imgs && in && scale && out, n, format_outside(format, 0, HEIFGPU_PIX_RGBA16))) return rc;
+    if (linear)
+        if (int rc = linear_check(imgs, n, format, xf)) return rc;
     std::vector<ScaleDesc> descs(n);
     int bps = 0, max_tiles = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -470,7 +503,7 @@ static int render_scaled_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs
             return rc;
         max_tiles = std::max(max_tiles, descs[i].r.tiles);
     }
-    return render_submit(ctx, imgs, descs, max_tiles, format, bps, xf, stream);
+    return render_submit(ctx, imgs, descs, max_tiles, format, bps, xf, stream, linear);
 }
 
 int heifgpu_render_batch_scaled(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
@@ -527,8 +560,10 @@ static int render_tensor_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs
                               const heifgpu_image *const *alpha_imgs, const heifgpu_planes *alpha_in,
                               const heifgpu_tensor_format *fmt, const heifgpu_scale *scale, const uint32_t *flip,
                               const heifgpu_color_transform *const *xf, const heifgpu_tensor_surface *out,
-                              void *stream) {
+                              void *stream, bool linear = false) {
     if (int rc = call_check(imgs && in && fmt && scale && out, n, tensor_format_invalid(fmt))) return rc;
+    if (linear)
+        if (int rc = linear_check(imgs, n, fmt->src, xf)) return rc;
     std::vector<TensorDesc> descs(n);
     int bps = 0, max_tiles = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -539,7 +574,7 @@ static int render_tensor_impl(heifgpu_ctx *ctx, const heifgpu_image *const *imgs
         if (int rc = tensor_out_fill(*fmt, out[i], fl, td)) return rc;
         max_tiles = std::max(max_tiles, td.s.r.tiles);
     }
-    return render_submit(ctx, imgs, descs, max_tiles, fmt->src, bps, xf, stream);
+    return render_submit(ctx, imgs, descs, max_tiles, fmt->src, bps, xf, stream, linear);
 }
 
 int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n, const heifgpu_planes *in,
@@ -547,6 +582,23 @@ int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *im
                                 const heifgpu_tensor_format *fmt, const heifgpu_scale *scale, const uint32_t *flip,
                                 const heifgpu_tensor_surface *out, void *stream) {
     return render_tensor_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, fmt, scale, flip, nullptr, out, stream);
+}
+
+int heifgpu_render_batch_scaled_linear(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                       const heifgpu_planes *in, const heifgpu_image *const *alpha_imgs,
+                                       const heifgpu_planes *alpha_in, uint32_t format, const heifgpu_scale *scale,
+                                       const heifgpu_color_transform *const *xf, const heifgpu_surface *out,
+                                       void *stream) {
+    return render_scaled_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, format, scale, xf, out, stream, true);
+}
+
+int heifgpu_render_batch_tensor_linear(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                       const heifgpu_planes *in, const heifgpu_image *const *alpha_imgs,
+                                       const heifgpu_planes *alpha_in, const heifgpu_tensor_format *fmt,
+                                       const heifgpu_scale *scale, const uint32_t *flip,
+                                       const heifgpu_color_transform *const *xf, const heifgpu_tensor_surface *out,
+                                       void *stream) {
+    return render_tensor_impl(ctx, imgs, n, in, alpha_imgs, alpha_in, fmt, scale, flip, xf, out, stream, true);
 }
 
 // ---- the filtered renders (k_render_resampled) ----

@@ -79,6 +79,32 @@ HG_XF_HD void color_xform_px(Lut in_lut, int n, const Out &out_lut, const int32_
     color_xform_linear(out_lut, m, l0, l1, l2, r, g, b);
 }
 
+// ---- the linear-light scaled render (include/heifgpu.h, "Linear-light scaled render") ----
+// The order is the other one: every source sample of the window goes through in_lut BEFORE
+// the area sum (color_linear_level, three table reads per sample), the rounded mean levels
+// Lm go through the matrix and out_lut AFTER the quotient (color_linear_encode).  Called by
+// k_render_scaled's kRenderLinear instantiations and by heifgpu_linear_average_apply
+// (api/image.cpp); tests/linear_ref.py restates the whole in numpy.
+//   S_c  = sum_j sum_i wy(Y,j) wx(X,i) in_lut[c][code_c(j,i)]     (below 2^48: sides and levels at most 65535)
+//   Lm_c = floor((2 S_c + cw ch) / (2 cw ch))                     (round half up; 0..65535)
+
+// the per-sample step: channel c's code as its linear level
+template <typename Lut>
+HG_XF_HD uint32_t color_linear_level(Lut in_lut, int n, int c, uint32_t code) {
+    return in_lut[c * n + (int)code];
+}
+
+// the rounded mean level of a full sum S over a window of cwch = cw * ch pixels, in plain
+// integers (the kernel takes the same quotient from a double estimate corrected exactly)
+HG_XF_HD uint32_t color_linear_mean(uint64_t S, uint64_t cwch) { return (uint32_t)((2 * S + cwch) / (2 * cwch)); }
+
+// the level-to-code step: three mean levels through the matrix and out_lut
+template <typename Out>
+HG_XF_HD void color_linear_encode(const Out &out_lut, const int32_t (&m)[9], uint32_t lm0, uint32_t lm1, uint32_t lm2,
+                                  uint32_t &r, uint32_t &g, uint32_t &b) {
+    color_xform_linear(out_lut, m, (int64_t)lm0, (int64_t)lm1, (int64_t)lm2, r, g, b);
+}
+
 // ---- the tone stage of an HDR source (include/heifgpu.h, "HDR render") ----------
 //   L_c   = in_lut32[c][code_c]                       (u32 below 2^22; 65535 = 203 cd/m2)
 //   Y     = (w0 L_0 + w1 L_1 + w2 L_2 + 8192) >> 14   (w in Q14, sum 16384: Y below 2^22 too)

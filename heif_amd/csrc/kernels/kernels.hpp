@@ -136,6 +136,9 @@ constexpr int kRenderXf = 4;  // added to a kernel's format parameter: the colou
 constexpr int kRenderTone = 8;  // added beside kRenderXf: the instantiation that also knows the tone stage of HDR sources
 // added beside both: the instantiations that also know bilinear chroma upsampling (ChromaRef)
 constexpr int kRenderChromaUp = 16;
+// read by k_render_scaled only: the instantiations that average in linear light (render_linear.hip;
+// include/heifgpu.h "Linear-light scaled render"), always with kRenderXf and kRenderChromaUp
+constexpr int kRenderLinear = 32;
 constexpr int kRenderTile = 64;                   // axis-swapping images: 64 x 64 output pixels per workgroup
 constexpr int kRenderRowW = 256, kRenderRowH = 16;  // the others: 256 x 16
 struct RenderDesc {
@@ -437,6 +440,12 @@ hipError_t launch_render_chroma<ResampleDesc>(const ResampleDesc *descs, int n_i
 template <>
 hipError_t launch_render_chroma<ResampleTensorDesc>(const ResampleTensorDesc *descs, int n_images, int max_tiles,
                                                     int format, int bytes_per_sample, hipStream_t s);
+// the linear-light scaled renders: the kRenderLinear instantiations of k_render_scaled, a code object
+// of their own (render_linear.hip).  Desc: ScaleDesc or TensorDesc; behind the n_images descriptors a
+// ColorRef per image, every one with its tables (lut != 0, no tone), then a ChromaRef per image.
+template <typename Desc>
+hipError_t launch_render_linear(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                                hipStream_t s);
 // k_render_gain (render_gain.hip): one launch over (max_tiles, n_images); n_images RenderDescs with
 // as many GainRefs behind them on the device; format GAIN_*
 hipError_t launch_render_gain(const RenderDesc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,

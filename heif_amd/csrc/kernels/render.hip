@@ -59,7 +59,24 @@
 // convert() forms C' from the clamped 2 x 2 neighbourhood of Cb and of Cr (chroma_up.hpp)
 // in place of the one replicated sample, and k_render_scaled walks its columns with
 // scale_columns_up; everything behind that is unchanged.
+//
+// The linear-light scaled render adds a fourth bit, kRenderLinear, read by k_render_scaled
+// only: the instantiations (kRenderXf | kRenderLinear | kRenderChromaUp, render_linear.hip)
+// that heifgpu_render_batch_scaled_linear and _tensor_linear launch whatever the batch's mix.
+// Stage 1 sends every clipped R, G, B through the image's in_lut before the weighted add (three
+// table reads per source sample; alpha not), the quotients are 16-bit levels in the wide tile
+// layout for every format, and the pass behind them runs the matrix and out_lut and packs the
+// codes as the stores read them (include/heifgpu.h "Linear-light scaled render").
 #include <type_traits>
+
+// where the linear instantiations read in_lut in stage 1: LDS (1) or global gathers (0); both
+// staged, as measured on the MI355X
+#if !defined(HG_LIN_LDS8)
+#define HG_LIN_LDS8 1
+#endif
+#if !defined(HG_LIN_LDS16)
+#define HG_LIN_LDS16 1
+#endif
 
 #include "color_xform.hpp"
 #include "kernels.hpp"
@@ -194,9 +211,10 @@ void launch_fmt(const RenderDesc *descs, dim3 grid, int format, hipStream_t s) {
 // of output line a, weighted.  The loads of kScaleRowGroup rows are issued before the
 // first of them is used (rows past the end load the last one again and are skipped); a chroma
 // row is loaded when the walk enters it and serves the luma rows that follow in it.
-template <typename Pel, int FMT>
+// (LIN, lin: scale_acc's, for the kRenderLinear instantiations)
+template <typename Pel, int FMT, bool LIN = false, typename Lin = NoLin>
 __device__ __forceinline__ void scale_columns(const ScaleDesc &s, int x0, int x1, int ka0, int ka1, uint32_t alo,
-                                              uint32_t ahi, uint32_t (&sum)[2][4]) {
+                                              uint32_t ahi, uint32_t (&sum)[2][4], const Lin &lin = Lin{}) {
     constexpr int G = kScaleRowGroup;
     const RenderDesc &d = s.r;
     const int sx = chroma_sx(d.chroma), sy = chroma_sy(d.chroma);
@@ -244,7 +262,7 @@ __device__ __forceinline__ void scale_columns(const ScaleDesc &s, int x0, int x1
             if (k >= ka1) break;  // (uniform; the repeated rows past the end were loaded for nothing)
             if (enter[g]) cc = lc[g];
             const uint32_t w = min((uint32_t)(k + 1) * oa, ahi) - max((uint32_t)k * oa, alo);
-            scale_acc<FMT>(d, ly[g], cc, la[g], w, sum);
+            scale_acc<FMT, false, LIN>(d, ly[g], cc, la[g], w, sum, lin);
         }
     }
 }
@@ -259,9 +277,9 @@ struct ScaleChromaRow {
     int cb[2][2], cr[2][2];  // [column][tap], as loaded
 };
 
-template <typename Pel, int FMT>
+template <typename Pel, int FMT, bool LIN = false, typename Lin = NoLin>
 __device__ __forceinline__ void scale_columns_up(const ScaleDesc &s, const ChromaRef &cu, int x0, int x1, int ka0, int ka1,
-                                                 uint32_t alo, uint32_t ahi, uint32_t (&sum)[2][4]) {
+                                                 uint32_t alo, uint32_t ahi, uint32_t (&sum)[2][4], const Lin &lin = Lin{}) {
     constexpr int G = kScaleRowGroup;
     const RenderDesc &d = s.r;
     const uint32_t oa = (uint32_t)s.oa;
@@ -328,7 +346,7 @@ __device__ __forceinline__ void scale_columns_up(const ScaleDesc &s, const Chrom
                 cc.cr[c] = chroma_value(r0.cr[c][0], r0.cr[c][1], r1.cr[c][0], r1.cr[c][1], tx[c], ty[g]);
             }
             const uint32_t w = min((uint32_t)(k + 1) * oa, ahi) - max((uint32_t)k * oa, alo);
-            scale_acc<FMT, true>(d, ly[g], cc, la[g], w, sum);
+            scale_acc<FMT, true, LIN>(d, ly[g], cc, la[g], w, sum, lin);
         }
     }
 }
@@ -344,16 +362,34 @@ __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
     constexpr bool CUP = (FMTX & kRenderChromaUp) != 0;
     constexpr bool TENSOR = std::is_same<Desc, TensorDesc>::value;  // (else ScaleDesc: the integer surfaces)
     constexpr bool WIDE = FMT >= RENDER_RGB16;
+    // the linear-light instantiations (render_linear.hip): stage 1 sums in_lut's levels, the
+    // quotients are 16-bit levels for every format (WRES: two dwords per pixel in the result
+    // tile), and the pass behind them encodes into the format's own layout
+    constexpr bool LIN = (FMTX & kRenderLinear) != 0;
+    constexpr bool WRES = WIDE || LIN;
+    // in_lut staged into LDS (HG_LIN_LDS8: the 1.5 KiB of the 8-bit formats; HG_LIN_LDS16: the 6 to
+    // 24 KiB of the 16-bit ones) or gathered where it lies in global memory; DESIGN 5.38 has the A/B
+    constexpr bool STAGE = LIN && (WIDE ? HG_LIN_LDS16 != 0 : HG_LIN_LDS8 != 0);
     constexpr int NCH = (FMT & 1) ? 4 : 3;
     constexpr int RES = kScaleTile * (kScaleTile + 1);  // dwords: 64 lines of pitch 65 (>= 8 lines of pitch 256)
     __shared__ uint32_t colsum[4 * kScaleCols];
-    __shared__ uint32_t res[(WIDE ? 2 : 1) * RES];
+    __shared__ uint32_t res[(WRES ? 2 : 1) * RES];
     const Desc dd = descs[blockIdx.y];
     const ScaleDesc &s = scale_of(dd);
     const RenderDesc &d = s.r;
     if ((int)blockIdx.x >= d.tiles) return;  // (a smaller image of the batch: the whole workgroup leaves)
     const ChromaRef cu = chroma_ref_of<CUP>(descs);
     const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    // a linear call's ColorRef always has a table (an identity transform is applied here)
+    ColorRef lx{};
+    if constexpr (LIN) lx = reinterpret_cast<const ColorRef *>(descs + gridDim.y)[blockIdx.y];
+    __shared__ uint32_t lin_lds[STAGE ? 3 * (WIDE ? 4096 : 256) / 2 : 1];
+    if constexpr (STAGE) {
+        // once per workgroup, before the first a-line: 3 * n entries of 16 bits, n a multiple of 256
+        const uint32_t __attribute__((address_space(1))) *src = (const uint32_t __attribute__((address_space(1))) *)lx.lut;
+        for (int i = t; i < 3 * lx.n / 2; i += 256) lin_lds[i] = src[i];
+        __syncthreads();
+    }
     const int a0 = ((int)blockIdx.x / d.tiles_x) * s.na, b0 = ((int)blockIdx.x % d.tiles_x) * s.nb;
     const int a1 = min(a0 + s.na, s.oa), b1 = min(b0 + s.nb, s.ob);
     const uint32_t ca = (uint32_t)s.ca, cb = (uint32_t)s.cb, oa = (uint32_t)s.oa, ob = (uint32_t)s.ob;
@@ -381,8 +417,18 @@ __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
                 uint32_t sum[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
                 bool up = false;
                 if constexpr (CUP) up = cu.mode != 0;  // (uniform)
-                if (up) scale_columns_up<Pel, FMT>(s, cu, x0c, x1c, ka0, ka1, alo, ahi, sum);
-                else scale_columns<Pel, FMT>(s, x0c, x1c, ka0, ka1, alo, ahi, sum);
+                if constexpr (STAGE) {
+                    const LinLut<const uint16_t *> lin{reinterpret_cast<const uint16_t *>(lin_lds), lx.n};
+                    if (up) scale_columns_up<Pel, FMT, true>(s, cu, x0c, x1c, ka0, ka1, alo, ahi, sum, lin);
+                    else scale_columns<Pel, FMT, true>(s, x0c, x1c, ka0, ka1, alo, ahi, sum, lin);
+                } else if constexpr (LIN) {
+                    const LinLut<XfLut> lin{(XfLut)lx.lut, lx.n};
+                    if (up) scale_columns_up<Pel, FMT, true>(s, cu, x0c, x1c, ka0, ka1, alo, ahi, sum, lin);
+                    else scale_columns<Pel, FMT, true>(s, x0c, x1c, ka0, ka1, alo, ahi, sum, lin);
+                } else {
+                    if (up) scale_columns_up<Pel, FMT>(s, cu, x0c, x1c, ka0, ka1, alo, ahi, sum);
+                    else scale_columns<Pel, FMT>(s, x0c, x1c, ka0, ka1, alo, ahi, sum);
+                }
 #pragma unroll
                 for (int c = 0; c < NCH; ++c)
                     reinterpret_cast<uint2 *>(colsum + c * kScaleCols)[t] = make_uint2(sum[0][c], sum[1][c]);
@@ -418,13 +464,33 @@ __global__ void __launch_bounds__(256) k_render_scaled(const Desc *descs) {
                     else if (rem >= (int64_t)s.den) ++q;
                 }
                 const int at = (a - a0) * lp + bl;
-                if (WIDE) reinterpret_cast<uint16_t *>(res)[2 * ((c >> 1) * RES + at) + (c & 1)] = (uint16_t)q;
+                if (WRES) reinterpret_cast<uint16_t *>(res)[2 * ((c >> 1) * RES + at) + (c & 1)] = (uint16_t)q;
                 else reinterpret_cast<uint8_t *>(res)[4 * at + c] = (uint8_t)q;
             }
         }
     }
     __syncthreads();
-    if constexpr (XF) {
+    if constexpr (LIN) {
+        // the tile holds mean levels Lm_0..2 and alpha's mean code, 16 bits each: the matrix and
+        // out_lut (color_linear_encode), then the packed codes where store_row / store_tensor
+        // read them for this format; alpha's quotient passes through
+        typedef const uint32_t __attribute__((address_space(1))) *XfWords;
+        const XfOutPairs<XfWords> out{(XfWords)(lx.lut + 6 * (uint64_t)lx.n)};
+        const int nbv = b1 - b0, cnt = (a1 - a0) * nbv;
+        for (int idx = t; idx < cnt; idx += 256) {
+            const int al = idx / nbv, at = al * lp + (idx - al * nbv);
+            const uint32_t lo = res[at], hi = res[RES + at];
+            uint32_t R, G, B;
+            color_linear_encode(out, lx.m, lo & 0xffffu, lo >> 16, hi & 0xffffu, R, G, B);
+            if (WIDE) {
+                res[at] = R | (G << 16);
+                res[RES + at] = B | (hi & 0xffff0000u);
+            } else {
+                res[at] = R | (G << 8) | (B << 16) | ((hi >> 16) << 24);
+            }
+        }
+        __syncthreads();
+    } else if constexpr (XF) {
         // the transform of the tile's rounded averages, in place in the result tile
         const ColorRef x = reinterpret_cast<const ColorRef *>(descs + gridDim.y)[blockIdx.y];
         if (x.lut) {  // (uniform)
@@ -509,7 +575,10 @@ void launch_fmt(const Desc *descs, dim3 grid, int format, hipStream_t s) {
 #define HG_LAUNCH_FMT(XF, Desc)                                                   \
     template void launch_fmt<uint8_t, XF>(const Desc *, dim3, int, hipStream_t); \
     template void launch_fmt<uint16_t, XF>(const Desc *, dim3, int, hipStream_t)
-#if defined(HG_RENDER_CHROMA_UNIT)
+#if defined(HG_RENDER_LINEAR_UNIT)
+HG_LAUNCH_FMT(kRenderXf | kRenderLinear | kRenderChromaUp, ScaleDesc);
+HG_LAUNCH_FMT(kRenderXf | kRenderLinear | kRenderChromaUp, TensorDesc);
+#elif defined(HG_RENDER_CHROMA_UNIT)
 HG_LAUNCH_FMT(kRenderXf | kRenderTone | kRenderChromaUp, RenderDesc);
 HG_LAUNCH_FMT(kRenderXf | kRenderTone | kRenderChromaUp, ScaleDesc);
 HG_LAUNCH_FMT(kRenderXf | kRenderTone | kRenderChromaUp, TensorDesc);
@@ -529,7 +598,20 @@ HG_LAUNCH_FMT(0, RenderDesc);
 
 }  // namespace
 
-#if defined(HG_RENDER_CHROMA_UNIT)
+#if defined(HG_RENDER_LINEAR_UNIT)
+// (render_linear.hip: k_render_scaled averaging in linear light; no RenderDesc, no tone)
+template <typename Desc>
+hipError_t launch_render_linear(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,
+                                hipStream_t s) {
+    constexpr int LINEAR = kRenderXf | kRenderLinear | kRenderChromaUp;
+    const dim3 grid((unsigned)max_tiles, (unsigned)n_images);
+    if (bytes_per_sample == 1) launch_fmt<uint8_t, LINEAR>(descs, grid, format, s);
+    else launch_fmt<uint16_t, LINEAR>(descs, grid, format, s);
+    return hipGetLastError();
+}
+template hipError_t launch_render_linear(const ScaleDesc *, int, int, int, int, hipStream_t);
+template hipError_t launch_render_linear(const TensorDesc *, int, int, int, int, hipStream_t);
+#elif defined(HG_RENDER_CHROMA_UNIT)
 // (render_chroma.hip: the instantiations that know everything, bilinear chroma upsampling included)
 template <typename Desc>
 hipError_t launch_render_chroma(const Desc *descs, int n_images, int max_tiles, int format, int bytes_per_sample,

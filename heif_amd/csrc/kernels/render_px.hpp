@@ -346,9 +346,18 @@ struct ScaleChroma {
 // convert()'s arithmetic for the two columns of one source row (samples as loaded),
 // weighted into the column sums; every product has factors below 2^23
 // (UP: cc holds C' of either column, chroma_up.hpp: two sets of products whatever the format)
-template <int FMT, bool UP = false>
+// (LIN: the kRenderLinear instantiations: each clipped R, G, B goes through the image's in_lut,
+// read through lin, before the weighted add, color_linear_level; alpha does not.  A level is at
+// most 65535 and a line's weights sum to a window side, so the sums still fit 32 bits.)
+struct NoLin {};
+template <typename Lut>
+struct LinLut {
+    Lut t;  // in_lut[3][n], in LDS or in global memory
+    int n;
+};
+template <int FMT, bool UP = false, bool LIN = false, typename Lin = NoLin>
 __device__ __forceinline__ void scale_acc(const RenderDesc &d, const int (&ys)[2], const ScaleChroma &cc,
-                                          const int (&al)[2], uint32_t w, uint32_t (&acc)[2][4]) {
+                                          const int (&al)[2], uint32_t w, uint32_t (&acc)[2][4], const Lin &lin = Lin{}) {
     int tr[2] = {0, 0}, tg[2] = {0, 0}, tb[2] = {0, 0};  // the chroma terms of R, G, B
     if (d.chroma) {
         const int n = !UP && chroma_sx(d.chroma) ? 1 : 2;  // a subsampled pair shares its sample: one set of products
@@ -366,9 +375,15 @@ __device__ __forceinline__ void scale_acc(const RenderDesc &d, const int (&ys)[2
         const int R = min(max((yv + tr[c]) >> 16, 0), d.maxv);
         const int G = min(max((yv - tg[c]) >> 16, 0), d.maxv);
         const int B = min(max((yv + tb[c]) >> 16, 0), d.maxv);
-        acc[c][0] += __umul24(w, (uint32_t)R);
-        acc[c][1] += __umul24(w, (uint32_t)G);
-        acc[c][2] += __umul24(w, (uint32_t)B);
+        if constexpr (LIN) {
+            acc[c][0] += __umul24(w, color_linear_level(lin.t, lin.n, 0, (uint32_t)R));
+            acc[c][1] += __umul24(w, color_linear_level(lin.t, lin.n, 1, (uint32_t)G));
+            acc[c][2] += __umul24(w, color_linear_level(lin.t, lin.n, 2, (uint32_t)B));
+        } else {
+            acc[c][0] += __umul24(w, (uint32_t)R);
+            acc[c][1] += __umul24(w, (uint32_t)G);
+            acc[c][2] += __umul24(w, (uint32_t)B);
+        }
         if (FMT & 1) {
             int A = d.maxv;  // opaque
             if (d.alpha) A = d.alpha_shift >= 0 ? al[c] >> d.alpha_shift : al[c] << -d.alpha_shift;

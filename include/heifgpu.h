@@ -465,7 +465,8 @@ int heifgpu_render_batch_tensor(heifgpu_ctx *ctx, const heifgpu_image *const *im
  * kernels/color_xform.hpp is its one statement in code, shared by the kernels and
  * heifgpu_color_apply.  The scaled and tensor renders transform the rounded
  * average R (what heifgpu_render_batch_scaled writes), not each source pixel:
- * averaging in linear light is another feature and is not done here. */
+ * averaging in linear light is another feature, "Linear-light scaled render"
+ * further down, and is not done here. */
 enum { HEIFGPU_CS_SRGB = 0, HEIFGPU_CS_DISPLAY_P3 = 1 };
 enum { HEIFGPU_COLOR_NONE = 0, HEIFGPU_COLOR_ICC = 1, HEIFGPU_COLOR_NCLX = 2 };
 typedef struct {
@@ -1043,6 +1044,73 @@ int heifgpu_resample_apply(const void *in, uint32_t in_width, uint32_t in_height
  * gives heifgpu_window_source_rect of the scale's window. */
 int heifgpu_window_source_rect_resampled(const heifgpu_image *img, const heifgpu_scale *scale, uint32_t filter,
                                          heifgpu_rect *src);
+
+/* ---- Linear-light scaled render: the area average taken in linear light ------
+ * (added within ABI 6: new entry points only; no struct changes.)
+ * The scaled and tensor renders above average the encoded (gamma-coded) R'G'B'
+ * integers, and their _color forms transform the rounded average.  Fine bright
+ * detail on dark ground then comes out too dark: a pixel-pitch black / white
+ * pattern averages to code 128 where a display shows the light of code 188.  The
+ * calls below take the same area average over LINEAR levels instead: decode to
+ * linear before the sum, encode after the quotient.  Opt-in; every other call is
+ * what it was, byte for byte.
+ * Per image, with
+ *   t          a heifgpu_color_transform made for the depth B the render computes at,
+ *   (c_0, c_1, c_2, A)  the integers the unmanaged render gives for a source pixel
+ *              of the window (clap / irot / imir folded in, bilinear chroma when the
+ *              image is set to it),
+ *   wy, wx, cw, ch      the weights and window sides of "scaled render" above:
+ *     L_c(j,i) = t.in_lut[c][c_c(j,i)]                               c = 0,1,2   (u16)
+ *     S_c(Y,X) = sum_j sum_i wy(Y,j) * wx(X,i) * L_c(j,i)
+ *     Lm_c     = floor((2*S_c + cw*ch) / (2*cw*ch))                  (round half up; 0..65535)
+ *     L'_k     = clamp((m[3k]*Lm_0 + m[3k+1]*Lm_1 + m[3k+2]*Lm_2 + 8192) >> 14, 0, 65535)
+ *     out_k    = the out_lut interpolation of L'_k, exactly as in "colour-managed render"
+ *     alpha    = the scaled render's average of A, unchanged (straight alpha, codes;
+ *                nothing is premultiplied)
+ * Ranges: a level and a window side are at most 65535, so the weighted sum down one
+ * output line's rows of a column is at most 65535 * 65535 < 2^32, S_c < 2^48 and
+ * 2*S_c + cw*ch < 2^50: 64-bit integers hold everything, and a double-precision
+ * estimate of the quotient corrected in integers is exact.
+ * Consequences: with out = the window's own size S_c = cw*ch*L_c, so Lm_c = L_c and
+ * the result is bit for bit the window of heifgpu_render_batch_color with the same
+ * transform, which for an identity transform is the window of heifgpu_render_batch
+ * (identity includes "every code maps to itself"); a uniform window gives the
+ * per-pixel managed result at any size.
+ * An identity transform is APPLIED here, not skipped: its tables are what makes the
+ * average linear.  Refusals, all before anything is launched and before ctx is
+ * looked at: xf NULL, an xf[i] NULL, or xf[i]->bits not the depth image i is
+ * rendered at: HEIFGPU_E_INVALID; a transform with tone != 0 (PQ / HLG sources):
+ * HEIFGPU_E_UNSUPPORTED; then everything the _color siblings refuse.  Everything
+ * else is theirs too: the arguments, ONE launch and one descriptor copy whatever
+ * the mix of sources, orientations and chroma modes, the descriptor ring, the table
+ * cache.  Not done: the filtered (bilinear / bicubic) renders, premultiplied alpha,
+ * tone transforms and the gain-map renders in linear light.
+ * numpy restates this (tests/linear_ref.py); kernels/color_xform.hpp holds the
+ * per-sample and the level-to-code step, shared by the kernel and
+ * heifgpu_linear_average_apply. */
+int heifgpu_render_batch_scaled_linear(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                       const heifgpu_planes *in,
+                                       const heifgpu_image *const *alpha_imgs,
+                                       const heifgpu_planes *alpha_in,
+                                       uint32_t format, const heifgpu_scale *scale,
+                                       const heifgpu_color_transform *const *xf,
+                                       const heifgpu_surface *out, void *stream);
+int heifgpu_render_batch_tensor_linear(heifgpu_ctx *ctx, const heifgpu_image *const *imgs, size_t n,
+                                       const heifgpu_planes *in,
+                                       const heifgpu_image *const *alpha_imgs,
+                                       const heifgpu_planes *alpha_in,
+                                       const heifgpu_tensor_format *fmt, const heifgpu_scale *scale,
+                                       const uint32_t *flip,
+                                       const heifgpu_color_transform *const *xf,
+                                       const heifgpu_tensor_surface *out, void *stream);
+/* host only: the contract above over rgb_in, in_height x in_width x channels (3 or
+ * 4; the fourth is averaged as codes) interleaved uint16 codes 0..maxv without
+ * padding (a larger code is HEIFGPU_E_INVALID), window NULL or 0, 0 sized: the whole
+ * of it; rgb_out (not rgb_in) receives out_height x out_width x channels.  Sides as
+ * in heifgpu_render_batch_scaled; a tone transform is HEIFGPU_E_UNSUPPORTED. */
+int heifgpu_linear_average_apply(const heifgpu_color_transform *t, const uint16_t *rgb_in, uint32_t in_width,
+                                 uint32_t in_height, uint32_t channels, const heifgpu_rect *window,
+                                 uint32_t out_width, uint32_t out_height, uint16_t *rgb_out);
 
 /* ---- host test hooks (reference unit-test surface) -------------------- */
 size_t heifgpu_remove_emulation_prevention(const uint8_t *in, size_t n, uint8_t *out); /* rbsp_reader.rs:11-39 */

@@ -100,8 +100,11 @@ one process in each of the --runs runs:
                          any resize
 Min and spread (max - min over runs) are reported; nothing is gated.
 
+--linear measures the linear-light scaled renders (heifgpu_render_batch_scaled_linear and
+_tensor_linear) against the encoded-managed calls on the same planes; see linear_main.
+
 usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json]
-                                    [--scaled | --tensor | --color | --filter | --tone | --chroma bilinear | --gain [--scaled] | --jpeg]
+                                    [--scaled | --tensor | --color | --filter | --tone | --chroma bilinear | --gain [--scaled] | --jpeg | --linear]
 """
 import argparse
 import ctypes
@@ -1028,6 +1031,114 @@ def jpeg_main(args):
         pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
 
 
+def linear_main(args):
+    """--linear: the linear-light scaled renders (heifgpu_render_batch_scaled_linear / _tensor_linear,
+    DESIGN 5.38) beside the encoded-managed calls (colorspace="srgb" as before: the rounded average
+    transformed) on the same planes, Display P3 (halfmoonbay's profile) to sRGB, RGB8 and f16 CHW, to
+    224 x 224 (cover) and to 1008 x 756 (stretch, 4 : 1), rotation 0 and 3, and RGB16 of a 10-bit and of a
+    12-bit batch to 224 x 224 (the table placement of the 16-bit formats), the variants alternated in one process
+    in each of the --runs runs.  linear / managed is reported, nothing is gated.  HEIFGPU_LIBRARY
+    naming a build with another table placement (make variant VDEFS=-DHG_LIN_LDS8=0 or
+    -DHG_LIN_LDS16=0) gives the other half of that A/B."""
+    n = args.images
+    dev = torch.device("cuda", 0)
+    ctx = H.DecodeContext(0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+    golden = (ROOT / "tests" / "golden" / "halfmoonbay.heic").read_bytes()
+    g = torch.Generator(device=dev).manual_seed(1)
+
+    def planes_of(dtype, top):
+        ys = [torch.randint(0, top, (HGT, W), generator=g, device=dev, dtype=torch.int32).to(dtype) for _ in range(n)]
+        cs = [[torch.randint(0, top, (HGT // 2, W // 2), generator=g, device=dev, dtype=torch.int32).to(dtype)
+               for _ in range(n)] for _ in range(2)]
+        arr = (_lib.Planes * n)()
+        for i in range(n):
+            for c, t in enumerate((ys[i], cs[0][i], cs[1][i])):
+                arr[i].plane[c] = t.data_ptr()
+                arr[i].pitch[c] = t.stride(0) * t.element_size()
+        return arr, (ys, cs)
+
+    result = {"images": n, "width": W, "height": HGT, "reps": args.reps, "runs": args.runs,
+              "device": torch.cuda.get_device_name(0), "library": os.environ.get("HEIFGPU_LIBRARY", "default"),
+              "transform": "Display P3 profile (halfmoonbay) -> sRGB", "cases": {}}
+    variants, keep = [], []
+    L = _lib.lib
+
+    def add_cases(tag, img, planes, bits, pix, boxes):
+        d = img.display
+        imgs = (ctypes.c_void_p * n)(*[img._h.value] * n)
+        t = img.color_transform("srgb", bits)
+        assert not t.identity
+        xf = (ctypes.c_void_p * n)(*[ctypes.addressof(t)] * n)
+        keep.extend([img, imgs, t, xf])
+        wide = pix >= _lib.PIX_RGB16
+        for box, bw, bh, mode in boxes:
+            sc = (_lib.Scale * n)()
+            for i in range(n):
+                _lib.check(L.heifgpu_scale_fit(ctypes.byref(d), bw, bh, mode, ctypes.byref(sc[i])))
+            out = torch.empty((n, bh, bw, 3), dtype=torch.int16 if wide else torch.uint8, device=dev)
+            surf = (_lib.Surface * n)()
+            for i in range(n):
+                surf[i].pixels, surf[i].pitch = out[i].data_ptr(), out[i].stride(0) * out.element_size()
+            keep.extend([sc, out, surf])
+            for kind, fn in (("managed", L.heifgpu_render_batch_scaled_color), ("linear", L.heifgpu_render_batch_scaled_linear)):
+                def run(fn=fn, sc=sc, surf=surf):
+                    _lib.check(fn(ctx._h, imgs, n, planes, None, None, pix, sc, xf, surf, stream))
+                variants.append((f"scaled{box}_{tag}", kind, run))
+            if wide:
+                continue
+            tout = torch.empty((n, 3, bh, bw), dtype=torch.float16, device=dev)
+            fmt = _lib.TensorFormat(src=pix, elem=_lib.ELEM_F16, layout=_lib.LAYOUT_CHW)
+            for c, (m_, s_) in enumerate(zip((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))):
+                fmt.a[c], fmt.b[c] = 1.0 / (255.0 * s_), -m_ / s_
+            ts = (_lib.TensorSurface * n)()
+            for i in range(n):
+                ts[i].data, ts[i].stride_c, ts[i].stride_y = tout[i].data_ptr(), bh * bw * 2, bw * 2
+            keep.extend([tout, fmt, ts])
+            for kind, fn in (("managed", L.heifgpu_render_batch_tensor_color), ("linear", L.heifgpu_render_batch_tensor_linear)):
+                def trun(fn=fn, sc=sc, ts=ts, fmt=fmt):
+                    _lib.check(fn(ctx._h, imgs, n, planes, None, None, ctypes.byref(fmt), sc, None, xf, ts, stream))
+                variants.append((f"tensor{box}_{tag}", kind, trun))
+
+    planes8, keep8 = planes_of(torch.uint8, 256)
+    for rot in (0, 3):
+        img = H.HeifImage.parse(forced_rotation(golden, rot))
+        big = ("1008", 1008, 756, _lib.FIT_STRETCH) if rot == 0 else ("1008", 756, 1008, _lib.FIT_STRETCH)
+        add_cases(f"rgb8_rot{rot}", img, planes8, 8, _lib.PIX_RGB8, (("224", 224, 224, _lib.FIT_COVER), big))
+    p10 = S.SynthParams(bit_depth=10)
+    colr = S.icc_box(H.HeifImage.parse(golden).icc_profile)
+    img10 = H.HeifImage.parse(S.grid_heic(W, HGT, p10, pictures=[S.picture(p10, 1)] * 48, colr=colr))
+    planes10, keep10 = planes_of(torch.int16, 1024)
+    add_cases("rgb16_10bit", img10, planes10, 10, _lib.PIX_RGB16, (("224", 224, 224, _lib.FIT_COVER),))
+    p12 = S.SynthParams(bit_depth=12)
+    img12 = H.HeifImage.parse(S.grid_heic(W, HGT, p12, pictures=[S.picture(p12, 1)] * 48, colr=colr))
+    planes12, keep12 = planes_of(torch.int16, 4096)
+    add_cases("rgb16_12bit", img12, planes12, 12, _lib.PIX_RGB16, (("224", 224, 224, _lib.FIT_COVER),))
+
+    for *_, fn in variants:  # warm-up (and the tables' one upload)
+        fn()
+    torch.cuda.synchronize()
+    ms = {(name, kind): [] for name, kind, _ in variants}
+    for _ in range(args.runs):
+        for name, kind, fn in variants:
+            ms[(name, kind)].append(timed(fn, args.reps))
+    for name, kind, _ in variants:
+        v = ms[(name, kind)]
+        result["cases"].setdefault(name, {})[kind] = {
+            "ms_per_batch": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
+            "ms_runs": [round(x, 4) for x in v], "spread_ms": round(max(v) - min(v), 4)}
+    for name, r in result["cases"].items():
+        r["linear_over_managed"] = round(r["linear"]["ms_per_batch"] / r["managed"]["ms_per_batch"], 4)
+        r["linear_minus_managed_ms"] = round(r["linear"]["ms_per_batch"] - r["managed"]["ms_per_batch"], 4)
+        print(f"{name}: " + ", ".join(f"{k} {r[k]['ms_per_batch']:.3f} ms (spread {r[k]['spread_ms']:.3f})"
+                                      for k in ("managed", "linear")) + f", linear / managed {r['linear_over_managed']:.3f}",
+              flush=True)
+    print(json.dumps(result))
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=128)
@@ -1043,7 +1154,10 @@ def main():
                     help="measure the render, scaled and filtered calls with chroma upsampling set, beside replicate")
     ap.add_argument("--gain", action="store_true", help="measure the gain-map HDR render (see above)")
     ap.add_argument("--jpeg", action="store_true", help="measure render + encode_jpeg against render + copy + Pillow")
+    ap.add_argument("--linear", action="store_true", help="measure the linear-light scaled renders beside the managed ones")
     args = ap.parse_args()
+    if args.linear:
+        return linear_main(args)
     if args.jpeg:
         return jpeg_main(args)
     if args.gain and args.scaled:
