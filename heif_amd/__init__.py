@@ -994,6 +994,160 @@ class DecodeContext:
             icc_profiles = [o.image.icc_profile for o in outs]
         return self.encode_jpeg(rgb, quality, subsampling, icc_profiles, restart_mcus)
 
+    @staticmethod
+    def _png_first_guess(filtered: int) -> int:
+        """encode_png's first capacity for a picture of `filtered` filtered bytes: eight bits a
+        byte, and per block the code lengths (at most 235 bytes) and the chunk around them (21).
+        Filtered pictures stay far below it; a picture that does not is encoded once more."""
+        return filtered + (filtered // _lib.PNG_BLOCK + 1) * 256 + 64
+
+    def encode_png(self, pictures, bits: Optional[int] = None, filter: str = "adaptive", icc_profiles=None,
+                   srgb: bool = False, cicp=None) -> List[bytes]:
+        """PNG files of a batch of RGB or RGBA pictures of 8 or 16 bits, encoded on the
+        device with heifgpu_png_encode_batch: a fixed number of kernel launches for
+        the whole batch, and only the files cross to the host.  The files are lossless:
+        a reader gets back exactly the samples given, alpha included.  pictures is an
+        (N, h, w, C) device tensor or a list of (h, w, C) device tensors, C 3 or 4,
+        uint8, or int16 / uint16 for the 16-bit formats (sizes may differ; rows may be
+        strided, pixels are packed; one dtype and C per call): what render(),
+        render_scaled() and render_hdr(fmt="rgb16pq") return.  bits is the number of
+        significant bits of 16-bit samples (the image's bit depth; None: 16): sample s
+        is stored as (s << (16 - bits)) | (s >> (2 bits - 16)) with an sBIT chunk, so
+        s = v >> (16 - bits) comes back.  filter "adaptive" picks per row the PNG
+        filter type with the least sum of magnitudes; "none", "sub", "up", "average"
+        or "paeth" forces one.  At most one of: icc_profiles[i] (bytes or None) goes
+        into picture i's iCCP chunk; srgb=True writes an sRGB chunk; cicp=(primaries,
+        transfer, matrix, full_range) writes a cICP chunk.  An HDR PNG is
+        encode_png(render_hdr(outs, gains, fmt="rgb16pq", pq_bits=P), bits=P,
+        cicp=(primaries, 16, 0, 1)), primaries 1 (BT.709), 12 (Display P3) or 9
+        (BT.2020).  The deflate stream is Huffman-coded literals in independent blocks
+        (no matches: long flat regions, such as a fully transparent area, cost one bit
+        per byte).  The output buffers are a first guess; a picture that does not fit
+        is encoded once more with the room its size word states.  The call runs on the
+        current stream and waits for it."""
+        torch = self._torch
+        if filter not in _lib.PNG_FILTERS:
+            raise ValueError(f"filter {filter!r}: one of {sorted(_lib.PNG_FILTERS)}")
+        pics = list(pictures) if isinstance(pictures, (list, tuple)) else [pictures[i] for i in range(len(pictures))]
+        n = len(pics)
+        if icc_profiles is not None and len(icc_profiles) != n:
+            raise ValueError("icc_profiles must have one entry per picture")
+        if (icc_profiles is not None and any(icc_profiles)) + bool(srgb) + (cicp is not None) > 1:
+            raise ValueError("encode_png: at most one of icc_profiles, srgb and cicp")
+        if cicp is not None and (len(cicp) != 4 or any(not 0 <= int(v) <= 255 for v in cicp)):
+            raise ValueError("cicp: four values in 0..255")
+        if n == 0:
+            return []
+        wide_types = (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
+        wide, ch = pics[0].dtype in wide_types, pics[0].shape[-1] if pics[0].dim() == 3 else 0
+        for t in pics:
+            if (t.dtype != pics[0].dtype or (t.dtype != torch.uint8 and not wide) or t.dim() != 3 or t.shape[2] != ch
+                    or ch not in (3, 4) or not t.is_cuda or t.device.index != self.device or t.stride(2) != 1
+                    or t.stride(1) != ch or 0 in t.shape):
+                raise ValueError("encode_png takes (h, w, 3 or 4) uint8 or int16 / uint16 tensors of this context's device, "
+                                 "one dtype and channel count per call, with packed pixels")
+        if bits is None:
+            bits = 16 if wide else 8
+        fmt = (_lib.PIX_RGB16 if wide else 0) | (1 if ch == 4 else 0)
+        opts = _lib.PngOpts(fmt, int(bits), _lib.PNG_FILTERS[filter], 0)
+        bpp = ch * (2 if wide else 1)
+        heads, keep = [], []
+        for i, t in enumerate(pics):
+            col = _lib.PngColour()
+            icc = (icc_profiles[i] if icc_profiles is not None else None) or b""
+            if icc:
+                keep = _lib.u8buf(icc)
+                col.kind, col.icc, col.icc_len = _lib.PNG_COLOUR_ICC, ctypes.cast(keep, ctypes.POINTER(ctypes.c_uint8)), len(icc)
+            elif srgb:
+                col.kind = _lib.PNG_COLOUR_SRGB
+            elif cicp is not None:
+                col.kind = _lib.PNG_COLOUR_CICP
+                col.cicp[:] = [int(v) for v in cicp]
+            ln = ctypes.c_size_t()
+            args = (t.shape[1], t.shape[0], ctypes.byref(opts), ctypes.byref(col))
+            _lib.check(lib.heifgpu_png_header(*args, None, 0, ctypes.byref(ln)))
+            buf = (ctypes.c_uint8 * ln.value)()
+            _lib.check(lib.heifgpu_png_header(*args, buf, ln.value, ctypes.byref(ln)))
+            heads.append(bytes(buf))
+        dev = torch.device("cuda", self.device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        caps = [min(self._png_first_guess(t.shape[0] * (t.shape[1] * bpp + 1)), 2 ** 31 - 16) for t in pics]
+        bodies = [None] * n
+        todo = list(range(n))
+        for _ in range(2):  # the guess, then the stated sizes
+            offs, total = [], 0
+            for i in todo:
+                offs.append(total)
+                total += (caps[i] + 15) // 16 * 16
+            out = torch.empty(total, dtype=torch.uint8, device=dev)
+            sizes = torch.empty(len(todo), dtype=torch.int64, device=dev)
+            src = self._surfaces([pics[i] for i in todo])
+            dst = (_lib.Surface * len(todo))()
+            for k, i in enumerate(todo):
+                dst[k].pixels = out.data_ptr() + offs[k]
+                dst[k].pitch = caps[i]
+            ws = (ctypes.c_uint32 * len(todo))(*[pics[i].shape[1] for i in todo])
+            hs = (ctypes.c_uint32 * len(todo))(*[pics[i].shape[0] for i in todo])
+            _lib.check(lib.heifgpu_png_encode_batch(self._h, len(todo), src, ws, hs, ctypes.byref(opts), dst,
+                                                    ctypes.cast(sizes.data_ptr(), ctypes.POINTER(ctypes.c_uint64)), stream))
+            got = [int(v) & (2 ** 64 - 1) for v in sizes.cpu().tolist()]  # (the copy waits for the kernels)
+            again = []
+            for k, i in enumerate(todo):
+                size = got[k] & ~_lib.PNG_TOO_SMALL
+                if got[k] & _lib.PNG_TOO_SMALL:
+                    caps[i] = size
+                    again.append(i)
+                else:
+                    bodies[i] = bytes(out[offs[k]:offs[k] + size].cpu().numpy())
+            todo = again
+            if not todo:
+                break
+        if todo:
+            raise HeifGpuError(_lib.HEIFGPU_E_DEVICE, "encode_png: a picture did not fit the size the device stated")
+        return [h + s for h, s in zip(heads, bodies)]
+
+    def render_png(self, outs: Sequence[DecodedImage], size=None, mode: str = "cover", windows=None, fmt: str = "rgb8",
+                   alphas: Optional[Sequence[Optional[DecodedImage]]] = None, filter: str = "area",
+                   colorspace: Optional[str] = None, tone_map: Optional[str] = None, linear: bool = False,
+                   embed_icc: bool = True, icc_profiles=None) -> List[bytes]:
+        """The PNG files of a batch of decoded images: render() (render_scaled() when
+        size or windows is given; windows need a size) in `fmt` ("rgb8", "rgba8",
+        "rgb16", "rgba16", with alphas as there), then encode_png(), all on the
+        device: the file holds exactly the render's pixels.  The 16-bit formats need
+        one bit depth in the batch, which becomes encode_png's bits.  `filter` is the
+        resize filter of render_scaled(); the PNG row filter is adaptive.  With
+        colorspace "srgb" the files carry an sRGB chunk, with "display-p3" a cICP chunk
+        of (12, 13, 0, 1).  With colorspace None and embed_icc, each item's own ICC
+        profile (HeifImage.icc_profile, when it has one) goes into an iCCP chunk; an
+        nclx-only item gets no colour chunk.  icc_profiles (one profile or None per
+        image) are embedded as given instead, whatever the colorspace.  linear (with a
+        size) as in render_scaled()."""
+        if windows is not None and size is None:
+            raise ValueError("render_png: windows need a size")
+        if fmt not in ("rgb8", "rgba8", "rgb16", "rgba16"):
+            raise ValueError(f"render_png: fmt {fmt!r}: one of rgb8, rgba8, rgb16, rgba16")
+        self._check_linear("render_png", linear, colorspace, filter, tone_map, size)
+        bits = 8
+        if fmt.endswith("16"):
+            depths = {o.info.bit_depth for o in outs}
+            if len(depths) > 1:
+                raise ValueError(f"render_png: {fmt} needs one bit depth in the batch, got {sorted(depths)}")
+            bits = depths.pop() if depths else 16
+        if size is not None:
+            px = self.render_scaled(outs, size, mode, fmt, alphas, windows, colorspace=colorspace, filter=filter,
+                                    tone_map=tone_map, linear=linear)
+        else:
+            px = self.render(outs, fmt, alphas, colorspace=colorspace, tone_map=tone_map)
+        srgb, cicp = False, None
+        if icc_profiles is None:
+            if colorspace == "srgb":
+                srgb = True
+            elif colorspace == "display-p3":
+                cicp = (12, 13, 0, 1)
+            elif colorspace is None and embed_icc:
+                icc_profiles = [o.image.icc_profile for o in outs]
+        return self.encode_png(px, bits, "adaptive", icc_profiles, srgb, cicp)
+
     def render_tensor(self, outs: Sequence[DecodedImage], size, mode: str = "cover", dtype=None, layout: str = "chw",
                       mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), src: str = "rgb8", windows=None,
                       flips=None, alphas: Optional[Sequence[Optional[DecodedImage]]] = None, scale_bias=None,
@@ -1289,6 +1443,27 @@ class HeicDecoder:
         return cls.context(device).render_jpeg([out], size, mode, None, filter, colorspace, tone_map, quality, subsampling,
                                                embed_icc, None if icc_profile is None else [icc_profile], restart_mcus,
                                                linear)[0]
+
+    @classmethod
+    def decode_png(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, size=None, mode: str = "cover",
+                   tiles: str = "all", filter: str = "area", colorspace: Optional[str] = None,
+                   tone_map: Optional[str] = None, linear: bool = False, embed_icc: bool = True,
+                   icc_profile: Optional[bytes] = None) -> bytes:
+        """One HEIC file as one PNG file: decodes the primary image and, when it has
+        one, its alpha plane, then DecodeContext.render_png of that one picture (its
+        arguments; icc_profile is render_png's icc_profiles for the one picture).
+        fmt None picks the format as decode_display does: RGBA when the file has
+        alpha, 16 bits (with an sBIT chunk of the bit depth) above 8.  tiles="window"
+        decodes only the grid tiles the rendered window reads, as there."""
+        DecodeContext._check_tone(colorspace, tone_map)
+        DecodeContext._check_linear("decode_png", linear, colorspace, filter, tone_map, size)
+        with_alpha = fmt is None or fmt.startswith("rgba")
+        out, alpha = cls._decode_pair(data, device, size, mode, tiles, with_alpha, filter)
+        if fmt is None:
+            fmt = ("rgba" if alpha is not None else "rgb") + ("16" if out.info.bit_depth > 8 else "8")
+        alphas = [alpha] if alpha is not None and fmt.startswith("rgba") else None
+        return cls.context(device).render_png([out], size, mode, None, fmt, alphas, filter, colorspace, tone_map, linear,
+                                              embed_icc, None if icc_profile is None else [icc_profile])[0]
 
     @classmethod
     def decode_hdr(cls, data: bytes, fmt: Optional[str] = None, device: int = 0, colorspace: str = "display-p3",

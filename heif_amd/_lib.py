@@ -277,6 +277,24 @@ JPEG_444, JPEG_420 = 0, 1
 JPEG_SUBSAMPLINGS = {"4:4:4": JPEG_444, "4:2:0": JPEG_420}
 JPEG_TOO_SMALL = 1 << 63  # a bit of heifgpu_jpeg_encode_batch's sizes
 
+
+class PngOpts(ctypes.Structure):
+    """heifgpu_png_opts: a render format, the significant bits of a 16-bit one, filter 0..5."""
+    _fields_ = [("format", ctypes.c_uint32), ("bits", ctypes.c_uint32), ("filter", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class PngColour(ctypes.Structure):
+    """heifgpu_png_colour: which of sRGB / cICP / iCCP the header carries."""
+    _fields_ = [("kind", ctypes.c_uint32), ("cicp", ctypes.c_uint8 * 4), ("icc", ctypes.POINTER(ctypes.c_uint8)),
+                ("icc_len", ctypes.c_size_t)]
+
+
+PNG_COLOUR_NONE, PNG_COLOUR_SRGB, PNG_COLOUR_CICP, PNG_COLOUR_ICC = 0, 1, 2, 3
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+PNG_TOO_SMALL = 1 << 63  # a bit of heifgpu_png_encode_batch's sizes
+PNG_BLOCK = 32768        # filtered bytes per deflate block (one IDAT chunk each)
+
 PARSE_AUTO, PARSE_LANES, PARSE_SOLO, PARSE_SPREAD = 0, 1, 2, 3
 PARSE_ROWS = 4  # ABI 5 only; removed in ABI 6 (prepare answers HEIFGPU_E_UNSUPPORTED)
 PARSE_MODES = {"auto": PARSE_AUTO, "lanes": PARSE_LANES, "solo": PARSE_SOLO, "spread": PARSE_SPREAD}
@@ -307,6 +325,7 @@ EXPORTS = (
     "heifgpu_render_batch_gain", "heifgpu_render_batch_gain_scaled", "heifgpu_gain_average",
     "heifgpu_jpeg_quant_tables", "heifgpu_jpeg_header", "heifgpu_jpeg_encode_host", "heifgpu_jpeg_encode_batch",
     "heifgpu_render_batch_scaled_linear", "heifgpu_render_batch_tensor_linear", "heifgpu_linear_average_apply",
+    "heifgpu_png_header", "heifgpu_png_encode_host", "heifgpu_png_encode_batch",
 )
 
 
@@ -433,6 +452,10 @@ def _load() -> ctypes.CDLL:
                                                      P(U32), P(VP), P(TensorSurface), VP]),
         "heifgpu_linear_average_apply": (I32, [P(ColorTransform), P(ctypes.c_uint16), U32, U32, U32, P(Rect), U32, U32,
                                                P(ctypes.c_uint16)]),
+        "heifgpu_png_header": (I32, [U32, U32, P(PngOpts), P(PngColour), u8p, SZ, P(SZ)]),
+        "heifgpu_png_encode_host": (I32, [VP, ctypes.c_int32, U32, U32, P(PngOpts), P(PngColour), u8p, SZ, P(SZ)]),
+        "heifgpu_png_encode_batch": (I32, [VP, SZ, P(Surface), P(U32), P(U32), P(PngOpts), P(Surface),
+                                           P(ctypes.c_uint64), VP]),
     }
     # added within ABI 6: an earlier build of it (HEIFGPU_LIBRARY, a same-box A/B) has one lanes body
     # (and no window decode: DecodeContext.prepare without windows then goes through prepare_ex)
@@ -458,7 +481,9 @@ def _load() -> ctypes.CDLL:
                 "heifgpu_jpeg_encode_batch",
                 # the linear-light scaled renders (linear=True then needs a build that has them)
                 "heifgpu_render_batch_scaled_linear", "heifgpu_render_batch_tensor_linear",
-                "heifgpu_linear_average_apply"}
+                "heifgpu_linear_average_apply",
+                # the PNG output (encode_png / render_png / decode_png then need a build that has it)
+                "heifgpu_png_header", "heifgpu_png_encode_host", "heifgpu_png_encode_batch"}
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue

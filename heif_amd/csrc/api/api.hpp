@@ -1,6 +1,6 @@
 // api.hpp — what the units of the C ABI layer (include/heifgpu.h) share: the two
 // opaque handles every unit looks into, the error message, and the device and
-// pinned buffers.  image.cpp, gain.cpp, context.cpp, render.cpp, jpeg.cpp and batch.cpp hold the calls.
+// pinned buffers.  image.cpp, gain.cpp, context.cpp, render.cpp, jpeg.cpp, png.cpp and batch.cpp hold the calls.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +22,7 @@ constexpr int kTimingSlots = 32;
 struct RenderRing;  // the render calls' descriptor staging
 struct ColorCache;  // the tables of the colour, tone and gain transforms on the device
 struct JpegState;   // the JPEG encoder's scratch and descriptor staging
+struct PngState;    // the PNG encoder's scratch and descriptor staging
 struct heifgpu_ctx {
     int device = 0;
     bool timing = false;
@@ -43,6 +44,8 @@ struct heifgpu_ctx {
     ColorCache *color = nullptr;   // created by the first render that has a table to upload
     // jpeg.cpp's, opaque here; heifgpu_destroy frees it with jpeg_state_free
     JpegState *jpeg = nullptr;     // created by the first heifgpu_jpeg_encode_batch
+    // png.cpp's, likewise (png_state_free)
+    PngState *png = nullptr;       // created by the first heifgpu_png_encode_batch
 };
 
 namespace hg {
@@ -127,5 +130,7 @@ hipError_t fold_timing(heifgpu_ctx *ctx, int slot);
 void render_state_free(heifgpu_ctx *ctx);
 // deletes ctx->jpeg (jpeg.cpp)
 void jpeg_state_free(heifgpu_ctx *ctx);
+// deletes ctx->png (png.cpp)
+void png_state_free(heifgpu_ctx *ctx);
 
 }  // namespace hg

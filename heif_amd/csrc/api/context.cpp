@@ -91,6 +91,7 @@ void heifgpu_destroy(heifgpu_ctx *ctx) {
     if (ctx->prep) (void)hipStreamDestroy(ctx->prep);
     render_state_free(ctx);
     jpeg_state_free(ctx);
+    png_state_free(ctx);
     delete ctx;
 }
 

@@ -892,6 +892,65 @@ int heifgpu_jpeg_encode_batch(heifgpu_ctx *ctx, size_t n, const heifgpu_surface 
                               const uint32_t *height, const heifgpu_jpeg_opts *opts, const heifgpu_surface *out,
                               uint64_t *sizes, void *stream);
 
+/* ---- PNG output: RGB(A) 8- and 16-bit surfaces to PNG files on the device ----
+ * (added within ABI 6: new entry points only.)
+ * The input is what the renders write for HEIFGPU_PIX_RGB8, RGBA8, RGB16 and RGBA16 (a pitch in
+ * bytes, any alignment), so every render option composes with it, alpha and more than 8 bits
+ * included, and the file holds exactly the pixels it was given.  The file is a non-interlaced
+ * PNG of colour type 2 or 6 and bit depth 8 or 16.  A 16-bit surface holds samples of `bits`
+ * significant bits (the image's depth); sample s is stored as (s << (16 - bits)) | (s >> (2 bits
+ * - 16)) with an sBIT chunk of `bits`, so a reader recovers s = v >> (16 - bits).  Rows are
+ * filtered by one of the five PNG filter types (`filter` 0..4) or, with HEIFGPU_PNG_FILTER_ADAPTIVE,
+ * by the type with the least sum of magnitudes per row.  The filtered bytes are deflated in
+ * independent blocks of 32768 bytes, each a dynamic-Huffman block of literals only (no matches:
+ * long flat regions cost a bit per byte) in an IDAT chunk of its own.  The bytes of a file are
+ * fully determined by the pixels and the options: heif_amd/csrc/kernels/png.hpp states every
+ * rule, heifgpu_png_encode_host restates the whole encoder on the host.
+ * A file is heifgpu_png_header's bytes followed by what heifgpu_png_encode_batch writes (the
+ * IDAT chunks and IEND).  A format that is not one of the four, bits outside 8..16 (or not 8 for
+ * an 8-bit format), a filter above 5, a nonzero reserved, a zero side, a side above 65535, a
+ * pitch below width * bytes per pixel, a profile of 0 or more than 0x7fff0000 bytes or n above
+ * 65535 is HEIFGPU_E_INVALID, reported before anything is launched or written. */
+#define HEIFGPU_PNG_FILTER_ADAPTIVE 5u
+typedef struct {
+    uint32_t format;   /* HEIFGPU_PIX_RGB8, RGBA8, RGB16 or RGBA16 */
+    uint32_t bits;     /* significant bits of a 16-bit format's samples, 8..16; 8 for an 8-bit format */
+    uint32_t filter;   /* 0 none, 1 sub, 2 up, 3 average, 4 Paeth, 5 adaptive */
+    uint32_t reserved; /* 0 */
+} heifgpu_png_opts;
+#define HEIFGPU_PNG_COLOUR_NONE 0u
+#define HEIFGPU_PNG_COLOUR_SRGB 1u /* an sRGB chunk, perceptual intent */
+#define HEIFGPU_PNG_COLOUR_CICP 2u /* a cICP chunk of the four bytes of `cicp` */
+#define HEIFGPU_PNG_COLOUR_ICC 3u  /* an iCCP chunk of the profile at `icc` */
+typedef struct {
+    uint32_t kind;
+    uint8_t cicp[4]; /* colour primaries, transfer function, matrix coefficients (0 for RGB), full-range flag */
+    const uint8_t *icc;
+    size_t icc_len;
+} heifgpu_png_colour;
+/* host only: the bytes before the first IDAT (signature, IHDR, sBIT for a 16-bit format of fewer
+ * than 16 bits, and the chunk `colour` selects; NULL selects none) of a width x height picture.
+ * The profile is deflated in stored blocks.  *len receives their length; they are written when
+ * buf is not NULL and cap >= *len. */
+int heifgpu_png_header(uint32_t width, uint32_t height, const heifgpu_png_opts *opts, const heifgpu_png_colour *colour,
+                       uint8_t *buf, size_t cap, size_t *len);
+/* host only: the whole file of one picture in host memory, by the kernels' own rules;
+ * *len and buf as above. */
+int heifgpu_png_encode_host(const void *pixels, int32_t pitch, uint32_t width, uint32_t height,
+                            const heifgpu_png_opts *opts, const heifgpu_png_colour *colour, uint8_t *buf, size_t cap,
+                            size_t *len);
+/* Asynchronous on `stream`: the IDAT chunks and IEND of n pictures (sizes may differ; one set of
+ * options, so one format) in a fixed number of launches.  out[i].pixels receives picture i's
+ * bytes, out[i].pitch is its capacity in bytes.  sizes (n entries, device memory or pinned host
+ * memory the device can write) receives the exact length of every picture's IDAT chunks and
+ * IEND; when that exceeds the capacity, bit 63 of sizes[i] is set as well, nothing at or past the
+ * capacity is written and what was written is to be discarded: the caller encodes that picture
+ * again with room for the stated length.  The call's scratch belongs to the context: a call
+ * waits on the host for the context's previous encode call to finish. */
+int heifgpu_png_encode_batch(heifgpu_ctx *ctx, size_t n, const heifgpu_surface *surfaces, const uint32_t *width,
+                             const uint32_t *height, const heifgpu_png_opts *opts, const heifgpu_surface *out,
+                             uint64_t *sizes, void *stream);
+
 /* ---- window decode: decode only the pictures a window reads ----------------
  * (added within ABI 6: new entry points only; heifgpu_batch_opts keeps its layout.)
  * A render of a window of the displayed picture (heifgpu_scale's x, y, width,

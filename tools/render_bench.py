@@ -103,8 +103,12 @@ Min and spread (max - min over runs) are reported; nothing is gated.
 --linear measures the linear-light scaled renders (heifgpu_render_batch_scaled_linear and
 _tensor_linear) against the encoded-managed calls on the same planes; see linear_main.
 
+--png measures the PNG output (heifgpu_png_encode_batch): render + encode_png of the golden
+picture's planes as rgb8, and of a 10-bit batch as rgba16, against render + copy + Pillow's save() at
+compress_level 1 and 6 on one core; see png_main.
+
 usage: python tools/render_bench.py [--images 128] [--reps 20] [--runs 5] [--out render.json]
-                                    [--scaled | --tensor | --color | --filter | --tone | --chroma bilinear | --gain [--scaled] | --jpeg | --linear]
+                                    [--scaled | --tensor | --color | --filter | --tone | --chroma bilinear | --gain [--scaled] | --jpeg | --png | --linear]
 """
 import argparse
 import ctypes
@@ -1031,6 +1035,157 @@ def jpeg_main(args):
         pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
 
 
+def png_main(args):
+    """--png: n copies of the golden twelve-megapixel picture to PNG files in host memory.
+    "rgb8": render() then encode_png(), the files copied to the host.  "rgba16_10bit": the golden
+    picture's decoded planes shifted up to 10 bits with two seeded random low bits, under a
+    10-bit image of the same geometry, rendered opaque as rgba16 and encoded with bits=10 (the
+    constant alpha is a flat region: a bit per byte).  "cpu_1" / "cpu_6": render(), a surface
+    copied to the host, Pillow's save(compress_level=1 / 6) on one core (for the 16-bit RGBA
+    pictures, which Pillow does not write: a Sub filter in numpy and zlib at that level), over
+    --pillow-pictures pictures and scaled to n (said so in the result).  Wall-clock time per batch; beside it the
+    encode call alone (events around heifgpu_png_encode_batch, buffers allocated beforehand).
+    One picture of "flat" is the flat-region limitation measured: the golden picture with its left
+    half fully transparent black, as rgba8, against Pillow."""
+    import io
+    import time
+    import zlib
+
+    import numpy as np
+    from PIL import Image
+
+    n = args.images
+    dev = torch.device("cuda", 0)
+    ctx = H.DecodeContext(0)
+    golden = (ROOT / "tests" / "golden" / "halfmoonbay.heic").read_bytes()
+    out = H.HeicDecoder.decode(golden)
+    d = out.image.display
+    result = {"images": n, "width": d.out_width, "height": d.out_height, "reps": args.reps, "runs": args.runs,
+              "device": torch.cuda.get_device_name(0)}
+
+    def wall(fn, reps):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3 / reps
+
+    # the 10-bit batch: the golden planes at 10 bits under a synthetic 10-bit image's handle
+    p10 = S.SynthParams(bit_depth=10)
+    img10 = H.HeifImage.parse(S.grid_heic(W, HGT, p10, pictures=[S.picture(p10, 1)] * 48))
+    assert img10.info.bit_depth == 10 and (img10.info.width, img10.info.height) == (W, HGT)
+    g = torch.Generator(device=dev).manual_seed(1)
+
+    def deep(t):
+        low = torch.randint(0, 4, t.shape, generator=g, device=dev, dtype=torch.int32)
+        return ((t.to(torch.int32) << 2) | low).to(torch.int16)
+
+    y10, cb10, cr10 = deep(out.y), deep(out.cb), deep(out.cr)
+    planes10 = (_lib.Planes * n)()
+    for i in range(n):
+        for c, t in enumerate((y10, cb10, cr10)):
+            planes10[i].plane[c] = t.data_ptr()
+            planes10[i].pitch[c] = t.stride(0) * t.element_size()
+    imgs10 = (ctypes.c_void_p * n)(*[img10._h.value] * n)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(0).cuda_stream)
+
+    def render16(m):
+        res = [torch.empty((HGT, W, 4), dtype=torch.int16, device=dev) for _ in range(m)]
+        _lib.check(_lib.lib.heifgpu_render_batch(ctx._h, imgs10, m, planes10, None, None, _lib.PIX_RGBA16,
+                                                 ctx._surfaces(res), stream))
+        return res
+
+    def pillow_png(a, level):
+        b = io.BytesIO()
+        Image.fromarray(a).save(b, "PNG", compress_level=level)
+        return b.getvalue()
+
+    def numpy_zlib_png(a, level):
+        """Pillow writes no 16-bit RGBA: the big-endian replicated samples, every row filtered by Sub
+        in numpy, through zlib at `level` (the IDAT payload a plain CPU writer would make)."""
+        s = a.view(np.uint16).astype(np.uint32)
+        v = ((s << 6) | (s >> 4)).astype(">u2")
+        rows = v.reshape(v.shape[0], -1).view(np.uint8)
+        sub = rows.copy()
+        sub[:, 8:] -= rows[:, :-8]
+        return zlib.compress(np.concatenate([np.ones((rows.shape[0], 1), np.uint8), sub], axis=1).tobytes(), level)
+
+    files = {}
+    routes = {
+        "rgb8": (lambda m: ctx.render([out] * m, "rgb8"), lambda px: ctx.encode_png(px), 3, 8, pillow_png,
+                 "Pillow save(compress_level=L)"),
+        "rgba16_10bit": (render16, lambda px: ctx.encode_png(px, bits=10), 8, 10, numpy_zlib_png,
+                         "numpy Sub filter + zlib level L (Pillow writes no 16-bit RGBA)"),
+    }
+    for name, (render, encode, bpp, bits, cpu_writer, cpu_name) in routes.items():
+        # the encode call alone
+        px = render(n)
+        h, w = px[0].shape[0], px[0].shape[1]
+        cap = ctx._png_first_guess(h * (w * bpp + 1))
+        buf = torch.empty((n, (cap + 15) // 16 * 16), dtype=torch.uint8, device=dev)
+        sizes = torch.empty(n, dtype=torch.int64, device=dev)
+        src, dst = ctx._surfaces(px), (_lib.Surface * n)()
+        for i in range(n):
+            dst[i].pixels, dst[i].pitch = buf[i].data_ptr(), cap
+        ws, hs = (ctypes.c_uint32 * n)(*[w] * n), (ctypes.c_uint32 * n)(*[h] * n)
+        o = _lib.PngOpts(_lib.PIX_RGB8 if bpp == 3 else _lib.PIX_RGBA16, bits, 5, 0)
+
+        def call():
+            _lib.check(_lib.lib.heifgpu_png_encode_batch(ctx._h, n, src, ws, hs, ctypes.byref(o), dst,
+                                                         ctypes.cast(sizes.data_ptr(), ctypes.POINTER(ctypes.c_uint64)), stream))
+
+        call()
+        torch.cuda.synchronize()
+        ms = [timed(call, args.reps) for _ in range(args.runs)]
+        total = int(sizes.sum().item())
+        result[name] = {"encode_call": {"ms_per_batch": round(statistics.median(ms), 3), "ms_min": round(min(ms), 3),
+                                        "ms_max": round(max(ms), 3), "idat_bytes_per_picture": total // n}}
+        print(f"{name}: encode call {statistics.median(ms):.3f} ms per batch of {n} (min {min(ms):.3f}, max {max(ms):.3f}), "
+              f"{total // n} bytes per picture", flush=True)
+        del buf, px
+
+        def device_route():
+            files[name] = encode(render(n))
+
+        device_route()
+        ms = [wall(device_route, 1) for _ in range(min(args.runs, 3))]
+        result[name]["device"] = {"ms_per_batch": round(statistics.median(ms), 2), "ms_min": round(min(ms), 2),
+                                  "ms_max": round(max(ms), 2), "ms_per_picture": round(statistics.median(ms) / n, 3)}
+        result[name]["file_bytes_per_picture"] = {"device": sum(len(f) for f in files[name]) // n}
+        print(f"{name}: render + encode_png {statistics.median(ms):.2f} ms per batch of {n}", flush=True)
+        # the CPU route on one core over a few pictures, scaled to the batch
+        k = max(1, min(args.pillow_pictures, n))
+        result[name]["cpu_writer"] = cpu_name
+        for level in (1, 6):
+            def cpu_route():
+                files[f"{name}_cpu_{level}"] = [cpu_writer(t.cpu().numpy(), level) for t in render(k)]
+            ms1 = wall(cpu_route, 1)
+            result[name][f"cpu_{level}"] = {"pictures_timed": k, "ms_per_picture": round(ms1 / k, 2),
+                                            "ms_per_batch_scaled_to_n": round(ms1 / k * n, 1)}
+            result[name]["file_bytes_per_picture"][f"cpu_{level}"] = sum(len(f) for f in files[f"{name}_cpu_{level}"]) // k
+            print(f"{name}: {cpu_name}, L={level}: {ms1 / k:.1f} ms per picture on one core "
+                  f"({k} timed; {ms1 / k * n:.0f} ms scaled to {n})", flush=True)
+            result[name][f"cpu_{level}_over_device"] = round(result[name][f"cpu_{level}"]["ms_per_batch_scaled_to_n"] /
+                                                             result[name]["device"]["ms_per_batch"], 2)
+        torch.cuda.empty_cache()
+    # the flat-region limitation: the left half fully transparent
+    rgba = ctx.render([out], "rgba8")[0].clone()
+    rgba[:, : rgba.shape[1] // 2] = 0
+    ours = ctx.encode_png([rgba])[0]
+    flat = {"device": len(ours)}
+    for level in (1, 6):
+        b = io.BytesIO()
+        Image.fromarray(rgba.cpu().numpy()).save(b, "PNG", compress_level=level)
+        flat[f"pillow_{level}"] = len(b.getvalue())
+    assert np.array_equal(np.asarray(Image.open(io.BytesIO(ours))), rgba.cpu().numpy())
+    result["flat_half_transparent_rgba8_bytes"] = flat
+    print(json.dumps(result))
+    if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+
+
 def linear_main(args):
     """--linear: the linear-light scaled renders (heifgpu_render_batch_scaled_linear / _tensor_linear,
     DESIGN 5.38) beside the encoded-managed calls (colorspace="srgb" as before: the rounded average
@@ -1155,11 +1310,15 @@ def main():
     ap.add_argument("--gain", action="store_true", help="measure the gain-map HDR render (see above)")
     ap.add_argument("--jpeg", action="store_true", help="measure render + encode_jpeg against render + copy + Pillow")
     ap.add_argument("--linear", action="store_true", help="measure the linear-light scaled renders beside the managed ones")
+    ap.add_argument("--png", action="store_true", help="measure render + encode_png against render + copy + Pillow")
+    ap.add_argument("--pillow-pictures", type=int, default=3, help="--png: pictures Pillow is timed over")
     args = ap.parse_args()
     if args.linear:
         return linear_main(args)
     if args.jpeg:
         return jpeg_main(args)
+    if args.png:
+        return png_main(args)
     if args.gain and args.scaled:
         return gain_scaled_main(args)
     if args.gain:
